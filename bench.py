@@ -16,10 +16,14 @@ mocapv2_amd/pipeline.py).  Other BASELINE.json configs:
 process touches a GPU); `--rehearse-on-one-gpu` lets the N ranks share cuda:0 and exchange through gloo (a check of the
 multi-rank code path on a one-GPU box, not a measurement).
 
-Three batches are in flight on three HIP streams (--depth).  Prints ONE JSON line (rank 0) with the driver's fields plus
-`roofline` (the filter stage against the HBM read roofline, from HIP events recorded on the launch streams),
-`cpu_baseline` (the C oracle on host cores), `parity` (3-D RMSE / centroid mismatches of the timed batch against that
-oracle) and, with one GPU, `extra` sections (32 markers, bright background, 4K) measured the same way.
+Three batches are in flight on three HIP streams (--depth).  Prints ONE JSON line (rank 0) with the driver's fields.  A plain
+run only sets up, warms up and times the K steps.  `--full` adds `roofline` (the filter stage against the HBM read roofline,
+from HIP events recorded on the launch streams in a sequential pass after the timed steps), `cpu_baseline` (the C oracle on
+host cores), `parity` (3-D RMSE / centroid mismatches of the timed batch against that oracle) and, with one GPU, the
+secondary runs and `extra` sections (32 markers, bright background, 4K) measured the same way.
+
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (float64, dump_outputs); the frames come
+from fixed seeds, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -28,6 +32,7 @@ import socket
 import subprocess
 import sys
 import time
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
@@ -65,15 +70,29 @@ def parse_args(argv=None):
     ap.add_argument("--bayer", action="store_true",
                     help="secondary measurement: the resident frames are raw Bayer GR sensor frames and every step starts with the "
                          "Bayer -> gray pre-pass (RealtimeTracking_FLIR.py:103-104); not the headline workload")
-    ap.add_argument("--cpu-steps", type=int, default=256, help="time steps in the CPU baseline / parity sample (0 = skip)")
-    ap.add_argument("--cpu-single-steps", type=int, default=48, help="time steps of the single-thread CPU baseline leg (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: per-kernel / roofline figures, CPU baseline + parity, the secondary runs and the "
+                         "extra workloads (off: set up, warm up, time --steps steps, print the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float64)")
+    ap.add_argument("--cpu-steps", type=int, default=256, help="time steps in the CPU baseline / parity sample (0 = skip; --full)")
+    ap.add_argument("--cpu-single-steps", type=int, default=48, help="time steps of the single-thread CPU baseline leg (0 = skip; --full)")
     ap.add_argument("--batches", type=int, default=3,
                     help="distinct resident batches the timed region rotates through (every image slot sees a different frame from "
                          "one step to the next, so the mask's on-demand clearing and the scan's base probe are inside the measurement)")
     ap.add_argument("--no-secondary", dest="secondary", action="store_false",
-                    help="skip the early-out-off rerun and the other distortion variant")
-    ap.add_argument("--no-extra", dest="extra", action="store_false", help="skip the extra workload sections")
-    return ap.parse_args(argv)
+                    help="with --full: skip the early-out-off rerun and the other distortion variant")
+    ap.add_argument("--no-extra", dest="extra", action="store_false", help="with --full: skip the extra workload sections")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+def render_threads():
+    """Host threads for rendering the synthetic frames: OMP_NUM_THREADS when set, else the CPUs this process may use, at most 16."""
+    n = int(os.environ.get("OMP_NUM_THREADS") or 0)
+    return n if n > 0 else min(16, len(os.sched_getaffinity(0)))
 
 
 def visible_gpu_count():
@@ -155,16 +174,19 @@ class Workload:
                      radius=4.0 if self.spread else 3.0)
 
     def render(self, scene, image_list, seed_base=1000):
-        """uint8 [n, H, W] frames for (camera, global time step) pairs; time step t uses seed seed_base + t."""
+        """uint8 [n, H, W] frames for (camera, global time step) pairs; time step t uses seed seed_base + t.  A frame depends
+        on its own seeds only, so the frames are rendered on a thread pool (NumPy's generators release the GIL while they
+        fill the noise, which is most of the work)."""
         out = np.empty((len(image_list), scene.height, scene.width), np.uint8)
-        cache = {}
-        for i, (c, t) in enumerate(image_list):
-            if t not in cache:
-                rng = np.random.default_rng(seed_base + t)
-                cache = {t: scene.markers(rng, self.markers, extent=1.2 if self.spread else 0.5)}
+
+        def one(i):
+            c, t = image_list[i]
+            markers = scene.markers(np.random.default_rng(seed_base + t), self.markers, extent=1.2 if self.spread else 0.5)
             rng = np.random.default_rng((seed_base + t) * 64 + c)
-            out[i] = scene.render(rng, cache[t], c, radius_range=(16.0, 22.0), noise_min=self.background[0],
+            out[i] = scene.render(rng, markers, c, radius_range=(16.0, 22.0), noise_min=self.background[0],
                                   noise_max=self.background[1], salt=0.001)
+        with ThreadPoolExecutor(render_threads()) as pool:
+            list(pool.map(one, range(len(image_list))))
         return out
 
 
@@ -185,8 +207,6 @@ def cpu_baseline(wl, arrays, frames, n_steps, threads=None):
     (RealtimeTracking_FLIR.py:307-312) -- or on `threads` threads (1 = the single-thread leg of BASELINE.md section 4) --
     then correspondence + DLT.  Returns the rate and every time step's results (image-point lists per camera,
     correspondence output) for the parity comparison."""
-    from concurrent.futures import ThreadPoolExecutor
-
     import oracle
     K, dist, R, t, F = arrays
     C = wl.cameras
@@ -273,6 +293,49 @@ def same_results(rec_a, out_a, rec_b, out_b):
     n = out_a["n"].clamp(min=0)
     roots = torch.arange(out_a["xyz"].shape[1], device=n.device)[None, :] < n[:, None]
     return all(torch.equal(out_a[k][roots], out_b[k][roots]) for k in ("xyz", "grp", "order"))
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, records, out, max_bytes=DUMP_MAX_BYTES):
+    """What one step returned, as DIR/<name>.npy in float64.  Per time step: `n` (root count, < 0 = capacity code) and, for
+    the roots below it, `xyz`, `err`, `grp`, `root`, `order`; per image: `centroid_count` and, below it, `centroids`.  Words
+    beyond a count hold whatever an earlier batch left there and are written as 0.  Above max_bytes in all, a fixed seeded
+    sample of the time steps and of the images is written, with its indices (`sample_time_steps`, `sample_images`).
+    records: int32 [images, 2 + 2 P] (count, pad, (x, y) x P); out: the step's dict of tensors or arrays.  Returns the names."""
+    def host(v):
+        return v.cpu().numpy() if hasattr(v, "cpu") else np.asarray(v)
+    rec = host(records)
+    out = {k: host(v) for k, v in out.items()}
+    n = out["n"]
+    per_step = {"n": n}
+    roots = np.arange(out["xyz"].shape[1])[None, :] < np.maximum(n, 0)[:, None]  # [T, P]
+    for k in ("xyz", "err", "grp", "root", "order"):
+        v = out[k].astype(np.float64)
+        per_step[k] = np.where(roots.reshape(roots.shape + (1,) * (v.ndim - 2)), v, 0.0)
+    cnt = rec[:, 0]
+    P = (rec.shape[1] - 2) // 2
+    live = np.arange(P)[None, :] < np.clip(cnt, 0, P)[:, None]  # [images, P]
+    per_image = {"centroid_count": cnt, "centroids": np.where(live[:, :, None], rec[:, 2:2 + 2 * P].reshape(-1, P, 2), 0)}
+    groups = [("sample_time_steps", per_step), ("sample_images", per_image)]
+    total = 8 * sum(v.size for _, g in groups for v in g.values())
+    if total > max_bytes:
+        total += 8 * sum(len(next(iter(g.values()))) for _, g in groups)  # the index arrays of the sample
+        for seed, (index_name, g) in enumerate(groups):
+            rows = len(next(iter(g.values())))
+            keep = max(1, int(rows * max_bytes / total))
+            pick = np.sort(np.random.default_rng(seed).choice(rows, keep, replace=False))
+            for k in g:
+                g[k] = g[k][pick]
+            g[index_name] = pick
+    os.makedirs(dirname, exist_ok=True)
+    names = []
+    for _, g in groups:
+        for k, v in g.items():
+            np.save(os.path.join(dirname, k + ".npy"), np.ascontiguousarray(v, np.float64))
+            names.append(k)
+    return names
 
 
 def batch_index(i, depth, n_batches):
@@ -391,10 +454,11 @@ def main():
 
     def timed(tracker, batches, steps, warmup):
         """W untimed + K timed steps rotating through the resident batches, barrier + synchronize on both sides, max over
-        ranks.  Then a short sequential pass (one batch at a time, a synchronize after each) for per-kernel durations that
-        are not stretched by the neighbouring batches' kernels (in the timed region `--depth` batches share the chip).
-        Returns the last output, the elapsed time, the profile, and what the timed region left in every lane's buffers:
-        (batch index, records, outputs) of the last batch each lane ran."""
+        ranks.  Then, with --full, a short sequential pass (one batch at a time, a synchronize after each) for per-kernel
+        durations that are not stretched by the neighbouring batches' kernels (in the timed region `--depth` batches share
+        the chip).  Returns the last output, the elapsed time, the profile, what the timed region left in every lane's
+        buffers: (batch index, records, outputs) of the last batch each lane ran, and (records, outputs) of the last timed
+        step."""
         nb = len(batches)
         lane_batch = {}
 
@@ -415,23 +479,26 @@ def main():
         elapsed = time.perf_counter() - t0
         tracker.profile(False)
         prof_timed = tracker.profile_read()
+        last = (tracker.records.clone(), {key: v.clone() for key, v in out.items()})
         left = [(k, tracker.lanes[l].records.clone(), {key: v.clone() for key, v in tracker.lanes[l].out.items()})
                 for l, k in sorted(lane_batch.items()) if tracker.lanes[l].out is not None]
-        n_seq = max(1, min(steps, 6))
-        tracker.profile(True)
-        for _ in range(n_seq):
-            out = one()
-            tracker.synchronize()
-        tracker.profile(False)
-        prof = tracker.profile_read()
-        prof["steps"] = n_seq
+        prof = {}
+        if args.full:
+            n_seq = max(1, min(steps, 6))
+            tracker.profile(True)
+            for _ in range(n_seq):
+                out = one()
+                tracker.synchronize()
+            tracker.profile(False)
+            prof = tracker.profile_read()
+            prof["steps"] = n_seq
+            prof["tiles"], prof["tiles_skipped"] = tracker.ctx.tile_stats()  # of the last step
         prof["timed_region"] = prof_timed
-        prof["tiles"], prof["tiles_skipped"] = tracker.ctx.tile_stats()  # of the last step
         if world > 1:
             tmax = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if args.rehearse_on_one_gpu else "cuda")
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
             elapsed = float(tmax.item())
-        return out, elapsed, prof, left
+        return out, elapsed, prof, left, last
 
     def run_each(tracker, batches):
         """every resident batch once more, one at a time (not timed): (batch index, records, outputs)"""
@@ -464,15 +531,19 @@ def main():
             if k == 0:
                 host = frames_host
             elif all(i is not None for i in idx):
+                if not args.from_host:  # batch 0's frames in another order: gathered on the GPU instead of uploaded again
+                    batches.append(batches[0][torch.tensor(idx, device=batches[0].device)])
+                    continue
                 host = frames_host[np.asarray(idx)]
             else:  # a rank that holds only part of a camera's time steps: render the shifted moments
                 host = wl.render(scene, want)
             batches.append(torch.from_numpy(host).pin_memory() if args.from_host else torch.from_numpy(host).cuda())
             del host
         torch.cuda.synchronize()
-        out, elapsed, prof, left = timed(tracker, batches, steps, warmup)
+        out, elapsed, prof, left, last = timed(tracker, batches, steps, warmup)
         return {"scene": scene, "arrays": arrays, "tracker": tracker, "images": images, "frames_host": frames_host, "batches": batches,
-                "out": out, "elapsed": elapsed, "prof": prof, "T": time_steps, "left": left, "shift": shift, "n_batches": n_batches}
+                "out": out, "elapsed": elapsed, "prof": prof, "T": time_steps, "left": left, "last": last, "shift": shift,
+                "n_batches": n_batches}
 
     def status_of(m):
         """no capacity code in any time step / image of any batch the timed region left behind"""
@@ -678,8 +749,6 @@ def main():
         value = T_STEPS * world * args.steps / elapsed
         std = (main_wl.cameras, main_wl.width, main_wl.height, main_wl.markers, main_wl.background, main_wl.bayer) == \
             (6, 1920, 1080, 8, (0, 60), False)
-        roof = roofline_of(prof, main_wl, len(m["images"]), 1 if world == 1 else len(tracker.segs),
-                           f"6x1920x1080-m8-{args.dist}" if std and world == 1 else None)
         res = f"{main_wl.width}x{main_wl.height}"
         line = {
             "metric": f"frames/sec ({main_wl.cameras}-cam {'1080p' if res == '1920x1080' else res})", "value": round(value, 2),
@@ -705,25 +774,30 @@ def main():
                        "collective": None if world == 1 else
                        ("mocap_allgather_centroids (ncclAllGather behind the C-ABI, RCCL)" if tracker.collective == "rccl"
                         else ("torch.distributed over gloo (one-GPU rehearsal)" if args.rehearse_on_one_gpu else "torch.distributed all_gather_into_tensor (RCCL)"))},
-            "roofline": roof,
-            "kernel_ms_per_step": kernel_ms(prof),
             "kernel_ms_per_step_in_timed_region": kernel_ms(prof, True),
             "status_ok": status_ok,
             "time_steps_without_result": int((n_roots < 0).sum()),  # capacity codes (MOCAP_CORR_E_*): e.g. the reference's cartesian
                                                                     # expansion beyond max_groups in a crowded rig (configs[4])
             "points_per_frame": float(np.maximum(n_roots, 0).mean()),
-            "dark_tile_early_out": {"tiles_per_step": prof["tiles"], "tiles_resolved_without_filtering": prof["tiles_skipped"],
-                                    "note": "exact: the scan kernel reads the frames once and sums every 8x8 cell's excess over a base "
-                                            "derived from the threshold; a filter tile whose cells prove that no mask bit can be set is "
-                                            "answered with zeros (DESIGN.md 4.1); disabled run in without_early_out"},
         }
         if args.rehearse_on_one_gpu:
             line["rehearsal"] = "N ranks on one GPU over gloo: a functional check of the multi-rank path, NOT a measurement"
-        if world == 1 and args.extra and std and not args.from_host:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, *m["last"])
+        if args.full:  # the sequential pass of timed(): per-kernel durations and the roofline
+            line["roofline"] = roofline_of(prof, main_wl, len(m["images"]), 1 if world == 1 else len(tracker.segs),
+                                           f"6x1920x1080-m8-{args.dist}" if std and world == 1 else None)
+            line["kernel_ms_per_step"] = kernel_ms(prof)
+            line["dark_tile_early_out"] = {
+                "tiles_per_step": prof["tiles"], "tiles_resolved_without_filtering": prof["tiles_skipped"],
+                "note": "exact: the scan kernel reads the frames once and sums every 8x8 cell's excess over a base "
+                        "derived from the threshold; a filter tile whose cells prove that no mask bit can be set is "
+                        "answered with zeros (DESIGN.md 4.1); disabled run in without_early_out"}
+        if args.full and world == 1 and args.extra and std and not args.from_host:
             # figures that only existed in DESIGN.md, now in the driver-recorded line
             pipe = {}
             n_ss = 300
-            _, el_s, prof_s, _ = timed(tracker, m["batches"], n_ss, args.warmup)
+            _, el_s, prof_s, _, _ = timed(tracker, m["batches"], n_ss, args.warmup)
             pipe["steady_state"] = {"workload": main_wl.name(world), "steps": n_ss, "value": round(T_STEPS * n_ss / el_s, 2), "unit": "frames/s",
                                     "ms_per_step": round(1e3 * el_s / n_ss, 4),
                                     "kernel_ms_per_step_in_timed_region": kernel_ms(prof_s, True),
@@ -733,12 +807,12 @@ def main():
             pipe["from_host"] = from_host_section(main_wl, m)
             line["pipeline"] = pipe
         left = m["left"]  # what the timed region left in the lanes' buffers: (batch, records, outputs)
-        if world == 1 and args.secondary:
+        if args.full and world == 1 and args.secondary:
             # the same batches with the early-out off: every tile runs the full filter (dense kernel); the results must not change
             for lane in tracker.lanes:
                 lane.ctx.set_tuning("skip_dark", 0)
             n_d = max(3, args.steps // 3)
-            out_d, el_d, prof_d, left_d = timed(tracker, m["batches"], n_d, 2)
+            out_d, el_d, prof_d, left_d, _ = timed(tracker, m["batches"], n_d, 2)
             each_d = run_each(tracker, m["batches"])
             for lane in tracker.lanes:
                 lane.ctx.set_tuning("skip_dark", 1)
@@ -751,7 +825,7 @@ def main():
                                          "filter_avg_launch_ms": roof_d["avg_launch_ms"], "roofline_frac": roof_d["frac"],
                                          "same_results": bool(same)}
             del left_d
-        if world == 1 and args.cpu_steps > 0:
+        if args.full and world == 1 and args.cpu_steps > 0:
             frames_tc = m["frames_host"].reshape(T_STEPS, main_wl.cameras, main_wl.height, main_wl.width)
             fps, dt, results = cpu_baseline(main_wl, m["arrays"], frames_tc, args.cpu_steps)
             line["cpu_baseline"] = {"value": round(fps, 3), "unit": "frames/s", "cores": main_wl.cameras, "kind": "port",
@@ -776,7 +850,7 @@ def main():
         m.clear()
         del tracker, out
         torch.cuda.empty_cache()
-        if world == 1 and args.secondary:
+        if args.full and world == 1 and args.secondary:
             other = "zero" if args.dist == "mild" else "mild"
             wl2 = Workload(main_wl.cameras, main_wl.width, main_wl.height, main_wl.markers, other, main_wl.background, main_wl.bayer)
             m2 = measure(wl2, T_STEPS, args.steps, args.warmup)
@@ -787,7 +861,7 @@ def main():
             line["other_distortion_variant"] = sec
             m2.clear()
             torch.cuda.empty_cache()
-        if world == 1 and args.extra and std:
+        if args.full and world == 1 and args.extra and std:
             extra = {}
             for key, wl in (("markers32_configs2", Workload(6, 1920, 1080, 32, args.dist)),
                             ("bright_background", Workload(6, 1920, 1080, 8, args.dist, (90, 110))),

@@ -5,7 +5,7 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd /tmp && export TMPDIR=/tmp
 set -e
-ARGS="--cpu-steps 0 --no-secondary --no-extra"
+ARGS="--full --cpu-steps 0 --no-secondary --no-extra"
 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_d3 -o d3 -- python3 $R/bench.py $ARGS > $R/gpurun_out/prof_d3.json
 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_d1 -o d1 -- python3 $R/bench.py --depth 1 $ARGS > $R/gpurun_out/prof_d1.json
 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_m32d1 -o m32d1 -- python3 $R/bench.py --depth 1 --markers 32 $ARGS > $R/gpurun_out/prof_m32d1.json

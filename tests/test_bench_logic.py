@@ -103,3 +103,59 @@ def test_same_results_ignores_what_lies_beyond_the_counts(bench):
     out4 = {k: v.clone() for k, v in out2.items()}
     out4["n"][3] = 2
     assert not bench.same_results(rec, out, rec2, out4)
+
+
+def test_frames_follow_their_seeds_whatever_the_order(bench):
+    """The rendered frames (a thread pool) equal the serial recipe: time step t's markers from seed 1000 + t, camera c's frame
+    of it from seed (1000 + t) * 64 + c.  `--dump-outputs` of two builds is compared on exactly these inputs."""
+    from mocapv2_amd.synth import MILD_DIST, Scene
+    wl = bench.Workload(3, 96, 64, 4, "mild")
+    scene = Scene(3, 96, 64, dist=MILD_DIST)
+    images = [(c, t) for t in range(4) for c in range(3)] + [(1, 9), (0, 2), (2, 9)]
+    got = wl.render(scene, images)
+    for i, (c, t) in enumerate(images):
+        markers = scene.markers(np.random.default_rng(1000 + t), 4, extent=0.5)
+        exp = scene.render(np.random.default_rng((1000 + t) * 64 + c), markers, c, radius_range=(16.0, 22.0), noise_min=0,
+                           noise_max=60, salt=0.001)
+        assert np.array_equal(got[i], exp), (c, t)
+    assert np.array_equal(wl.render(scene, images[::-1]), got[::-1])
+
+
+def test_dump_outputs_writes_the_counted_results_only(bench, tmp_path):
+    """float64 files; words beyond a count (stale memory of an earlier batch) are written as 0; a failed time step (< 0) keeps
+    its code and no roots; above the byte cap a fixed sample of time steps and images is written with its indices."""
+    T, C, P = 5, 2, 3
+    rec = np.full((T * C, 2 + 2 * P), 99, np.int32)
+    rec[:, 0] = [0, 1, 3, 2, -4, 1, 0, 0, 2, 3]
+    n = np.array([2, 0, -2, 1, 3], np.int32)
+    out = {"n": n, "xyz": np.full((T, P, 3), 7.5), "err": np.full((T, P), 0.25), "grp": np.full((T, P, C, 2), 3.0),
+           "root": np.full((T, P), 4, np.int32), "order": np.full((T, P), 1, np.int32)}
+    names = bench.dump_outputs(str(tmp_path / "a"), torch.from_numpy(rec), {k: torch.from_numpy(v) for k, v in out.items()})
+    assert sorted(names) == ["centroid_count", "centroids", "err", "grp", "n", "order", "root", "xyz"]
+    d = {k: np.load(tmp_path / "a" / (k + ".npy")) for k in names}
+    assert all(v.dtype == np.float64 for v in d.values())
+    assert np.array_equal(d["n"], n) and np.array_equal(d["centroid_count"], rec[:, 0])
+    for t in range(T):
+        k = max(0, n[t])
+        assert (d["xyz"][t, :k] == 7.5).all() and (d["xyz"][t, k:] == 0).all()
+        assert (d["grp"][t, :k] == 3.0).all() and (d["grp"][t, k:] == 0).all() and (d["order"][t, k:] == 0).all()
+    for i in range(T * C):
+        k = min(max(0, rec[i, 0]), P)
+        assert (d["centroids"][i, :k] == 99).all() and (d["centroids"][i, k:] == 0).all()
+    cap = 600
+    names = bench.dump_outputs(str(tmp_path / "b"), rec, out, max_bytes=cap)
+    assert "sample_time_steps" in names and "sample_images" in names
+    assert sum(os.path.getsize(tmp_path / "b" / (k + ".npy")) - 128 for k in names) <= cap  # 128 = .npy header
+    st = np.load(tmp_path / "b" / "sample_time_steps.npy").astype(int)
+    assert np.array_equal(np.load(tmp_path / "b" / "n.npy"), n[st])
+    bench.dump_outputs(str(tmp_path / "c"), rec, out, max_bytes=cap)
+    assert all(np.array_equal(np.load(tmp_path / "b" / (k + ".npy")), np.load(tmp_path / "c" / (k + ".npy"))) for k in names)
+
+
+def test_plain_run_is_the_headline_only(bench):
+    """A plain run measures the headline; the other figures are behind --full (off by default)."""
+    a = bench.parse_args(["--steps", "7", "--warmup", "2"])
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    assert bench.parse_args(["--full", "--dump-outputs", "d"]).full
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
