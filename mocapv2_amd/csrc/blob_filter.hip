@@ -981,6 +981,12 @@ __global__ __launch_bounds__(256) void filter_rows_staged_kernel(FilterArgs a)
             }
         };
         auto stage_write = [&](const BandRect& R, const rows_u32x4 (&v)[ROWS_LOADS]) __attribute__((always_inline)) {
+            // A band that is not staged takes its taps from memory and never reads Sb.  Its rectangle has R.n >= stage_units
+            // units, so the store index below (clamped only to R.llast < R.n) may lie past this wave's buffer -- in the next
+            // wave's, or past sbuf for wave 3.  No store then (R.staged is wave-uniform: a scalar branch; clamping the index
+            // to ROWS_STAGE_U - 1 instead would still write 9 KB of LDS nobody reads).  The loads in stage_issue stay
+            // unconditional.
+            if (!R.staged) return;
             if (!R.interior) { // units outside the image read 0 (cv::remap's BORDER_CONSTANT): clear, then the inside part on top
 #pragma unroll
                 for (int u = 0; u < ROWS_LOADS; u++) Sb[lane + 64 * u] = rows_u32x4{0u, 0u, 0u, 0u};
