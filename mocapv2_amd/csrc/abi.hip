@@ -179,6 +179,9 @@ struct mocap_ctx {
     int probe_images;                      // images the pending probe counted on (every 16th of its batch)
     bool hot_dense;                        // the last probe found a crowded scene (many hot cells per image): the scan leaves a hot map
     uint32_t* cells_ext; uint32_t* cur_box_ext; size_t cells_ext_images; // the same for caller-owned masks (mocap_filter_mask)
+    // the caller's row-major masks pass through masks of the internal layout (kernels.h: mask_word_index), converted at the boundary:
+    uint32_t* mask_out; size_t mask_out_images; // mocap_filter_mask filters into this one (a caller-owned mask for run_filter)
+    uint32_t* mask_in; size_t mask_in_images;   // mocap_contours_from_mask reads the caller's mask from this one
     void* cwork; size_t cwork_images;      // contour kernel workspace, contour_work_bytes() per image
     uint64_t* walk_list; uint64_t* link_list; uint32_t* walk_count; // contour stage, split form: the batch's border walks / link walks
                                                                     //   (grown with cwork) and their counters
@@ -276,7 +279,8 @@ int mocap_ctx_create(int device_id, int width, int height, int n_slots, mocap_ct
     c->maps = nullptr; c->map4 = nullptr; c->srcbox = nullptr; c->rowbox = nullptr; c->reach = nullptr; c->cflags = nullptr; c->map_flags = nullptr;
     c->mask = nullptr; c->mask_images = 0; c->mask_dirty = false; c->cells = nullptr; c->cells_images = 0; c->last_images = 0;
     c->hotmap = nullptr; c->tile_rows = nullptr; c->tile_rows_flip = 0; c->tile_rows_hold[0] = c->tile_rows_hold[1] = 0; c->cur_box = nullptr; c->items = nullptr; c->n_items = nullptr; c->cap_items = 0; c->wide_tiles = nullptr; c->cap_wide = 0;
-    c->cells_ext = nullptr; c->cur_box_ext = nullptr; c->cells_ext_images = 0; c->cwork = nullptr; c->cwork_images = 0; c->walk_list = nullptr; c->link_list = nullptr; c->walk_count = nullptr;
+    c->cells_ext = nullptr; c->cur_box_ext = nullptr; c->cells_ext_images = 0;
+    c->mask_out = nullptr; c->mask_out_images = 0; c->mask_in = nullptr; c->mask_in_images = 0; c->cwork = nullptr; c->cwork_images = 0; c->walk_list = nullptr; c->link_list = nullptr; c->walk_count = nullptr;
     c->cams = nullptr; c->n_cam = 0; c->n_F = 0; c->scratch = nullptr; c->scratch_elems = 0; c->profiling = false;
     c->ba_obj = nullptr; c->ba_obj_elems = 0; c->ba_pinned = nullptr; c->ba_pinned_bytes = 0;
     c->comm.reset();
@@ -342,6 +346,8 @@ int mocap_ctx_destroy(mocap_ctx_t c)
     if (c->cells_ext) (void)hipFree(c->cells_ext);
     if (c->map_flags) (void)hipFree(c->map_flags);
     if (c->mask) (void)hipFree(c->mask);
+    if (c->mask_out) (void)hipFree(c->mask_out);
+    if (c->mask_in) (void)hipFree(c->mask_in);
     if (c->cells) (void)hipFree(c->cells);
     if (c->tile_rows) (void)hipFree(c->tile_rows);
     if (c->hotmap) (void)hipFree(c->hotmap);
@@ -698,7 +704,7 @@ static int run_filter(mocap_ctx* c, const void* frames, int n_images, int cam_mo
         return 0;
     }
     if (own_mask && c->mask_dirty) { // the general kernel wrote the whole mask last time: back to "zero outside the regions"
-        HIP_TRY(hipMemsetAsync(c->mask, 0, sizeof(uint32_t) * c->mask_images * c->H * c->wpr, s));
+        HIP_TRY(hipMemsetAsync(c->mask, 0, sizeof(uint32_t) * c->mask_images * mask_image_words(c->H, c->wpr), s));
         std::vector<uint32_t> init(c->mask_images * cells_per_image(c) * 4);
         for (size_t i = 0; i < init.size(); i += 4) { init[i] = 1u; init[i + 1] = 1u; init[i + 2] = 1u; init[i + 3] = 1u; }
         HIP_TRY(hipStreamSynchronize(s));
@@ -754,7 +760,7 @@ static int run_filter(mocap_ctx* c, const void* frames, int n_images, int cam_mo
         BrightArgs b{(const uint8_t*)frames, image_stride, pitch, c->H, c->W, n_images, cam_mod, ncx_magic, wide, base, allow / 4, allow_cut1 / 4, allow_cut2 / 4,
                      c->reach + (size_t)slot_base * source_cells(c), c->cflags + (size_t)slot_base * source_cells(c),
                      tr_cur, tl.n_cgroups * 4, tl.n_strips, (uint32_t)(((1u << 23) + tl.rows - 1) / tl.rows),
-                     mask, own_mask ? 0 : (size_t)n_images * c->H * c->wpr, ((uintptr_t)mask & 15) == 0, nullptr, base_alt, allow_alt / 4, 0};
+                     mask, own_mask ? 0 : (size_t)n_images * mask_image_words(c->H, c->wpr), ((uintptr_t)mask & 15) == 0, nullptr, base_alt, allow_alt / 4, 0};
         b.prio = c->tune.scan_prio; // A/B switch
         b.max_blocks = c->tune.scan_blocks_per_cu * c->n_cu; b.blocks_x = 0;
         b.zero_counters = scan_zeroes ? c->n_items : nullptr;
@@ -994,7 +1000,7 @@ static int ensure_mask(mocap_ctx* c, int n_images)
     std::lock_guard<std::mutex> lk(c->mu);
     if ((size_t)n_images <= c->mask_images) return 0;
     if (c->mask) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(c->mask)); c->mask = nullptr; c->mask_images = 0; c->last_images = 0; }
-    size_t bytes = sizeof(uint32_t) * (size_t)n_images * c->H * c->wpr;
+    size_t bytes = sizeof(uint32_t) * (size_t)n_images * mask_image_words(c->H, c->wpr);
     HIP_TRY(hipMalloc(&c->mask, bytes));
     HIP_TRY(hipMemset(c->mask, 0, bytes));
     c->mask_images = n_images;
@@ -1033,6 +1039,20 @@ static int ensure_mask(mocap_ctx* c, int n_images)
     return 0;
 }
 
+// a zeroed mask of the internal layout for n_images (the padding rows stay zero: nothing writes them)
+static int ensure_blocked(mocap_ctx* c, uint32_t** m, size_t* images, int n_images)
+{
+    if ((size_t)n_images <= *images) return 0;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if ((size_t)n_images <= *images) return 0;
+    if (*m) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(*m)); *m = nullptr; *images = 0; }
+    const size_t bytes = sizeof(uint32_t) * (size_t)n_images * mask_image_words(c->H, c->wpr);
+    HIP_TRY(hipMalloc(m, bytes));
+    HIP_TRY(hipMemset(*m, 0, bytes));
+    *images = n_images;
+    return 0;
+}
+
 int mocap_filter_mask(mocap_ctx_t c, const void* frames, int n_images, int cam_mod, int slot_base, size_t image_stride,
                       int pitch, uint32_t* mask_dev, void* stream)
 {
@@ -1049,7 +1069,13 @@ int mocap_filter_mask(mocap_ctx_t c, const void* frames, int n_images, int cam_m
         HIP_TRY(hipMalloc(&c->cur_box_ext, sizeof(uint32_t) * 4 * (size_t)n_images * cells_per_image(c)));
         c->cells_ext_images = n_images;
     }
-    return run_filter(c, frames, n_images, cam_mod, slot_base, image_stride, pitch, mask_dev, c->cells_ext, (hipStream_t)stream);
+    if ((rc = ensure_blocked(c, &c->mask_out, &c->mask_out_images, n_images))) return rc;
+    // filtered as a caller-owned mask (cleared by the scan, or written whole), then written whole into the caller's row-major one
+    if ((rc = run_filter(c, frames, n_images, cam_mod, slot_base, image_stride, pitch, c->mask_out, c->cells_ext, (hipStream_t)stream)))
+        return rc;
+    launch_mask_convert(c->mask_out, mask_dev, n_images, c->H, c->wpr, false, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return MOCAP_OK;
 }
 
 int mocap_contours_from_mask(mocap_ctx_t c, const uint32_t* mask_dev, int n_images, int32_t* out_xy, long xy_stride,
@@ -1061,7 +1087,11 @@ int mocap_contours_from_mask(mocap_ctx_t c, const uint32_t* mask_dev, int n_imag
         return fail(MOCAP_E_INVALID, "n_images=%d max_blobs=%d strides %ld %ld", n_images, max_blobs, xy_stride, count_stride);
     if ((dbg != nullptr) != (dbg_count != nullptr) || (dbg && dbg_cap < 1)) return fail(MOCAP_E_INVALID, "inconsistent debug buffers");
     if (set_device(c)) return MOCAP_E_HIP;
-    return run_contours(c, mask_dev, nullptr, nullptr, n_images, out_xy, xy_stride, out_count, count_stride, max_blobs, dbg, dbg_count, dbg_cap,
+    int rc = ensure_blocked(c, &c->mask_in, &c->mask_in_images, n_images);
+    if (rc) return rc;
+    launch_mask_convert(mask_dev, c->mask_in, n_images, c->H, c->wpr, true, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return run_contours(c, c->mask_in, nullptr, nullptr, n_images, out_xy, xy_stride, out_count, count_stride, max_blobs, dbg, dbg_count, dbg_cap,
                         (hipStream_t)stream);
 }
 

@@ -204,15 +204,18 @@ __global__ __launch_bounds__(256) void settle_tiles_kernel(BoxArgs a)
             a.cells[idx] = 0u;
         }
     }
-    for (uint64_t todo = __ballot(need_clear); todo; todo &= todo - 1) { // the whole wave clears one region: lane = row
+    for (uint64_t todo = __ballot(need_clear); todo; todo &= todo - 1) { // the whole wave clears one region
         const int src = __ffsll((long long)todo) - 1;
         const uint32_t cx = (uint32_t)__builtin_amdgcn_readlane((int)pout_x, src), cy = (uint32_t)__builtin_amdgcn_readlane((int)pout_y, src);
         const int cimage = __builtin_amdgcn_readlane(image, src);
         const int x0 = (int)(cx & 0xffffu), x1 = (int)(cx >> 16), y0 = (int)(cy & 0xffffu), y1 = (int)(cy >> 16);
-        uint8_t* m = (uint8_t*)(a.mask + (size_t)cimage * a.H * a.words_per_row);
-        const int b0 = x0 >> 3, b1 = x1 >> 3, rb = a.words_per_row * 4;
-        for (int y = y0 + lane; y <= y1; y += 64)
-            for (int b = b0; b <= b1; b++) m[(size_t)y * rb + b] = 0;
+        uint8_t* m = (uint8_t*)(a.mask + (size_t)cimage * mask_image_words(a.H, a.words_per_row));
+        // consecutive lanes walk down the rows of one byte column: 32 of them share a line of the blocked mask
+        const int b0 = x0 >> 3, nr = y1 - y0 + 1, n = nr * ((x1 >> 3) - b0 + 1);
+        for (int i = lane; i < n; i += 64) {
+            const int bc = i / nr;
+            m[mask_byte_index(y0 + (i - bc * nr), b0 + bc, a.words_per_row)] = 0;
+        }
     }
 
     if (uint64_t wb = __ballot(wide)) { // the wide tiles of this wave: `wide_bands` slots each in their list (the row pipeline is a
@@ -693,7 +696,7 @@ __global__ __attribute__((amdgpu_waves_per_eu(MOCAP_BOX_WAVES, MOCAP_BOX_WAVES))
         // the item's output region lies in at most 2 x 2 tiles: chunks chunk0 (+1), strips strip0 (+1)
         const int chunk0 = oy0 / a_rows_per_chunk, strip0 = ox0 / 240;
         const int tile_r0 = chunk0 * a_rows_per_chunk, tile_r1 = tile_r0 + a_rows_per_chunk; // first row of chunk0 / of chunk0 + 1
-        uint8_t* __restrict__ mrow = (uint8_t*)(a_mask + (size_t)image * H * a_words_per_row);
+        uint8_t* __restrict__ mrow = (uint8_t*)(a_mask + (size_t)image * mask_image_words(H, a_words_per_row));
         const int out_byte = (ox0 >> 3) + ((q - 1) >> 1);
         const bool stores = lane_on && (q & 1) && q <= Q - 3 && out_byte < ((W + 7) >> 3) && out_byte < row_bytes;
         uint32_t lacc = 0, lacc1 = 0; // bit g: rows 8g..8g+7 of chunk0 (lacc) / chunk0 + 1 (lacc1) hold set pixels in this lane's columns
@@ -721,7 +724,7 @@ __global__ __attribute__((amdgpu_waves_per_eu(MOCAP_BOX_WAVES, MOCAP_BOX_WAVES))
                 const uint32_t odd = from_next(mn);
                 const uint32_t byte = mn | ((odd & 0xfu) << 4);
                 const bool st = stores && y <= oy1;
-                if (st) mrow[(size_t)y * row_bytes + out_byte] = (uint8_t)byte;
+                if (st) mrow[mask_byte_index(y, out_byte, a_words_per_row)] = (uint8_t)byte;
                 const uint32_t hit = (st && byte != 0u) ? 1u : 0u;
                 if (yy < tile_r1) lacc |= hit << ((yy - tile_r0) >> 3);
                 else lacc1 |= hit << ((yy - tile_r1) >> 3);

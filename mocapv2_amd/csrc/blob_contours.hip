@@ -26,7 +26,7 @@
 // images with an ambiguous link wait) -> contour_follow_kernel (the link walks) -> contours_kernel<2> (the images that waited);
 // the hand-over is the per-image global workspace (L2) and the two batch-wide walk lists.  contours_kernel<0> is the same work
 // as one kernel per image with the lone-lane walker `follow` below (contours_split = 0, and whenever contour_timing is on).
-// The mask is 1/8 B per pixel.
+// The mask is 1/8 B per pixel, in 32-row blocks (kernels.h: mask_word_index): a line holds one word column of 32 rows.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "kernels.h"
@@ -53,7 +53,7 @@ struct Mask {
     int RS; // raster stride W+1, so the virtual background column right of the image has its own index
     __device__ __forceinline__ uint32_t word(int y, int k) const
     {
-        return ((unsigned)y < (unsigned)H && (unsigned)k < (unsigned)wpr) ? w[(size_t)y * wpr + k] : 0u;
+        return ((unsigned)y < (unsigned)H && (unsigned)k < (unsigned)wpr) ? w[mask_word_index(y, k, wpr)] : 0u;
     }
 };
 
@@ -64,14 +64,14 @@ __device__ __forceinline__ uint64_t row64(const Mask& M, int y, int x0)
     const int k0 = x0 >> 5; // arithmetic shift = floor for negative x0
     const uint32_t sh = (uint32_t)x0 & 31u;
     const int yc = y < 0 ? 0 : (y > M.H - 1 ? M.H - 1 : y);
-    const uint32_t* __restrict__ rowp = M.w + (uint32_t)yc * (uint32_t)M.wpr;
+    const uint32_t* __restrict__ rowp = M.w + mask_word_index(yc, 0, M.wpr); // the row's word k is rowp[32 k]
     const bool yin = (unsigned)y < (unsigned)M.H;
     uint32_t w[3];
 #pragma unroll
     for (int i = 0; i < 3; i++) {
         const int k = k0 + i, kc = k < 0 ? 0 : (k > M.wpr - 1 ? M.wpr - 1 : k);
         const uint32_t keep = (yin && (unsigned)k < (unsigned)M.wpr) ? 0xffffffffu : 0u;
-        w[i] = rowp[kc] & keep; // an AND, not a select: the load stays unconditional (no branch around it)
+        w[i] = rowp[(uint32_t)kc * 32u] & keep; // an AND, not a select: the load stays unconditional (no branch around it)
     }
     const uint32_t lo = __builtin_amdgcn_alignbit(w[1], w[0], sh), hi = __builtin_amdgcn_alignbit(w[2], w[1], sh);
     return ((uint64_t)hi << 32) | lo;
@@ -335,7 +335,7 @@ __device__ __forceinline__ void contours_body(const ContourArgs& a, const int im
     else if (a.prio == 3) __builtin_amdgcn_s_setprio(3);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = uni(tid >> 6);
-    Mask M{a.mask + (size_t)image * a.H * a.words_per_row, a.words_per_row, a.H, a.W, a.W + 1};
+    Mask M{a.mask + (size_t)image * mask_image_words(a.H, a.words_per_row), a.words_per_row, a.H, a.W, a.W + 1};
     ContourWork& work = ((ContourWork*)a.work)[image];
     int32_t* const out_count = a.out_count + (size_t)image * a.count_stride;
     if (tid == 0) { ncand = 0; nrec = 0; nkept = 0; err = 0; ncell = 0; dbg_steps = 0; }
@@ -432,10 +432,10 @@ __device__ __forceinline__ void contours_body(const ContourArgs& a, const int im
             if (ncell > MAXCELL && tid == 0) atomicMax(&err, 4);
         }
         const int ncl = cells ? (ncell < MAXCELL ? ncell : MAXCELL) : n_cells;
-        // One task = one cell, taken by a group of 8 lanes: lane i of the group holds word kf - 1 + i of a row (kf = first
-        // word of the cell's column range, see above) and of the row above it, so a wave's loads cover 8 rows x 32 contiguous
-        // bytes; lanes 1..6 test their word with the neighbours' words from lanes i - 1 / i + 1 (DPP), ranges longer than 6
-        // words take further passes.  The 16 loads of a cell's 8 rows are in flight together.
+        // One task = one cell, taken by a group of 8 lanes: lane j of the group holds row j of the cell (the lanes of a load lie
+        // in one or two lines of the blocked mask) and loads 8 consecutive words of it, kf - 1 + p0 .. kf + p0 + 6 (kf = first
+        // word of the cell's column range, see above); the row above comes from lane j - 1 (DPP), lane 0 loads it.  Words
+        // 1..6 are tested with their neighbours; ranges longer than 6 words take further passes.
         const int sub = tid & 7, grp8 = tid >> 3;
         for (int ci0 = 0; ci0 < ncl; ci0 += NTHREADS / 8) {
             const int ci = ci0 + grp8;
@@ -449,28 +449,25 @@ __device__ __forceinline__ void contours_body(const ContourArgs& a, const int im
             int kf = ka, cnt = kb - ka + 1;
             if (ranged && cv) { const uint32_t rg = cell_rng[ci]; kf = (int)(rg & 0xfffu); cnt = (int)(rg >> 12); }
             if (!cv) cnt = 0;
-            for (int p0 = 0; p0 < cnt; p0 += 6) {
-                const int k = kf - 1 + p0 + sub;
-                const bool tests = sub >= 1 && sub <= 6 && k < kf + cnt && k >= ka && k <= kb;
-                // the cell's 8 rows and the row above the first: 9 loads in flight together (the row above row j is row j - 1)
-                uint32_t rw[9];
-                rw[0] = cv ? M.word(y0 - 1, k) : 0u;
+            const int y = y0 + sub;
+            const bool rowv = y < yend && 8 * g + sub < R;
+            for (int p0 = 0; p0 < cnt; p0 += 6) { // (cnt is uniform in the group: its 8 lanes run the same passes)
+                uint32_t rw[8], up[8];
 #pragma unroll
-                for (int j = 0; j < 8; j++) {
-                    const int y = y0 + j;
-                    const bool rowv = y < yend && 8 * g + j < R;
-                    rw[1 + j] = rowv ? M.word(y, k) : 0u;
+                for (int i = 0; i < 8; i++) rw[i] = rowv ? M.word(y, kf - 1 + p0 + i) : 0u;
+                // the row above: lane j - 1's row, exchanged while every lane of the group is active (before any lane-divergent code)
+#pragma unroll
+                for (int i = 0; i < 8; i++) up[i] = lane_prev(rw[i]);
+                if (sub == 0) {
+#pragma unroll
+                    for (int i = 0; i < 8; i++) up[i] = M.word(y0 - 1, kf - 1 + p0 + i);
                 }
-                // the neighbours' words, exchanged while every lane of the group is active (before any lane-divergent code)
-                uint32_t pr[9], nx[9];
 #pragma unroll
-                for (int j = 0; j < 9; j++) { pr[j] = lane_prev(rw[j]); nx[j] = lane_next(rw[j]); }
-#pragma unroll
-                for (int j = 0; j < 8; j++) {
-                    const int y = y0 + j;
-                    const uint32_t w = rw[1 + j], n = rw[j];
-                    const uint32_t prev_w = pr[1 + j], prev_n = pr[j], next_w = nx[1 + j], next_n = nx[j];
-                    if (!tests || !(y < yend && 8 * g + j < R)) continue;
+                for (int i = 1; i <= 6; i++) {
+                    const int k = kf - 1 + p0 + i;
+                    if (!rowv || !(k < kf + cnt && k >= ka && k <= kb)) continue;
+                    const uint32_t w = rw[i], n = up[i];
+                    const uint32_t prev_w = rw[i - 1], prev_n = up[i - 1], next_w = rw[i + 1], next_n = up[i + 1];
                     const uint32_t Wn = (w << 1) | (prev_w >> 31);
                     // Necessary conditions, evaluated on the 64 columns starting at this word (this word + the next):
                     // a raster-first foreground pixel starts a run none of whose pixels touches (8-connectivity) the
@@ -859,7 +856,7 @@ __global__ __launch_bounds__(64) void contour_follow_kernel(ContourArgs a)
     const uint32_t total = a.walk_count[2 * a.follow_list];
     uint32_t* const head_ctr = &a.walk_count[2 * a.follow_list + 1];
     ContourWork* const works = (ContourWork*)a.work;
-    const uint32_t image_words = (uint32_t)a.H * (uint32_t)a.words_per_row;
+    const uint32_t image_words = (uint32_t)mask_image_words(a.H, a.words_per_row);
     const int RS = a.W + 1;
     Walk w;
     w.status = 0; w.meta = 0; w.n = 0; w.known = 0; w.x = 0; w.y = 0; w.wx0 = 0; w.wy0 = 0; w.wslot = lane; w.steps = 0; w.s0 = 0;

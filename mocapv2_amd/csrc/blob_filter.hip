@@ -585,8 +585,9 @@ __global__ __attribute__((amdgpu_waves_per_eu(MOCAP_ROWS_WAVES))) __launch_bound
         const uint8_t* __restrict__ img = a.src + (size_t)image * a.image_stride;
         const uint32_t* __restrict__ map = REMAP ? a.map + (size_t)slot * a.H * a.W : nullptr;
         const uint32_t* __restrict__ mapw = REMAP ? a.mapw + (size_t)slot * a.H * a.W : nullptr;
-        uint8_t* __restrict__ mrow_base = (uint8_t*)(a.mask + (size_t)image * a.H * a.words_per_row);
+        uint8_t* __restrict__ mrow_base = (uint8_t*)(a.mask + (size_t)image * mask_image_words(a.H, a.words_per_row));
         const int row_bytes = a.words_per_row * 4;
+        const int wpr = a.words_per_row;
 
         const int xl = xbase + 4 * lane;
 
@@ -710,7 +711,7 @@ __global__ __attribute__((amdgpu_waves_per_eu(MOCAP_ROWS_WAVES))) __launch_bound
             uint32_t byte = (mn & 0xfu) | ((odd & 0xfu) << 4);
             // direct byte store: all loads here are global-address-space loads, so the compiler keeps counted vmcnt
             // waits around this exec-masked store and the load pipeline stays full
-            if (stores && on) mrow_base[(size_t)row * row_bytes + out_byte] = (uint8_t)byte;
+            if (stores && on) mrow_base[mask_byte_index(row, out_byte, wpr)] = (uint8_t)byte;
         };
 
         // ---- set-up: source rows kfirst-2 .. kfirst+2 (ring slots 3..7), first threshold row, replicated top rows ----
@@ -891,7 +892,7 @@ __global__ __launch_bounds__(256) void filter_rows_staged_kernel(FilterArgs a)
         const uint8_t* __restrict__ img = a_src + (size_t)image * a_image_stride;
         const uint32_t* __restrict__ map4 = a_map4 + (size_t)slot * H * W;
         const ushort4* __restrict__ rbox = a_rowbox + (size_t)slot * H * n_strips + strip; // row r: rbox[r * n_strips]
-        uint8_t* __restrict__ mrow_base = (uint8_t*)(a_mask + (size_t)image * H * words_per_row);
+        uint8_t* __restrict__ mrow_base = (uint8_t*)(a_mask + (size_t)image * mask_image_words(H, words_per_row));
         const int row_bytes = words_per_row * 4;
         const int xl = xbase + 4 * lane;
         uint32_t cx01, cx23, colmask = 0;
@@ -1092,7 +1093,7 @@ __global__ __launch_bounds__(256) void filter_rows_staged_kernel(FilterArgs a)
             lacc |= (mn != 0u ? 1u : 0u) << (((on ? row : r0) - tile_r0) >> 3);
             uint32_t odd = lane_from_next(mn);
             uint32_t byte = (mn & 0xfu) | ((odd & 0xfu) << 4);
-            if (stores && on) mrow_base[(size_t)row * row_bytes + out_byte] = (uint8_t)byte;
+            if (stores && on) mrow_base[mask_byte_index(row, out_byte, words_per_row)] = (uint8_t)byte;
         };
 
         // ---- band 0: the five rows y0 .. y0 + 4 of the set-up (ring slots 3 .. 7) ------------------------------------------
@@ -1305,8 +1306,24 @@ __global__ void mask_expand_kernel(const uint32_t* __restrict__ mask, int words_
 {
     int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
     if (x >= W || y >= H) return;
-    uint32_t w = mask[(size_t)y * words_per_row + (x >> 5)];
+    uint32_t w = mask[mask_word_index(y, x >> 5, words_per_row)];
     dst[(size_t)y * dpitch + x] = ((w >> (x & 31)) & 1u) ? 255 : 0;
+}
+
+// caller row-major masks [n][H][wpr] <-> the internal 32-row blocks (kernels.h), one thread per word in block order: lane = row
+__global__ void mask_convert_kernel(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst, int n_images, int H, int wpr,
+                                    int to_blocked)
+{
+    const size_t image_words = mask_image_words(H, wpr);
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (size_t)n_images * image_words) return;
+    const size_t n = t / image_words;
+    const uint32_t i = (uint32_t)(t - n * image_words);  // = mask_word_index(y, k, wpr)
+    const int y = (int)((i >> 5) / (uint32_t)wpr * 32u + (i & 31u)), k = (int)((i >> 5) % (uint32_t)wpr);
+    if (y >= H) return; // padding rows: zero from allocation, never written
+    const size_t r = ((size_t)n * H + y) * wpr + k;
+    if (to_blocked) dst[t] = src[r];
+    else dst[r] = src[t];
 }
 
 // image_filter_cpu order: exact 5x5 median (BORDER_REPLICATE) then threshold
@@ -1509,6 +1526,14 @@ void launch_undistort(const uint8_t* src, uint8_t* dst, int H, int W, int sp, in
 {
     hipLaunchKernelGGL(undistort_kernel, grid2d(W, H), dim3(64, 4), 0, s, src, dst, H, W, sp, dp, map, mapw);
 }
+void launch_mask_convert(const uint32_t* src, uint32_t* dst, int n_images, int H, int wpr, bool to_blocked, hipStream_t s)
+{
+    const size_t total = (size_t)n_images * mask_image_words(H, wpr);
+    if (!total) return;
+    hipLaunchKernelGGL(mask_convert_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, src, dst, n_images, H, wpr,
+                       to_blocked ? 1 : 0);
+}
+
 void launch_mask_expand(const uint32_t* mask, int wpr, uint8_t* dst, int H, int W, int dp, hipStream_t s)
 {
     hipLaunchKernelGGL(mask_expand_kernel, grid2d(W, H), dim3(64, 4), 0, s, mask, wpr, dst, H, W, dp);

@@ -5,6 +5,24 @@
 
 namespace mocap {
 
+// The bit masks the kernels pass between them are stored in blocks of 32 rows: word k of row y (bit b = pixel 32k + b) sits
+// at word ((y >> 5) * wpr + k) * 32 + (y & 31) of its image, so one 128-byte line holds one word column of 32 rows (32 x 32
+// pixels).  Every consumer works on 2-D neighbourhoods some 50-64 pixels across (contour windows, blob boxes, cleared regions):
+// a 64 x 64 window is at most 3 x 3 lines, a lane-per-row load of 64 rows touches 2-3 lines.  An image takes
+// mask_image_words(H, wpr) words, H padded up to a multiple of 32; the padding rows are zero from allocation and never written.
+// (The C-ABI's caller-owned masks stay row-major: abi.hip converts at the boundary.)
+__host__ __device__ __forceinline__ uint32_t mask_word_index(int y, int k, int wpr)
+{
+    return ((uint32_t)(y >> 5) * (uint32_t)wpr + (uint32_t)k) * 32u + (uint32_t)(y & 31);
+}
+// byte b of row y (pixels 8b .. 8b + 7), for the byte-granular writers
+__host__ __device__ __forceinline__ uint32_t mask_byte_index(int y, int b, int wpr)
+{
+    return mask_word_index(y, b >> 2, wpr) * 4u + (uint32_t)(b & 3);
+}
+__host__ __device__ __forceinline__ size_t mask_image_words(int H, int wpr) { return (size_t)((H + 31) >> 5) * 32 * (size_t)wpr; }
+void launch_mask_convert(const uint32_t* src, uint32_t* dst, int n_images, int H, int wpr, bool to_blocked, hipStream_t s);
+
 // The dense filter kernel (any geometry, any lens model): every tile of every image, the undistortion as a gather in the
 // row pipeline.  Used when every tile has to be filtered anyway (early-out off or not provable), for images narrower than
 // 8 pixels, for undistort tables whose displacements do not fit the compact table of the box kernel, and by the
@@ -13,7 +31,7 @@ struct FilterArgs {
     const uint8_t* src;   // images, image_stride bytes apart, rows `pitch` bytes apart
     size_t image_stride;
     int pitch, H, W;
-    uint32_t* mask;       // [n_images][H][words_per_row], bit b of word k = pixel 32k+b
+    uint32_t* mask;       // [n_images][mask_image_words(H, words_per_row)] in 32-row blocks (see mask_word_index)
     int words_per_row;
     uint32_t* cells;      // [n_images][n_cgroups*4][n_strips]: bit g = rows 8g..8g+7 of the chunk have set pixels in the strip; bit 31 = tile ran the full filter
     // undistort tables of the first slot used (remap variant only), each [cam_mod][H][W]:
@@ -50,7 +68,7 @@ struct BoxItem { uint32_t image, tile, x01, y01, bx01, by01, pad0, pad1; }; // o
                                                                         //   (x0 > x1: skip); the scan's box of the tile (not clipped to it)
 struct BoxArgs {
     const uint8_t* src; size_t image_stride; int pitch, H, W;
-    uint32_t* mask; int words_per_row;
+    uint32_t* mask; int words_per_row; // [n_images][mask_image_words(H, words_per_row)] in 32-row blocks (see mask_word_index)
     uint32_t* cells;            // occupancy words [n_images][n_chunks][n_strips] (see FilterArgs)
     const uint32_t* map4;       // compact undistort table of the first slot used, [cam_mod][H][W]: dx (11 bits, signed) |
                                 //   dy (11, signed) << 11 | x fraction (5) << 22 | y fraction (5) << 27; the 2x2 taps start at
@@ -110,7 +128,7 @@ struct ContourRec {
 };
 
 struct ContourArgs {
-    const uint32_t* mask;
+    const uint32_t* mask;  // [n_images][mask_image_words(H, words_per_row)] in 32-row blocks (see mask_word_index)
     int words_per_row, H, W, n_images;
     int32_t* out_xy;     // image n: out_xy + n*xy_stride, [max_blobs][2]
     int32_t* out_count;  // image n: out_count[n*count_stride]; may exceed max_blobs (truncated), <0 = error

@@ -2,7 +2,11 @@
 """Turns the rocprofv3 output of profiles/collect.sh (gpurun_out/prof_*) into the summaries kept under profiles/:
 rNN_kernel_stats_depth3_default.csv, rNN_kernel_stats_depth1(_markers32).csv (copies of rocprofv3's own kernel_stats),
 rNN_pmc_FETCH_SIZE(_markers32).csv / rNN_pmc_WRITE_SIZE(_markers32).csv (per-kernel averages in KB per launch) and hbm_traffic.json
-(= (2 * FETCH_SIZE + WRITE_SIZE) * 1024 bytes per launch; FETCH_SIZE doubled per the MI355X guide's gfx950 rule)."""
+(= (2 * FETCH_SIZE + WRITE_SIZE) * 1024 bytes per launch; FETCH_SIZE doubled per the MI355X guide's gfx950 rule), plus the same
+bytes per batch for every kernel of the chain behind the scan, the contour kernels included (chain_bytes_per_batch).
+  python profiles/summarize.py [--src DIR] [--round TAG]   (another TAG than the current round writes its csv files only, e.g. the
+                                                            parent commit's passes from the same box)"""
+import argparse
 import csv
 import json
 import os
@@ -29,8 +33,9 @@ def pmc(path, counter, dst):
     return {k: sum(v) / len(v) for k, v in acc.items()}, {k: len(v) for k, v in acc.items()}
 
 
-ROUND = "r04"
+ROUND = "r05"
 SHORT = ("bright_cells_kernel", "mark_tiles_kernel", "settle_tiles_kernel", "box_filter_kernel", "filter_rows_staged_kernel", "filter_mask_kernel")
+CONTOUR = ("contours_kernel<1", "contour_follow_kernel", "contours_kernel<2") # (candidates, follow: both passes, tree: both passes)
 
 
 def workload(tag_fetch, tag_write, suffix, key, markers):
@@ -49,11 +54,20 @@ def workload(tag_fetch, tag_write, suffix, key, markers):
         # the hot cells, then leaves the hot map -- both read the same bytes; the one launched most often is taken)
         kf.sort(key=lambda k: -counts_f[k]); kw.sort(key=lambda k: -counts_w[k])
         per[short] = int(round((2 * fetch[kf[0]] + write[kw[0]]) * 1024))
+    # per batch (one scan launch per batch): every launch of every instance, the contour kernels' passes summed
+    batches = sum(c for k, c in counts_f.items() if "bright_cells_kernel" in k)
+    chain = {}
+    for short in SHORT[1:] + CONTOUR:
+        b = 2 * sum(fetch[k] * counts_f[k] for k in fetch if short in k) + sum(write[k] * counts_w[k] for k in write if short in k)
+        if b:
+            chain[short] = int(round(b * 1024 / batches))
+    print(key, "chain bytes per batch", json.dumps(chain), "total %.1f MB" % (sum(chain.values()) / 1e6))
     scan_fetch = fetch[sorted((k for k in fetch if "bright_cells_kernel" in k), key=lambda k: -counts_f[k])[0]]
     algo = FRAME_BYTES * IMAGES
     total = sum(per.values())
     print(key, json.dumps(per), "total", total, "= %.3f x algorithmic" % (total / algo))
     return {"workload_key": key, "dist": "mild", "images_per_launch": float(IMAGES), "markers": markers, "hbm_bytes_per_launch": per,
+            "chain_bytes_per_batch": chain,
             "total_over_algorithmic": round(total / algo, 4),
             "derivation": "(2*FETCH_SIZE + WRITE_SIZE) * 1024 from profiles/%s_pmc_FETCH_SIZE%s.csv / %s_pmc_WRITE_SIZE%s.csv (separate --pmc "
                           "passes of `python bench.py --full --depth 1 %s--steps 3 --warmup 2 --cpu-steps 0 --no-secondary --no-extra`, "
@@ -64,6 +78,13 @@ def workload(tag_fetch, tag_write, suffix, key, markers):
 
 
 def main():
+    global SRC, ROUND
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--src", default=SRC)
+    ap.add_argument("--round", default=ROUND)
+    args = ap.parse_args()
+    write_json = args.round == ROUND
+    SRC, ROUND = os.path.abspath(args.src), args.round
     for tag, name in (("prof_d3", "depth3_default"), ("prof_d1", "depth1"), ("prof_m32d1", "depth1_markers32")):
         src = os.path.join(SRC, tag, tag[5:] + "_kernel_stats.csv")
         if os.path.exists(src):
@@ -73,6 +94,8 @@ def main():
         d = workload(*args)
         if d:
             docs[d["workload_key"]] = d
+    if not write_json:
+        return
     with open(os.path.join(OUT, "hbm_traffic.json"), "w") as f:
         json.dump({"workloads": docs}, f, indent=1)
 
