@@ -19,7 +19,7 @@
 extern "C" {
 #endif
 
-#define MOCAP_ABI_VERSION 5
+#define MOCAP_ABI_VERSION 6
 #define MOCAP_API __attribute__((visibility("default")))
 
 enum {
@@ -154,10 +154,16 @@ MOCAP_API int mocap_bayer_gray_u8(mocap_ctx_t ctx, const void* bayer_dev, void* 
                         long spitch, long dpitch, size_t src_image_stride, size_t dst_image_stride, int pattern,
                         int gray_shift, void* stream);
 /* mocap_blob_centroids on raw Bayer frames: the camera loop's cvtColor pair (RealtimeTracking_FLIR.py:103-104) followed by
- * _find_dot (:105) for a batch.  gray_frames_dev receives the gray frames (same pitch and image stride as the Bayer
- * frames); where the geometry allows (width a multiple of 16, height of 8, 16-byte aligned) the conversion is fused
- * with the early-out's streaming pass, so every frame byte is read once and the gray bytes are not read back to be
- * scanned.  Results equal mocap_bayer_gray_u8 followed by mocap_blob_centroids.  H, W >= 3. */
+ * _find_dot (:105) for a batch.  Results equal mocap_bayer_gray_u8 followed by mocap_blob_centroids.  H, W >= 3.
+ * gray_frames_dev == NULL (accepted since ABI 6; the normal use): no gray frame is written anywhere.  The early-out's
+ * streaming pass reads every Bayer byte once, and the filter forms the gray values it needs from the Bayer frames.
+ * That path needs a width that is a multiple of 16, a height that is a multiple of 8, 16-byte aligned frames, pitch and
+ * image stride, and the sparse filter path.
+ * Otherwise (the dense path, MOCAP_SKIP_DARK=0 and MOCAP_GENERAL_FILTER=1 included) the context converts the frames into
+ * a gray scratch buffer of its own, allocated on first use and grown to the largest batch: one frame-sized buffer, and
+ * one gray write and read per pixel.
+ * gray_frames_dev != NULL: the gray frames are written there (same pitch and image stride as the Bayer frames) and read
+ * back by the filter; where the geometry above allows, the conversion is fused with the early-out's streaming pass. */
 MOCAP_API int mocap_blob_centroids_bayer(mocap_ctx_t ctx, const void* bayer_frames_dev, void* gray_frames_dev, int n_images,
                                int cam_mod, int slot_base, size_t image_stride, int pitch, int pattern, int gray_shift,
                                int32_t* out_xy_dev, long xy_stride, int32_t* out_count_dev, long count_stride,

@@ -4,7 +4,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmocap_hip.so")
-ABI_VERSION = 5
+ABI_VERSION = 6
 COMM_ID_BYTES = 128  # MOCAP_COMM_ID_BYTES
 
 

@@ -182,6 +182,8 @@ struct mocap_ctx {
     // the caller's row-major masks pass through masks of the internal layout (kernels.h: mask_word_index), converted at the boundary:
     uint32_t* mask_out; size_t mask_out_images; // mocap_filter_mask filters into this one (a caller-owned mask for run_filter)
     uint32_t* mask_in; size_t mask_in_images;   // mocap_contours_from_mask reads the caller's mask from this one
+    uint8_t* gray_scratch; size_t gray_scratch_bytes; // mocap_blob_centroids_bayer without a gray buffer, where the gray-less path
+                                                      //   cannot run: the gray frames go here (grown to the largest batch)
     void* cwork; size_t cwork_images;      // contour kernel workspace, contour_work_bytes() per image
     uint64_t* walk_list; uint64_t* link_list; uint32_t* walk_count; // contour stage, split form: the batch's border walks / link walks
                                                                     //   (grown with cwork) and their counters
@@ -280,6 +282,7 @@ int mocap_ctx_create(int device_id, int width, int height, int n_slots, mocap_ct
     c->mask = nullptr; c->mask_images = 0; c->mask_dirty = false; c->cells = nullptr; c->cells_images = 0; c->last_images = 0;
     c->hotmap = nullptr; c->tile_rows = nullptr; c->tile_rows_flip = 0; c->tile_rows_hold[0] = c->tile_rows_hold[1] = 0; c->cur_box = nullptr; c->items = nullptr; c->n_items = nullptr; c->cap_items = 0; c->wide_tiles = nullptr; c->cap_wide = 0;
     c->cells_ext = nullptr; c->cur_box_ext = nullptr; c->cells_ext_images = 0;
+    c->gray_scratch = nullptr; c->gray_scratch_bytes = 0;
     c->mask_out = nullptr; c->mask_out_images = 0; c->mask_in = nullptr; c->mask_in_images = 0; c->cwork = nullptr; c->cwork_images = 0; c->walk_list = nullptr; c->link_list = nullptr; c->walk_count = nullptr;
     c->cams = nullptr; c->n_cam = 0; c->n_F = 0; c->scratch = nullptr; c->scratch_elems = 0; c->profiling = false;
     c->ba_obj = nullptr; c->ba_obj_elems = 0; c->ba_pinned = nullptr; c->ba_pinned_bytes = 0;
@@ -340,6 +343,7 @@ int mocap_ctx_destroy(mocap_ctx_t c)
     if (c->cur_box_ext) (void)hipFree(c->cur_box_ext);
     if (c->items) (void)hipFree(c->items);
     if (c->wide_tiles) (void)hipFree(c->wide_tiles);
+    if (c->gray_scratch) (void)hipFree(c->gray_scratch);
     if (c->n_items) (void)hipFree(c->n_items);
     if (c->reach) (void)hipFree(c->reach);
     if (c->cflags) (void)hipFree(c->cflags);
@@ -609,8 +613,22 @@ static int excess_base(int thr_mul, int sel)
     return c < 0 ? 0 : c;
 }
 
+static int ensure_gray_scratch(mocap_ctx* c, size_t bytes)
+{
+    if (bytes <= c->gray_scratch_bytes) return 0;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (bytes <= c->gray_scratch_bytes) return 0;
+    if (c->gray_scratch) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(c->gray_scratch)); c->gray_scratch = nullptr; c->gray_scratch_bytes = 0; }
+    HIP_TRY(hipMalloc(&c->gray_scratch, bytes));
+    c->gray_scratch_bytes = bytes;
+    return 0;
+}
+
 // bayer != nullptr: `frames` (= bayer->dst) does not exist yet -- the Bayer -> gray pass that writes it runs first, fused
-// with the streaming scan where the geometry allows (it has the gray bytes in registers anyway)
+// with the streaming scan where the geometry allows (it has the gray bytes in registers anyway).
+// bayer->dst == nullptr (no gray buffer): the gray-less path where it can run -- the fused scan without its write-back, every
+// marked tile as items of the box kernel's Bayer form, which forms the gray values it reads from the Bayer frames (no wide tiles:
+// the row pipeline has no Bayer form) --, else the gray frames go to the context's scratch buffer and the path above runs.
 static int run_filter(mocap_ctx* c, const void* frames, int n_images, int cam_mod, int slot_base, size_t image_stride,
                       int pitch, uint32_t* mask, uint32_t* cells, hipStream_t s, const BayerArgs* bayer = nullptr)
 {
@@ -680,6 +698,19 @@ static int run_filter(mocap_ctx* c, const void* frames, int n_images, int cam_mo
     // every tile has to be filtered anyway: the dense kernel's sliding row pipeline does that with less work per pixel
     // than the box kernel (MOCAP_DENSE_BOXES=1: the box kernel on whole tiles, a test switch)
     if (allow < 0 && !c->tune.dense_boxes) compact = false;
+    BayerArgs bl;
+    bool direct = false; // the gray-less path
+    if (bayer && !bayer->dst) {
+        bl = *bayer;
+        direct = compact && allow >= 0 && own_mask && bayer_scan_direct(bl);
+        if (!direct) { // the dense path, W % 16 or H % 8 not 0, unaligned frames, MOCAP_SKIP_DARK=0 / MOCAP_GENERAL_FILTER=1
+            const size_t bytes = (size_t)(n_images - 1) * image_stride + (size_t)(c->H - 1) * pitch + c->W;
+            if (int rc = ensure_gray_scratch(c, bytes)) return rc;
+            bl.dst = c->gray_scratch;
+        }
+        frames = direct ? (const void*)bl.src : (const void*)bl.dst;
+        bayer = &bl;
+    }
     if (!compact) {
         // general dense kernel (tiny images, tables beyond the compact format): every tile, every mask byte
         FilterArgs a;
@@ -736,7 +767,8 @@ static int run_filter(mocap_ctx* c, const void* frames, int n_images, int cam_mo
     // 0.53 instead of 0.49.  MOCAP_WIDE_QUADS="remap,identity" overrides (A/B switch; 1000 = never).
     a.wide_tiles = c->wide_tiles; a.cap_wide = c->cap_wide; a.wide_quads_remap = c->tune.wide_quads_remap; a.wide_quads_identity = c->tune.wide_quads_identity;
     a.wide_bands = c->tune.wide_bands; // measured: 2 / 4 bands 0.50 / 0.55 ms against 0.475 (8 markers), 1.33 / 1.58 against 1.22 (32 markers): the kernel is work-bound
-    if (c->W < 4) a.wide_tiles = nullptr;
+    if (c->W < 4 || direct) a.wide_tiles = nullptr;
+    a.bayer = direct ? bl : BayerArgs{}; // (a.src = the Bayer frames)
     a.stage_bytes = c->tune.box_stage_bytes; // test switch
     a.prio = c->tune.box_prio;
     a.ext_mask = own_mask ? 0 : 1;
@@ -773,7 +805,7 @@ static int run_filter(mocap_ctx* c, const void* frames, int n_images, int cam_mo
             b.probe = c->probe_dev;
         }
         c->probe_age = probe ? 1 : c->probe_age + 1;
-        const bool fused = bayer && own_mask && bayer_scan_fusable(*bayer);
+        const bool fused = bayer && own_mask && (direct || bayer_scan_fusable(*bayer)); // direct: the scan without the gray write-back
         // the streaming scan leaves a hot map (two bits per cell, no table lookups or atomics behind its loads) that
         // mark_tiles_kernel turns into tile boxes; the fused Bayer pass marks the tiles itself (MOCAP_SCAN_HOTMAP=0: so does the scan)
         const bool two_step = !fused && c->hotmap && (c->tune.scan_hotmap == 2 || (c->tune.scan_hotmap == 1 && c->hot_dense));
@@ -857,7 +889,7 @@ static int run_filter(mocap_ctx* c, const void* frames, int n_images, int cam_mo
         HIP_TRY(hipGetLastError());
         if (fork_wide) HIP_TRY(hipEventRecord(c->ev_join, c->side));
     }
-    launch_box_filter(a, c->box_grid, s);
+    launch_box_filter(a, c->box_grid, s, direct);
     HIP_TRY(hipGetLastError());
     if (a.wide_tiles && fork_wide) HIP_TRY(hipStreamWaitEvent(s, c->ev_join, 0));
     prof_end(c, 0, s, p, on);
@@ -1111,7 +1143,7 @@ int mocap_blob_centroids(mocap_ctx_t c, const void* frames, int n_images, int ca
 }
 
 static int bayer_args(BayerArgs& a, const void* bayer, void* gray, int n_images, int H, int W, long spitch, long dpitch,
-                      size_t src_image_stride, size_t dst_image_stride, int pattern, int gray_shift);
+                      size_t src_image_stride, size_t dst_image_stride, int pattern, int gray_shift, bool gray_optional = false);
 
 int mocap_blob_centroids_bayer(mocap_ctx_t c, const void* bayer_frames, void* gray_frames, int n_images, int cam_mod, int slot_base,
                                size_t image_stride, int pitch, int pattern, int gray_shift, int32_t* out_xy, long xy_stride,
@@ -1122,7 +1154,8 @@ int mocap_blob_centroids_bayer(mocap_ctx_t c, const void* bayer_frames, void* gr
     if (!out_xy || !out_count || max_blobs < 1 || xy_stride < 2L * max_blobs || count_stride < 1)
         return fail(MOCAP_E_INVALID, "bad output arguments");
     BayerArgs b;
-    if ((rc = bayer_args(b, bayer_frames, gray_frames, n_images, c->H, c->W, pitch, pitch, image_stride, image_stride, pattern, gray_shift)))
+    if ((rc = bayer_args(b, bayer_frames, gray_frames, n_images, c->H, c->W, pitch, pitch, image_stride, image_stride, pattern, gray_shift,
+                         true)))
         return rc;
     if (set_device(c)) return MOCAP_E_HIP;
     if ((rc = ensure_mask(c, n_images))) return rc;
@@ -1196,9 +1229,9 @@ int mocap_box_blur_u8(mocap_ctx_t c, const void* src, void* dst, int H, int W, i
 }
 
 static int bayer_args(BayerArgs& a, const void* bayer, void* gray, int n_images, int H, int W, long spitch, long dpitch,
-                      size_t src_image_stride, size_t dst_image_stride, int pattern, int gray_shift)
+                      size_t src_image_stride, size_t dst_image_stride, int pattern, int gray_shift, bool gray_optional)
 {
-    if (!bayer || !gray) return fail(MOCAP_E_INVALID, "null argument");
+    if (!bayer || (!gray && !gray_optional)) return fail(MOCAP_E_INVALID, "null argument");
     if (n_images < 1 || n_images > 65535 || H < 3 || W < 3 || spitch < W || dpitch < W)
         return fail(MOCAP_E_INVALID, "bad geometry: n=%d H=%d W=%d pitches %ld %ld (H, W >= 3)", n_images, H, W, spitch, dpitch);
     if (n_images > 1 && (src_image_stride < (size_t)spitch * (H - 1) + W || dst_image_stride < (size_t)dpitch * (H - 1) + W))

@@ -17,32 +17,9 @@
 #include <stdint.h>
 #include "kernels.h"
 #include "scan_mark.h"
+#include "bayer.h"
 
 namespace mocap {
-
-__device__ __forceinline__ uint32_t luma(int b, int g, int r, const BayerArgs& a)
-{
-    return ((uint32_t)b * a.cb + (uint32_t)g * a.cg + (uint32_t)r * a.cr + (1u << (a.shift - 1))) >> a.shift;
-}
-
-// colours at a site from its 3x3 neighbourhood (centre c, l/r/u/d, the four diagonals)
-__device__ __forceinline__ uint32_t site_gray(int c, int l, int r_, int u, int d, int ul, int ur, int dl, int dr, bool red_row,
-                                              bool red_col, const BayerArgs& a)
-{
-    const int horiz = (l + r_ + 1) >> 1, vert = (u + d + 1) >> 1;
-    const int cross = (l + r_ + u + d + 2) >> 2, diag = (ul + ur + dl + dr + 2) >> 2;
-    int r, g, b;
-    if (red_row == red_col) { // a red or a blue site
-        g = cross;
-        r = red_row ? c : diag;
-        b = red_row ? diag : c;
-    } else {                  // a green site: its row's colour left and right, the other one above and below
-        g = c;
-        r = red_row ? horiz : vert;
-        b = red_row ? vert : horiz;
-    }
-    return luma(b, g, r, a);
-}
 
 // ---- the 16 (or 8) pixels-per-lane kernel ----------------------------------------------------------------------------
 // Within a row, sites of equal column parity are of one kind, so the lane keeps its pixels (and their neighbours) as
@@ -50,7 +27,6 @@ __device__ __forceinline__ uint32_t site_gray(int c, int l, int r_, int u, int d
 // right neighbours of o (v_perm_b32 each).  Rounded means are then plain 32-bit adds on two pixels at once, which
 // kind of site the even columns hold is a wave-uniform branch (a wave is one row), and "which of the two interpolated
 // colours is red" only swaps two luma coefficients.  Luma per pixel: three v_dot2_u32_u16 that pick the field as they multiply.
-__device__ __forceinline__ uint32_t prm(uint32_t hi, uint32_t lo, uint32_t sel) { return __builtin_amdgcn_perm(hi, lo, sel); }
 __device__ __forceinline__ uint32_t wave_prev(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xf, 0xf, true); }
 __device__ __forceinline__ uint32_t wave_next(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x130, 0xf, 0xf, true); }
 
@@ -79,32 +55,6 @@ __device__ __forceinline__ RowPairs<ND> row_pairs(const uint32_t (&w)[ND])
         r.Ro[ND - 1] = prm(nw, w[ND - 1], 0x0c040c02u);
     }
     return r;
-}
-
-typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t pk_shr(uint32_t v, int n)
-{ // both 16-bit fields shifted right on their own (v_pk_lshrrev_b16): nothing leaks from the upper into the lower field
-    return __builtin_bit_cast(uint32_t, (u16x2)(__builtin_bit_cast(u16x2, v) >> (unsigned short)n));
-}
-__device__ __forceinline__ uint32_t mean2(uint32_t a, uint32_t b) { return pk_shr(a + b + 0x00010001u, 1); }
-__device__ __forceinline__ uint32_t mean4(uint32_t a, uint32_t b, uint32_t c, uint32_t d) { return pk_shr(a + b + c + d + 0x00020002u, 2); }
-
-// luma of the two pixels held in the 16-bit fields of (x, g, y): x = the row's own colour, y = the other one.
-// v_dot2_u32_u16 against (c, 0) / (0, c) picks the field and multiplies in one instruction.
-struct LumaCoef { uint32_t xa, ga, ya, xb, gb, yb, half; int shift; };
-__device__ __forceinline__ uint32_t dot2(uint32_t v, uint32_t c, uint32_t acc)
-{
-    return __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, v), __builtin_bit_cast(u16x2, c), acc, false);
-}
-__device__ __forceinline__ void luma2(uint32_t x, uint32_t g, uint32_t y, const LumaCoef& k, uint32_t& out_a, uint32_t& out_b)
-{
-#ifdef BAYER_LUMA_MUL
-    out_a = ((x & 0xffffu) * k.xa + ((g & 0xffffu) * k.ga + ((y & 0xffffu) * k.ya + k.half))) >> k.shift;
-    out_b = ((x >> 16) * k.xa + ((g >> 16) * k.ga + ((y >> 16) * k.ya + k.half))) >> k.shift;
-#else
-    out_a = dot2(x, k.xa, dot2(g, k.ga, dot2(y, k.ya, k.half))) >> k.shift;
-    out_b = dot2(x, k.xb, dot2(g, k.gb, dot2(y, k.yb, k.half))) >> k.shift;
-#endif
 }
 
 // ND dwords (4 * ND pixels) per lane; the two outer lanes of a wave only feed their neighbours
@@ -178,12 +128,15 @@ __global__ __launch_bounds__(256) void bayer_gray_kernel(BayerArgs a)
 // rows and sums their excess per 8x8 cell on the way (the gray bytes are in registers: the separate scan of the gray
 // frames, one more read of every byte, disappears); hot cells mark tiles exactly as bright_cells_kernel does.
 // Rows 0 and H-1 repeat rows 1 and H-2: they are not computed, their neighbours are written and counted twice.
+// WRITE = false (gray-less Bayer input, a.dst == nullptr): the same scan and marking, no gray row is stored; the box kernel
+// forms the gray values it needs from the Bayer frames itself (box_filter_kernel<true>).
 __device__ __forceinline__ LumaCoef luma_coef(const BayerArgs& a, bool red_row)
 {
     const uint32_t cx = red_row ? a.cr : a.cb, cy = red_row ? a.cb : a.cr;
     return LumaCoef{cx, a.cg, cy, cx << 16, a.cg << 16, cy << 16, 1u << (a.shift - 1), a.shift};
 }
 
+template <bool WRITE>
 __global__ __launch_bounds__(256) void bayer_gray_scan_kernel(BayerArgs a, BrightArgs b)
 {
     constexpr int ND = 4, PX = 16, WAVE_PX = 62 * PX;
@@ -249,7 +202,7 @@ __global__ __launch_bounds__(256) void bayer_gray_scan_kernel(BayerArgs a, Brigh
             out.z = g[8] | (g[9] << 8) | (g[10] << 16) | (g[11] << 24);
             out.w = g[12] | (g[13] << 8) | (g[14] << 16) | (g[15] << 24);
             const bool twice = y == 1 || y == a.H - 2;  // wave-uniform
-            if (writer) {
+            if (WRITE && writer) {
                 *(uint4*)(dst + (size_t)y * a.dpitch + x0) = out;
                 if (y == 1) *(uint4*)(dst + x0) = out;
                 if (y == a.H - 2) *(uint4*)(dst + (size_t)(a.H - 1) * a.dpitch + x0) = out;
@@ -299,15 +252,21 @@ void launch_bayer_gray(const BayerArgs& a, hipStream_t s)
         hipLaunchKernelGGL(bayer_gray_any_kernel, dim3((a.W + 63) / 64, (a.H + 3) / 4, a.n_images), dim3(64, 4), 0, s, a);
 }
 
+bool bayer_scan_direct(const BayerArgs& a)
+{
+    return a.W % 16 == 0 && a.H % 8 == 0 && a.H >= 8 && a.spitch % 16 == 0 && a.sstride % 16 == 0 && (uintptr_t)a.src % 16 == 0;
+}
+
 bool bayer_scan_fusable(const BayerArgs& a)
 {
-    return a.W % 16 == 0 && a.H % 8 == 0 && a.H >= 8 && a.spitch % 16 == 0 && a.dpitch % 16 == 0 && a.sstride % 16 == 0 &&
-           a.dstride % 16 == 0 && (uintptr_t)a.src % 16 == 0 && (uintptr_t)a.dst % 16 == 0;
+    return bayer_scan_direct(a) && a.dpitch % 16 == 0 && a.dstride % 16 == 0 && (uintptr_t)a.dst % 16 == 0;
 }
 
 void launch_bayer_gray_scan(const BayerArgs& a, const BrightArgs& b, hipStream_t s)
 {
-    hipLaunchKernelGGL(bayer_gray_scan_kernel, dim3((a.W + 62 * 16 - 1) / (62 * 16), (a.H / 8 + 3) / 4, a.n_images), dim3(64, 4), 0, s, a, b);
+    const dim3 grid((a.W + 62 * 16 - 1) / (62 * 16), (a.H / 8 + 3) / 4, a.n_images);
+    if (a.dst) hipLaunchKernelGGL(bayer_gray_scan_kernel<true>, grid, dim3(64, 4), 0, s, a, b);
+    else hipLaunchKernelGGL(bayer_gray_scan_kernel<false>, grid, dim3(64, 4), 0, s, a, b);
 }
 
 } // namespace mocap

@@ -23,6 +23,7 @@
 #include <stdint.h>
 #include <type_traits>
 #include "kernels.h"
+#include "bayer.h"
 
 namespace mocap {
 
@@ -47,6 +48,67 @@ __device__ __forceinline__ int taps5(int v, int n)
 }
 // floor(n / d) for 0 <= n < 4096, 1 <= d <= 4096 (float reciprocal, +0.5 keeps every quotient away from an integer)
 __device__ __forceinline__ int small_div(int n, float rcp_d) { return (int)(((float)n + 0.5f) * rcp_d); }
+
+// ---- gray values formed from raw Bayer frames (box_filter_kernel<true>) ------------------------------------------------------
+// gray(x, y) = site_gray at (clamp(x, 1, W-2), clamp(y, 1, H-2)) -- the arithmetic of orc_bayer_gray_u8 / bayer_gray_any_kernel --
+// so that the 3x3 Bayer neighbourhood always lies in the image.  Needs W >= 8, H >= 3.
+struct BayerK { int ry, rx; uint32_t cb, cg, cr; int shift; }; // wave-uniform (plain scalars: no struct in scratch)
+
+// The three Bayer rows around row y that the gray quad at columns x..x+3 reads (x % 4 == 0, 0 <= x <= W - 4, W % 4 == 0 and
+// 16-byte aligned rows: true on the gray-less path): per row the aligned dwords at x - 4, x and x + 4 (clamped into the row; a
+// clamped word is only read for a column whose gray value is replaced by its inner neighbour's).
+struct BayerWin { uint32_t w[9]; };
+__device__ __forceinline__ void bayer_win_load(BayerWin& b, const uint8_t* __restrict__ img, int pitch, int W, int H, int x, int y)
+{
+    const int yc = y < 1 ? 1 : (y > H - 2 ? H - 2 : y);
+    const uint32_t xl = (uint32_t)imax(x - 4, 0), xr = (uint32_t)imin(x + 4, W - 4);
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+        const uint32_t o = (uint32_t)(yc - 1 + r) * (uint32_t)pitch;
+        b.w[3 * r] = *(const uint32_t*)(img + o + xl);
+        b.w[3 * r + 1] = *(const uint32_t*)(img + o + (uint32_t)x);
+        b.w[3 * r + 2] = *(const uint32_t*)(img + o + xr);
+    }
+}
+// the gray quad from its window, two pixels of one kind at a time as in bayer_gray_kernel (16-bit fields: e = columns x, x+2,
+// o = x+1, x+3, Le / Ro their outer neighbours).  The lanes of a staging round lie in different rows, so which of e / o holds the
+// colour sites is a per-lane select of operands (Pc / Pg: colour / green sites, Lx / Rx their left / right neighbours).  Column 0
+// repeats column 1, column W - 1 repeats column W - 2.
+__device__ __forceinline__ uint32_t bayer_gray4(const BayerWin& b, int W, int H, int x, int y, const BayerK& k)
+{
+    const int yc = y < 1 ? 1 : (y > H - 2 ? H - 2 : y);
+    const bool red_row = (yc & 1) == k.ry;
+    const bool eic = (red_row ? k.rx : 1 - k.rx) == 0; // the row's red / blue sites sit on even columns
+    uint32_t Pc[3], Lc[3], Rc[3], Pg[3];
+    uint32_t Lg = 0, Rg = 0;
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+        const uint32_t pw = b.w[3 * r], w = b.w[3 * r + 1], nw = b.w[3 * r + 2];
+        const uint32_t e = prm(0, w, 0x0c020c00u), o = prm(0, w, 0x0c030c01u);
+        const uint32_t Le = prm(pw, w, 0x0c010c07u), Ro = prm(nw, w, 0x0c040c02u);
+        Pc[r] = eic ? e : o; Lc[r] = eic ? Le : e; Rc[r] = eic ? o : Ro; Pg[r] = eic ? o : e;
+        if (r == 1) { Lg = eic ? e : Le; Rg = eic ? Ro : o; }
+    }
+    const uint32_t cx = red_row ? k.cr : k.cb, cy = red_row ? k.cb : k.cr;
+    const LumaCoef kc{cx, k.cg, cy, cx << 16, k.cg << 16, cy << 16, 1u << (k.shift - 1), k.shift};
+    uint32_t ca, cb, ga, gb;
+    // colour sites: own value, green from the cross, the other colour from the diagonals
+    luma2(Pc[1], mean4(Lc[1], Rc[1], Pc[0], Pc[2]), mean4(Lc[0], Rc[0], Lc[2], Rc[2]), kc, ca, cb);
+    // green sites: the row's colour left and right, the other one above and below
+    luma2(mean2(Lg, Rg), Pg[1], mean2(Pg[0], Pg[2]), kc, ga, gb);
+    uint32_t g0 = eic ? ca : ga, g1 = eic ? ga : ca, g2 = eic ? cb : gb, g3 = eic ? gb : cb;
+    if (x == 0) g0 = g1;
+    if (x + 3 == W - 1) g3 = g2;
+    return g0 | (g1 << 8) | (g2 << 16) | (g3 << 24);
+}
+// one gray value (0 <= x < W, 0 <= y < H) from its nine Bayer bytes in memory (the taps-from-memory path: rare, only correct)
+__device__ __forceinline__ uint32_t bayer_gray1(const uint8_t* __restrict__ img, int pitch, int W, int H, int x, int y, const BayerK& k)
+{
+    const int yc = y < 1 ? 1 : (y > H - 2 ? H - 2 : y), xc = x < 1 ? 1 : (x > W - 2 ? W - 2 : x);
+    const uint32_t c = (uint32_t)yc * (uint32_t)pitch + (uint32_t)xc, u = c - (uint32_t)pitch, d = c + (uint32_t)pitch; // 32-bit offsets
+    return site_gray(img[c], img[c - 1], img[c + 1], img[u], img[d], img[u - 1], img[u + 1], img[d - 1], img[d + 1], (yc & 1) == k.ry,
+                     (xc & 1) == k.rx, k);
+}
 
 } // namespace
 
@@ -340,6 +402,9 @@ __device__ __forceinline__ SrcBounds source_bounds_partial(const ushort4* __rest
 // Round 4: groups of 3 trips and 14 staging loads, compiled for four waves per SIMD: 128 registers, no spills, the same duration
 // alone (0.49 ms for the benchmark batch's filters) and +3..7 % for the three-batch pipeline (profiles/history/r4_*.log).
 constexpr size_t BOX_LDS_BYTES = 1024 + (size_t)(BOX_HCAP + 64) * 8 + BOX_SCAP;
+// BAYER = true: a.src holds raw Bayer frames (gray-less input); the three source paths below -- identity rows, staged rectangle,
+// taps from memory -- form the gray values they read with bayer_gray4 / bayer_gray1, everything after them is the same.
+template <bool BAYER>
 __global__ __attribute__((amdgpu_waves_per_eu(MOCAP_BOX_WAVES, MOCAP_BOX_WAVES))) __launch_bounds__(64) void box_filter_kernel(BoxArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t box_lds[];
@@ -361,6 +426,7 @@ __global__ __attribute__((amdgpu_waves_per_eu(MOCAP_BOX_WAVES, MOCAP_BOX_WAVES))
     const uint32_t a_cap_items = a.cap_items;
     const uint32_t* const a_n_items = a.n_items;
     uint64_t* const a_timing = a.timing;
+    const BayerK bk{a.bayer.ry, a.bayer.rx, a.bayer.cb, a.bayer.cg, a.bayer.cr, a.bayer.shift};
     if (a.prio) __builtin_amdgcn_s_setprio(2); // A/B switch: these waves compute, the scan's waves of the next batch wait on HBM
     // lut[w]: byte k = number of set bits among bits k..k+4 of the 8-bit window w
 #pragma unroll
@@ -479,6 +545,28 @@ __global__ __attribute__((amdgpu_waves_per_eu(MOCAP_BOX_WAVES, MOCAP_BOX_WAVES))
             // identity map: the patch is the frame
             const int ax = xc > W - 4 ? W - 4 : xc; // W >= 4
             const uint32_t sh = (uint32_t)((xc - ax) * 8);
+            if constexpr (BAYER) { // the same rows, each lane's gray dword formed from the Bayer rows above, at and below it
+                auto load_rows = [&](BayerWin (&raw)[BOX_GROUP], int gi) __attribute__((always_inline)) {
+#pragma unroll
+                    for (int u = 0; u < BOX_GROUP; u++) {
+                        const int y = hy0 + (ka0 + gi * BOX_GROUP + u) * rpw + rsub, yc = y < ey0 ? ey0 : (y > ey1 ? ey1 : y);
+                        bayer_win_load(raw[u], img, a_pitch, W, H, ax, yc);
+                    }
+                };
+                auto use_rows = [&](const BayerWin (&raw)[BOX_GROUP], int gi) __attribute__((always_inline)) {
+#pragma unroll
+                    for (int u = 0; u < BOX_GROUP; u++) {
+                        const int kt = ka0 + gi * BOX_GROUP + u, r = kt * rpw + rsub, y = hy0 + r, yc = y < ey0 ? ey0 : (y > ey1 ? ey1 : y);
+                        const bool ok = q_exact && y >= ey0 && y <= ey1;
+                        store_h(ok ? ((bayer_gray4(raw[u], W, H, ax, yc, bk) >> sh) & bytemask) : 0u, kt < ka1 ? r : PR);
+                    }
+                };
+                for (int gi = 0; gi < ngroup_e; gi++) { // (one group's windows in flight: 27 registers per group)
+                    BayerWin ra[BOX_GROUP];
+                    load_rows(ra, gi);
+                    use_rows(ra, gi);
+                }
+            } else {
             auto load_rows = [&](uint32_t (&raw)[BOX_GROUP], int gi) __attribute__((always_inline)) {
 #pragma unroll
                 for (int u = 0; u < BOX_GROUP; u++) {
@@ -503,6 +591,7 @@ __global__ __attribute__((amdgpu_waves_per_eu(MOCAP_BOX_WAVES, MOCAP_BOX_WAVES))
                     load_rows(ra, gi + 2);
                     use_rows(rb, gi + 1);
                 }
+            }
             }
         } else {
             // 1. source pixels the exact region reads (their loads were issued during the previous item)
@@ -542,7 +631,26 @@ __global__ __attribute__((amdgpu_waves_per_eu(MOCAP_BOX_WAVES, MOCAP_BOX_WAVES))
                 const int nround = (SR + rpi - 1) / rpi;
                 // the whole source rectangle inside the image (the usual case): no clamps, no masks
                 const bool interior = sya >= 0 && syb <= Hm1 && sxa >= 0 && sxa + SP <= W;
-                if (interior) {
+                if constexpr (BAYER) {
+                    // each lane's gray dword from the Bayer rows above, at and below it (clamped rows: every read lies in the image);
+                    // fewer rows in flight than the gray form, whose 14 loads are one dword each against nine here
+                    constexpr int SB = 4;
+                    for (int r0 = 0; r0 < nround; r0 += SB) {
+                        BayerWin v[SB];
+#pragma unroll
+                        for (int u = 0; u < SB; u++) {
+                            const int gy = sya + (r0 + u) * rpi + srs, gyc = gy < 0 ? 0 : (gy > Hm1 ? Hm1 : gy);
+                            bayer_win_load(v[u], img, a_pitch, W, H, ax, gyc);
+                        }
+#pragma unroll
+                        for (int u = 0; u < SB; u++) {
+                            const int r = (r0 + u) * rpi + srs, gy = sya + r, gyc = gy < 0 ? 0 : (gy > Hm1 ? Hm1 : gy);
+                            const uint32_t val = ((unsigned)gy < (unsigned)H) ? ((bayer_gray4(v[u], W, H, ax, gyc, bk) >> shs) & keep) : 0u;
+                            if (s_on && r < SR) ((uint32_t*)Sbuf)[r * dpr + sc] = val;
+                        }
+                    }
+                    load_table(ta, 0); // (after the staging: its 12 registers would spill beside the windows)
+                } else if (interior) {
                     const uint32_t step = (uint32_t)__mul24(rpi, a_pitch);
                     const int scc = sc < dpr ? sc : dpr - 1; // (lanes past the last dword of a row re-read it)
                     const uint32_t glast = (uint32_t)__mul24(syb, a_pitch) + (uint32_t)(sxa + 4 * scc); // same column, last row
@@ -638,7 +746,38 @@ __global__ __attribute__((amdgpu_waves_per_eu(MOCAP_BOX_WAVES, MOCAP_BOX_WAVES))
                 }
             };
             if (staged) remap_rows(std::true_type{});
-            else remap_rows(std::false_type{});
+            else if constexpr (!BAYER) remap_rows(std::false_type{});
+            else {
+                // taps from memory, each tap's gray from its 3x3 Bayer neighbourhood: rare (strong local distortion), only correct.
+                // One trip at a time and one tap's nine loads in flight: the unrolled groups above would spill here.
+                for (int kt = ka0; kt < ka1; kt++) {
+                    const int r = kt * rpw + rsub, y = hy0 + r, yc = y < ey0 ? ey0 : (y > ey1 ? ey1 : y);
+                    const uint32_t okm = (q_exact && y >= ey0 && y <= ey1) ? bytemask : 0u;
+                    uint4 tw;
+                    __builtin_memcpy(&tw, map4 + ((uint32_t)yc * (uint32_t)W + (uint32_t)xc), 16);
+                    const uint32_t ww[4] = {tw.x, tw.y, tw.z, tw.w};
+                    uint32_t B = 0;
+#pragma unroll
+                    for (int k = 0; k < 4; k++) {
+                        const uint32_t w = ww[k];
+                        const int dx = (int)(w << 21) >> 21, dy = (int)(w << 10) >> 21;
+                        const uint32_t fa = (w >> 22) & 31u, fb = w >> 27;
+                        const int sx = xc + k + dx, sy = yc + dy;
+                        const int sx0 = sx < 0 ? 0 : (sx > W - 1 ? W - 1 : sx), sx1 = sx + 1 < 0 ? 0 : (sx + 1 > W - 1 ? W - 1 : sx + 1);
+                        const int sy0 = sy < 0 ? 0 : (sy > Hm1 ? Hm1 : sy), sy1 = sy + 1 < 0 ? 0 : (sy + 1 > Hm1 ? Hm1 : sy + 1);
+                        uint32_t t00 = bayer_gray1(img, a_pitch, W, H, sx0, sy0, bk); asm volatile("" : "+v"(t00) : : "memory");
+                        uint32_t t01 = bayer_gray1(img, a_pitch, W, H, sx1, sy0, bk); asm volatile("" : "+v"(t01) : : "memory");
+                        uint32_t t10 = bayer_gray1(img, a_pitch, W, H, sx0, sy1, bk); asm volatile("" : "+v"(t10) : : "memory");
+                        uint32_t t11 = bayer_gray1(img, a_pitch, W, H, sx1, sy1, bk); asm volatile("" : "+v"(t11) : : "memory");
+                        const bool c0 = sx0 == sx, c1 = sx1 == sx + 1, r0 = sy0 == sy, r1 = sy1 == sy + 1;
+                        const uint32_t p00 = (c0 && r0) ? t00 : 0u, p01 = (c1 && r0) ? t01 : 0u, p10 = (c0 && r1) ? t10 : 0u, p11 = (c1 && r1) ? t11 : 0u;
+                        const uint32_t wa = 32u - fa, wb = 32u - fb;
+                        const uint32_t top = __umul24(p00, wa) + __umul24(p01, fa), bot = __umul24(p10, wa) + __umul24(p11, fa);
+                        B |= ((__umul24(top, wb) + __umul24(bot, fb) + 512u) >> 10) << (8 * k);
+                    }
+                    store_h(B & okm, r);
+                }
+            }
         }
         __syncthreads();
         tick(2);
@@ -765,13 +904,14 @@ void launch_settle_tiles(const BoxArgs& a, hipStream_t s)
 int box_filter_blocks_per_cu()
 {
     int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, box_filter_kernel, 64, BOX_LDS_BYTES) != hipSuccess || n < 1) n = 8;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, box_filter_kernel<false>, 64, BOX_LDS_BYTES) != hipSuccess || n < 1) n = 8;
     return n;
 }
 
-void launch_box_filter(const BoxArgs& a, int grid, hipStream_t s)
+void launch_box_filter(const BoxArgs& a, int grid, hipStream_t s, bool bayer)
 {
-    hipLaunchKernelGGL(box_filter_kernel, dim3(grid), dim3(64), BOX_LDS_BYTES, s, a);
+    if (bayer) hipLaunchKernelGGL(box_filter_kernel<true>, dim3(grid), dim3(64), BOX_LDS_BYTES, s, a);
+    else hipLaunchKernelGGL(box_filter_kernel<false>, dim3(grid), dim3(64), BOX_LDS_BYTES, s, a);
 }
 
 } // namespace mocap

@@ -53,6 +53,17 @@ struct FilterArgs {
 void launch_rowbox(const uint32_t* map4, ushort4* rowbox, int H, int W, int n_strips, hipStream_t s);
 int rows_stage_dwords();
 
+// Bayer -> gray (bayer_gray.hip): red sites at row parity ry / column parity rx, luma coefficients cb, cg, cr >> shift
+struct BayerArgs {
+    const uint8_t* src; uint8_t* dst;
+    int H, W, n_images;
+    long spitch, dpitch;
+    size_t sstride, dstride;
+    int ry, rx;
+    uint32_t cb, cg, cr;
+    int shift;
+};
+
 // The sparse half of the filter stage (blob_boxes.hip): tiles, boxes, work items.
 // A tile = 240 mask columns x rows_per_chunk rows.  The scan kernel leaves per tile the box of mask rows / columns that
 // hot cells can reach (tile_rows); settle_tiles_kernel turns the boxes into items; box_filter_kernel consumes them.
@@ -97,9 +108,12 @@ struct BoxArgs {
     uint32_t* zero8;            // not null: 8 words (the contour stage's walk counters) that settle zeroes -- in place of a fill launch
     int dense;                  // 1 = no early-out: every tile is filtered whole
     int ext_mask;               // 1 = caller-owned mask (cleared by the scan kernel, or written whole when dense)
+    // gray-less Bayer input (box_filter_kernel<true>): src / pitch / image_stride are the raw Bayer frames', the kernel forms
+    // every gray value it reads from their 3x3 neighbourhood (bayer.src / dst are not used; W % 16 == 0, H >= 8)
+    BayerArgs bayer;
 };
 void launch_settle_tiles(const BoxArgs& a, hipStream_t s);
-void launch_box_filter(const BoxArgs& a, int grid, hipStream_t s);
+void launch_box_filter(const BoxArgs& a, int grid, hipStream_t s, bool bayer = false);
 int box_filter_blocks_per_cu();
 void launch_srcbox(const uint32_t* map4, ushort4* srcbox, int H, int W, hipStream_t s);
 
@@ -219,19 +233,11 @@ void launch_undistort(const uint8_t* src, uint8_t* dst, int H, int W, int sp, in
 void launch_mask_expand(const uint32_t* mask, int wpr, uint8_t* dst, int H, int W, int dp, hipStream_t s);
 void launch_median5(const uint8_t* src, uint8_t* dst, int H, int W, int sp, int dp, int ithresh, int apply, hipStream_t s);
 void launch_demosaic(const uint8_t* bayer, uint8_t* bgr, int H, int W, int sp, hipStream_t s);
-// Bayer -> gray (bayer_gray.hip): red sites at row parity ry / column parity rx, luma coefficients cb, cg, cr >> shift
-struct BayerArgs {
-    const uint8_t* src; uint8_t* dst;
-    int H, W, n_images;
-    long spitch, dpitch;
-    size_t sstride, dstride;
-    int ry, rx;
-    uint32_t cb, cg, cr;
-    int shift;
-};
 void launch_bayer_gray(const BayerArgs& a, hipStream_t s);
-// the same pass fused with the early-out's scan of the gray frames it writes (bayer_scan_fusable: W % 16 == 0, H % 8 == 0, aligned)
+// the same pass fused with the early-out's scan of the gray frames it writes (bayer_scan_fusable: W % 16 == 0, H % 8 == 0, aligned);
+// a.dst == nullptr: the scan alone, no gray frame is written (bayer_scan_direct: only the Bayer side's conditions)
 bool bayer_scan_fusable(const BayerArgs& a);
+bool bayer_scan_direct(const BayerArgs& a);
 void launch_bayer_gray_scan(const BayerArgs& a, const BrightArgs& b, hipStream_t s);
 
 // ---- geometry ----

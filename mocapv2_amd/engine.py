@@ -147,8 +147,12 @@ class MocapContext:
         slot_base + n % cam_mod).  Results land in centroid records, int32 [n, 2 + 2*max_blobs]:
         record[0] = number of image points, record[2:] = (cx, cy) pairs in the reference's contour order.
         Returns the records tensor (use record_views for xy / count views).
-        bayer_pattern 0..3 (BG, GB, RG, GR): the frames are raw sensor frames; the camera loop's cvtColor pair
-        (RealtimeTracking_FLIR.py:103-104) runs first, into `gray` (same shape as frames; allocated when None)."""
+        bayer_pattern 0..3 (BG, GB, RG, GR): the frames are raw sensor frames and the camera loop's cvtColor pair
+        (RealtimeTracking_FLIR.py:103-104) comes first.  gray=None: no gray frame is allocated or written; the library
+        forms the gray values from the Bayer frames where it needs them, or, on geometries that path does not cover
+        (width not a multiple of 16, height not of 8, unaligned frames, the dense path), converts into a scratch buffer of
+        the context's own.  A tensor passed as `gray` (same shape as frames) is filled with the gray frames.  The records
+        are the same either way."""
         flat, n, stride, pitch = self._frames(frames)
         rec_ints = 2 + 2 * max_blobs
         if records is None:
@@ -159,9 +163,7 @@ class MocapContext:
             _abi.check(self.lib.mocap_blob_centroids(self._h, _ptr(flat), n, cam_mod, slot_base, stride, pitch, xy_ptr, rec_ints,
                                                      _ptr(records), rec_ints, max_blobs, _stream()))
             return records
-        if gray is None:
-            gray = torch.empty_strided(flat.shape, flat.stride(), dtype=torch.uint8, device=self.device)
-        assert gray.dtype == torch.uint8 and gray.is_cuda and gray.reshape(flat.shape).stride() == flat.stride()
+        assert gray is None or (gray.dtype == torch.uint8 and gray.is_cuda and gray.reshape(flat.shape).stride() == flat.stride())
         _abi.check(self.lib.mocap_blob_centroids_bayer(self._h, _ptr(flat), _ptr(gray), n, cam_mod, slot_base, stride, pitch,
                                                        bayer_pattern, gray_shift, xy_ptr, rec_ints, _ptr(records), rec_ints,
                                                        max_blobs, _stream()))

@@ -168,7 +168,6 @@ class _Lane:
         self.ctx, self.records, self.stream, self.out = ctx, records, stream, None
         self.gathered = None # all ranks' records (collective == "rccl")
         self.staging = None  # device copy of a batch that arrived in host memory
-        self.gray = None     # gray frames of a batch that arrived as raw Bayer frames
 
 
 class BatchTracker:
@@ -193,8 +192,9 @@ class BatchTracker:
         self.world, self.rank, self.group = world, rank, group
         self.t_total = self.T * world
         self.max_points, self.max_groups = max_points, max_groups
-        # raw sensor frames: the camera loop's Bayer -> BGR -> gray (RealtimeTracking_FLIR.py:103-104) runs first, on the
-        # batch's own stream and into the batch's own gray buffer (pattern 0..3 = BG, GB, RG, GR; None = gray frames)
+        # raw sensor frames: the camera loop's Bayer -> BGR -> gray (RealtimeTracking_FLIR.py:103-104) comes first, with no gray
+        # frame in memory: the library forms the gray values where its kernels read them (pattern 0..3 = BG, GB, RG, GR; None =
+        # gray frames; MocapContext.blob_centroids says where a context scratch buffer takes over)
         self.bayer_pattern, self.gray_shift = bayer_pattern, gray_shift
         self.segs = shard_plan(self.n_cam, self.T, world, rank)
         local_cams = sorted({c for c, _, _ in self.segs})
@@ -287,25 +287,18 @@ class BatchTracker:
 
     def extract(self, frames):
         """Stage A on this rank's block.  frames: uint8 [per, H, W] on the GPU, ordered as local_image_list(); raw Bayer
-        frames when the tracker was built with `bayer_pattern` (their gray version goes to the batch's own buffer).
+        frames when the tracker was built with `bayer_pattern` (no gray frame is allocated: see MocapContext.blob_centroids).
         Fills and returns self.records ([per, REC] int32, one centroid record per image)."""
         ctx = self.ctx
         kw = {}
         if self.bayer_pattern is not None:
-            lane = self._cur
-            if lane.gray is None or lane.gray.shape != frames.shape:
-                lane.gray = torch.empty(frames.shape, dtype=torch.uint8, device=ctx.device)
             kw = {"bayer_pattern": self.bayer_pattern, "gray_shift": self.gray_shift}
         if self.world == 1:
-            if kw:
-                kw["gray"] = self._cur.gray
             ctx.blob_centroids(frames, cam_mod=self.n_cam, max_blobs=self.max_points, records=self.records, **kw)
             return self.records
         o = 0
         for c, t0, t1 in self.segs:
             n = t1 - t0
-            if kw:
-                kw["gray"] = self._cur.gray[o:o + n]
             ctx.blob_centroids(frames[o:o + n], cam_mod=1, slot_base=self.slot_of[c], max_blobs=self.max_points,
                                records=self.records[o:o + n], **kw)
             o += n

@@ -49,8 +49,9 @@ class ReplayTracker:
         self.tracker = BatchTracker(K, dist, R, t, F, width, height, self.batch, device=device, max_points=max_points,
                                     max_groups=max_groups, bayer_pattern=bayer_pattern, gray_shift=gray_shift, depth=self.depth)
         self.point = [0, 0, 0, 0, 0, 0, 0, 0]  # RealtimeTracking_FLIR.py:171 (eight zeros until the first detection)
-        # raw sensor frames: the camera loop's cvtColor(BAYER_GR2BGR) + cvtColor(BGR2GRAY) (:103-104) run on the GPU first;
-        # bayer_pattern 0..3 = BG, GB, RG, GR (the reference: 3), None = the frames are gray already
+        # raw sensor frames: the camera loop's cvtColor(BAYER_GR2BGR) + cvtColor(BGR2GRAY) (:103-104) run on the GPU first, with
+        # no gray frame in memory (BatchTracker.extract); bayer_pattern 0..3 = BG, GB, RG, GR (the reference: 3), None = the
+        # frames are gray already
         self.bayer_pattern, self.gray_shift = bayer_pattern, gray_shift
 
     def _select(self, xyz, order, n):
