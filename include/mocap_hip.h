@@ -19,7 +19,7 @@
 extern "C" {
 #endif
 
-#define MOCAP_ABI_VERSION 6
+#define MOCAP_ABI_VERSION 7
 #define MOCAP_API __attribute__((visibility("default")))
 
 enum {
@@ -40,7 +40,10 @@ enum {
                                      groups in the whole time step than its share of the error scratch holds: max(2 * max_groups,
                                      8192) by default, raised with mocap_set_tuning(ctx, "corr_step_groups", n) */
     MOCAP_CORR_E_TRUNCATED = -3,  /* a camera holds more image points than the P that mocap_correspond was told to read */
-    MOCAP_CORR_E_BLOB = -4        /* a camera's point count is negative: its blob stage reported MOCAP_BLOB_E_* */
+    MOCAP_CORR_E_BLOB = -4,       /* a camera's point count is negative: its blob stage reported MOCAP_BLOB_E_* */
+    MOCAP_FUND_E_SAMPLE = -2,     /* mocap_fundamental_ransac: a sample index outside its pair's point list */
+    MOCAP_FUND_E_DEGENERATE = -3  /* no valid hypothesis (e.g. coincident points), a winner with fewer than 8 inliers, or
+                                     inliers that do not span a model in the refit */
 };
 
 typedef struct mocap_ctx* mocap_ctx_t;
@@ -226,6 +229,31 @@ MOCAP_API int mocap_reproject_batch(mocap_ctx_t ctx, const double* pts_dev, cons
 MOCAP_API int mocap_ba_residuals(mocap_ctx_t ctx, const double* params_host, int B, const double* pts_dev,
                                  const uint8_t* valid_dev, int N, int C, float* residuals_host, int32_t* counts_host,
                                  void* stream);
+
+/* cv.findFundamentalMat(p1, p2, cv.FM_RANSAC, threshold, .) (CalculateCameraPoses.py:189) for n_pairs camera pairs in one
+ * call.  Not OpenCV's random sequence nor its 7-point solver: the definition of DESIGN.md section 2 (FP64 throughout).
+ * The caller draws the samples: hypothesis h of pair p is the normalised 8-point solve (Hartley normalisation, smallest
+ * eigenvector of A^T A, rank 2, unit Frobenius norm) over the 8 distinct points samples[p][h][0..7]; a point is an inlier
+ * iff the larger of its two squared point-to-epipolar-line distances is <= threshold^2; the valid hypothesis with the most
+ * inliers wins, the lowest index on ties.
+ *   pts_a_dev, pts_b_dev  float64 [total][2]: the pairs' point lists one after another (a: first camera, b: second;
+ *                         x_b^T F x_a = 0)
+ *   pair_offset_host      int32 [n_pairs + 1] HOST array, copied before the call returns: pair p owns points
+ *                         offset[p] .. offset[p + 1] - 1; at least 8 points per pair
+ *   samples_dev, H        int32 [n_pairs][H][8], indices local to the pair
+ *   refit                 != 0: F_refit_dev receives the 8-point solve over all inliers of the winner (the mask is NOT
+ *                         recomputed under it); 0: F_refit_dev is not written and may be NULL
+ *   F_sample_dev, F_refit_dev  float64 [n_pairs][9] row-major, unit norm; not written for a failed pair
+ *   inlier_dev            uint8 [total]: 1 = inlier of its pair's winner (0 everywhere in a failed pair)
+ *   status_dev            int32 [n_pairs][2] = (winning hypothesis, its inlier count), or (MOCAP_FUND_E_* < 0, 0): the pair
+ *                         has no result.  Nothing is ever returned silently wrong
+ *   counts_dev            int32 [n_pairs][H] inliers of every hypothesis (0 for an invalid one), or NULL (tests, tuning)
+ * Asynchronous on `stream`.  The hypotheses' matrices and counters live in scratch the context owns and grows on demand:
+ * calls on one context must be ordered on one stream.  A pair's results do not depend on the rest of the batch. */
+MOCAP_API int mocap_fundamental_ransac(mocap_ctx_t ctx, int n_pairs, const double* pts_a_dev, const double* pts_b_dev,
+                                       const int32_t* pair_offset_host, const int32_t* samples_dev, int H, double threshold,
+                                       int refit, double* F_sample_dev, double* F_refit_dev, uint8_t* inlier_dev,
+                                       int32_t* status_dev, int32_t* counts_dev, void* stream);
 
 /* The path's one exchange step: with the cameras sharded over GPUs (one process per GPU), every rank
  * contributes the fixed-size centroid records of its images and receives all ranks' records, in rank order, before

@@ -4,7 +4,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmocap_hip.so")
-ABI_VERSION = 6
+ABI_VERSION = 7
 COMM_ID_BYTES = 128  # MOCAP_COMM_ID_BYTES
 
 
@@ -59,6 +59,7 @@ SIGNATURES = {
     "mocap_correspond": [_vp, _vp, _l, _l, _vp, _l, _l, _i, _i, _i, _i, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "mocap_epipolar_scores": [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp],
     "mocap_ba_residuals": [_vp, _dp, _i, _vp, _vp, _i, _i, C.POINTER(C.c_float), _ip, _vp],
+    "mocap_fundamental_ransac": [_vp, _i, _vp, _vp, _ip, _vp, _i, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "mocap_triangulate_batch": [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp],
     "mocap_reproject_batch": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp],
     "mocap_comm_unique_id": [_vp],

@@ -1,18 +1,22 @@
 """Calibration-time batch paths: the arithmetic of the reference's
-`CalculateCameraPoses.py` -- relative pose from a fundamental matrix with the four-candidate cheirality vote
-(:195-231), bundle adjustment (lib/Helpers.py:158-176), origin / floor alignment (:283-361) and
+`CalculateCameraPoses.py` -- fundamental matrices from image points by RANSAC (:189), relative pose from a fundamental
+matrix with the four-candidate cheirality vote (:195-231), bundle adjustment (lib/Helpers.py:158-176), origin / floor alignment (:283-361) and
 `poses_to_fundamental_matrix` (:26-78) -- on top of the same HIP triangulation / reprojection kernels the per-frame
 path uses.
 
 What is batched that the reference loops over:
+  * `cv.findFundamentalMat(p1, p2, cv.FM_RANSAC, 10, .)` per consecutive camera pair (:189) is ONE call for any list of
+    camera pairs (`find_fundamental_matrices`; `tracker_fundamentals` for the pairs 0 -> i the tracker needs): every
+    hypothesis of every pair is solved and scored on the GPU (csrc/fundamental.hip; definition in DESIGN.md section 2);
   * the four (R, t) candidates are triangulated by ONE launch over 4 N groups (the reference calls
     `triangulate_points` four times, one Python SVD per point);
   * one bundle-adjustment Jacobian (SciPy's 2-point forward differences: 6 perturbed parameter vectors per free
     camera) is ONE triangulation launch + ONE reprojection launch over 7 N groups instead of 6 x 2 x N Python calls;
     steps and rounding are SciPy's, so the optimiser walks the same iterates as the reference's
     `least_squares(..., jac='2-point')`.
-Image capture, `cv.findFundamentalMat` (RANSAC) and the plotting / JSON writing of that script are outside the path;
-fundamental matrices come in as arguments.
+Image capture and the plotting / JSON writing of that script are outside the path.  `calculate_extrinsics` is the
+script's function of that name (:162-255) from image points to poses; the pieces still take fundamental matrices as
+arguments.
 """
 import json
 from itertools import combinations
@@ -53,6 +57,148 @@ def _intrinsics(camera_params, n):
     K = [np.asarray(camera_params[i % len(camera_params)]["intrinsic_matrix"], float) for i in range(n)]
     d = [np.asarray(camera_params[i % len(camera_params)]["distortion_coef"], float).ravel()[:5] for i in range(n)]
     return np.array(K), np.array(d)
+
+
+# ---- fundamental matrices: batched RANSAC on the GPU --------------------------------------------------------------
+def sample_table(n_points, hypotheses, seed):
+    """The sample table of `mocap_fundamental_ransac`: int32 [hypotheses][8] point indices, 8 distinct ones per row, from
+    `default_rng(seed).integers(0, n_points, (H, 8))`; rows holding an index twice are redrawn from the same generator
+    until none is left.  The host draws, the device never does: a run is reproducible from its seed."""
+    n_points, hypotheses = int(n_points), int(hypotheses)
+    if n_points < 8:
+        raise ValueError(f"a fundamental matrix needs at least 8 points, got {n_points}")
+    if hypotheses < 1:
+        raise ValueError(f"hypotheses = {hypotheses}")
+    rng = np.random.default_rng(seed)
+    S = rng.integers(0, n_points, (hypotheses, 8))
+    while True:
+        srt = np.sort(S, axis=1)
+        bad = np.flatnonzero((srt[:, 1:] == srt[:, :-1]).any(axis=1))
+        if len(bad) == 0:
+            break
+        S[bad] = rng.integers(0, n_points, (len(bad), 8))
+    return np.ascontiguousarray(S, np.int32)
+
+
+def _scaled_like_cv2(F):
+    """OpenCV's 8-point solver returns F scaled so that F[2, 2] = 1 when that entry is not negligible."""
+    F = np.asarray(F, float).reshape(3, 3)
+    return F / F[2, 2] if abs(F[2, 2]) > np.finfo(float).eps else F.copy()
+
+
+def find_fundamental_matrices(image_points, pairs, valid=None, threshold=10.0, hypotheses=1000, seed=0, refit=True, ctx=None,
+                              details=False):
+    """`cv.findFundamentalMat(p_i, p_j, cv.FM_RANSAC, threshold, .)` (reference CalculateCameraPoses.py:189) for a list of
+    camera pairs in ONE batched GPU call (engine.MocapContext.fundamental_ransac -> mocap_fundamental_ransac).
+    image_points [C][N][2]; pairs: list of (i, j), F maps camera-i pixels to camera-j lines (x_j^T F x_i = 0); valid
+    [C][N] (optional): a pair uses the points both of its cameras saw.  Pair k draws its sample table from seed + k.
+    Returns a list of (F, mask) per pair in the shape of cv2's return: F 3x3 scaled to F[2, 2] = 1, mask uint8 [N, 1] over
+    ALL N points (0 for points the pair did not use); (None, None) for a pair that fails (fewer than 8 common points, no
+    valid hypothesis, a winner with fewer than 8 inliers), as cv2 returns None.  details=True appends the engine's dict
+    (unit-norm F_sample / F_refit, best, n_inliers) to each tuple."""
+    ip = np.asarray(image_points, float)
+    if ip.ndim != 3 or ip.shape[2] != 2:
+        raise ValueError(f"image_points must be [C][N][2], got {ip.shape}")
+    Cn, N = ip.shape[:2]
+    vis = np.ones((Cn, N), bool) if valid is None else np.asarray(valid).astype(bool).reshape(Cn, N)
+    if not float(threshold) > 0 or int(hypotheses) < 1:
+        raise ValueError(f"threshold = {threshold}, hypotheses = {hypotheses}")
+    use, lists, tables = [], [], []
+    for k, (i, j) in enumerate(pairs):
+        if not (0 <= i < Cn and 0 <= j < Cn and i != j):
+            raise ValueError(f"pair {(i, j)} is not two different cameras of {Cn}")
+        idx = np.flatnonzero(vis[i] & vis[j])
+        use.append(idx)
+        if len(idx) >= 8:
+            lists.append((ip[i][idx], ip[j][idx]))
+            tables.append(sample_table(len(idx), hypotheses, seed + k))
+    ctx = ctx or default_context()
+    res = iter(ctx.fundamental_ransac(lists, tables, threshold, refit=refit) if lists else [])
+    out = []
+    for idx in use:
+        r = next(res) if len(idx) >= 8 else None
+        if r is None or r["best"] < 0:
+            out.append((None, None, r) if details else (None, None))
+            continue
+        mask = np.zeros((N, 1), np.uint8)
+        mask[idx, 0] = r["mask"]
+        F = _scaled_like_cv2(r["F_refit"] if refit else r["F_sample"])
+        out.append((F, mask, r) if details else (F, mask))
+    return out
+
+
+def find_fundamental_matrix(points1, points2, threshold=10.0, hypotheses=1000, seed=0, refit=True, ctx=None):
+    """`cv.findFundamentalMat(points1, points2, cv.FM_RANSAC, threshold, .)` -> (F, mask) on the GPU: x2^T F x1 = 0, F
+    scaled to F[2, 2] = 1, mask uint8 [N, 1]; (None, None) when the pair fails.  Defaults: the reference's threshold of 10
+    pixels (CalculateCameraPoses.py:189) and 1000 hypotheses, cv2's iteration cap for this overload.  ALL hypotheses are
+    evaluated: there is no early exit by confidence on a GPU (the batch is one launch sequence; cv2's 0.99999 has no
+    counterpart).  The 8-point solver stands in for cv2's 7-point one and the host's seeded generator for cv2's own, so the
+    result is cv2's up to the choice of samples, not bit for bit.  refit: F is the 8-point fit over
+    all inliers of the best sample (cv2 does the same); the mask is the best sample's."""
+    p1 = np.asarray(points1, float)
+    p2 = np.asarray(points2, float)
+    if p1.ndim != 2 or p1.shape[1] != 2 or p1.shape != p2.shape:
+        raise ValueError(f"points1 / points2 must both be [N][2], got {p1.shape} and {p2.shape}")
+    if len(p1) < 8:
+        raise ValueError(f"a fundamental matrix needs at least 8 point pairs, got {len(p1)}")
+    if not (np.isfinite(p1).all() and np.isfinite(p2).all()):
+        raise ValueError("points must be finite")
+    if int(hypotheses) < 1:
+        raise ValueError(f"hypotheses = {hypotheses}")
+    return find_fundamental_matrices(np.stack([p1, p2]), [(0, 1)], None, threshold, hypotheses, seed, refit, ctx)[0]
+
+
+def tracker_fundamentals(image_points, valid=None, threshold=10.0, hypotheses=1000, seed=0, refit=True, ctx=None):
+    """Fs of the tracker (`mocap_set_fundamentals`, lib.Helpers.Fs): Fs[i - 1] = F(camera 0 -> camera i) for EVERY camera
+    i = 1..C-1, estimated from wand points in one batched call.  (The reference only estimates the chain i -> i + 1 and
+    writes each matrix twice, CalculateCameraPoses.py:190-191, which serves two cameras.)  Raises when a pair fails."""
+    ip = np.asarray(image_points, float)
+    pairs = [(0, i) for i in range(1, len(ip))]
+    res = find_fundamental_matrices(ip, pairs, valid, threshold, hypotheses, seed, refit, ctx)
+    for (i, j), (F, _) in zip(pairs, res):
+        if F is None:
+            raise ValueError(f"no fundamental matrix for cameras {i} -> {j}")
+    return [F for F, _ in res]
+
+
+def calculate_extrinsics(image_points, camera_params, threshold=10.0, hypotheses=1000, seed=0, refit=True, ctx=None):
+    """reference `calculate_extrinsics` (CalculateCameraPoses.py:162-255) without plotting and file writing: RANSAC per
+    consecutive camera pair (:189, one batched call here), E = K2^T F K1 and the four-candidate vote
+    (`extrinsics_from_fundamentals`), bundle adjustment over the first two cameras (the reference's residual is
+    two-camera, lib/Helpers.py:161-167), final triangulation and mean reprojection error.
+    Returns dict: poses_initial, poses (after BA; cameras beyond the second keep their initial pose), pair_Fs (one per
+    consecutive pair, for `save_fundamentals`), masks, votes (per link: the four candidates' cheirality counts),
+    object_points [N][3], error (mean of the per-point reprojection MSE), ba_result (SciPy's)."""
+    ctx = ctx or default_context()
+    ip = np.asarray(image_points, float)
+    if ip.ndim != 3 or ip.shape[0] < 2 or ip.shape[2] != 2:
+        raise ValueError(f"image_points must be [C >= 2][N][2], got {ip.shape}")
+    pairs = [(i, i + 1) for i in range(len(ip) - 1)]
+    res = find_fundamental_matrices(ip, pairs, None, threshold, hypotheses, seed, refit, ctx)
+    for (i, j), (F, _) in zip(pairs, res):
+        if F is None:
+            raise ValueError(f"no fundamental matrix for cameras {i} -> {j}")
+    pair_Fs = [F for F, _ in res]
+    K2, _ = _intrinsics(camera_params, 2)
+    initial, votes = [{"R": np.eye(3), "t": np.zeros((3, 1))}], []
+    for i, F in enumerate(pair_Fs):  # the loop of extrinsics_from_fundamentals, keeping each link's vote
+        R1, R2, t = decompose_essential(K2[1].T @ F @ K2[0])
+        link = select_relative_pose(ip[i], ip[i + 1], initial[-1], R1, R2, t, camera_params, ctx)
+        initial.append(link["pose"])
+        votes.append(link["counts"])
+    two = np.transpose(ip[:2], (1, 0, 2))
+    ba_poses, result = bundle_adjustment(two, initial[:2], camera_params, ctx=ctx)
+    poses = [{"R": np.asarray(p["R"], float), "t": np.asarray(p["t"], float).reshape(3, 1)} for p in ba_poses] + initial[2:]
+    n = len(poses)
+    K, d = _intrinsics(camera_params, n)
+    ctx.set_cameras(K, d, np.array([p["R"] for p in poses]), np.array([np.asarray(p["t"], float).reshape(3) for p in poses]))
+    groups = np.transpose(ip, (1, 0, 2))
+    ones = np.ones(groups.shape[:2], np.uint8)
+    xyz, _ = ctx.triangulate_batch(groups, ones, compact_k=True)
+    mse, _ = ctx.reproject_batch(groups, ones, xyz, compact_k=True)
+    return {"poses_initial": initial, "poses": poses, "pair_Fs": pair_Fs, "masks": [m for _, m in res], "votes": votes,
+            "object_points": xyz,
+            "error": float(np.mean(mse)), "ba_result": result}
 
 
 # ---- relative pose: four candidates, one launch -----------------------------------------------------------------
@@ -226,7 +372,8 @@ def calculate_normal(points_3d):
 
 
 def rotation_matrix_from_vectors(vec_orig, vec_rot):
-    """reference :335-363: Rodrigues rotation taking vec_orig onto vec_rot."""
+    """reference :335-363: Rodrigues rotation taking vec_orig onto vec_rot.  Follows the reference's function nearly line
+    for line (the same case split and the same formula), so that `set_floor` rotates exactly as the reference does."""
     a = np.asarray(vec_orig, float) / np.linalg.norm(vec_orig)
     b = np.asarray(vec_rot, float) / np.linalg.norm(vec_rot)
     cross = np.cross(a, b)
@@ -322,4 +469,5 @@ def pair_fundamentals(Fs):
 __all__ = ["poses_to_fundamental_matrix", "decompose_essential", "select_relative_pose", "extrinsics_from_fundamentals",
            "residuals_batched", "forward_difference_steps", "residual_and_jacobian", "bundle_adjustment", "set_origin",
            "calculate_normal", "rotation_matrix_from_vectors", "set_floor", "get_points", "save_extrinsics", "save_objects",
-           "save_fundamentals", "pair_fundamentals"]
+           "save_fundamentals", "pair_fundamentals", "sample_table", "find_fundamental_matrix", "find_fundamental_matrices",
+           "tracker_fundamentals", "calculate_extrinsics"]

@@ -190,6 +190,7 @@ struct mocap_ctx {
     CameraTable* cams; int n_cam, n_F;
     double* scratch; size_t scratch_elems;
     double* ba_obj; size_t ba_obj_elems;   // object points of mocap_ba_residuals, [B][N][3]
+    void* fund_scratch; size_t fund_scratch_bytes; // mocap_fundamental_ransac: every hypothesis' matrix, the counters, the pair offsets
     void* ba_pinned; size_t ba_pinned_bytes; // its host-side hand-over: parameters in, residuals + counts out (the kernel reads / writes it directly)
     std::shared_ptr<struct SharedComm> comm; // RCCL communicator of mocap_comm_init / mocap_comm_share, else null
     bool profiling;
@@ -286,6 +287,7 @@ int mocap_ctx_create(int device_id, int width, int height, int n_slots, mocap_ct
     c->mask_out = nullptr; c->mask_out_images = 0; c->mask_in = nullptr; c->mask_in_images = 0; c->cwork = nullptr; c->cwork_images = 0; c->walk_list = nullptr; c->link_list = nullptr; c->walk_count = nullptr;
     c->cams = nullptr; c->n_cam = 0; c->n_F = 0; c->scratch = nullptr; c->scratch_elems = 0; c->profiling = false;
     c->ba_obj = nullptr; c->ba_obj_elems = 0; c->ba_pinned = nullptr; c->ba_pinned_bytes = 0;
+    c->fund_scratch = nullptr; c->fund_scratch_bytes = 0;
     c->comm.reset();
     c->side = nullptr; c->ev_fork = nullptr; c->ev_join = nullptr;
     c->tune = tuning_from_env();
@@ -362,6 +364,7 @@ int mocap_ctx_destroy(mocap_ctx_t c)
     if (c->cams) (void)hipFree(c->cams);
     if (c->scratch) (void)hipFree(c->scratch);
     if (c->ba_obj) (void)hipFree(c->ba_obj);
+    if (c->fund_scratch) (void)hipFree(c->fund_scratch);
     if (c->ba_pinned) (void)hipHostFree(c->ba_pinned);
     delete c;
     return MOCAP_OK;
@@ -1436,6 +1439,50 @@ int mocap_ba_residuals(mocap_ctx_t c, const double* params_host, int B, const do
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream)); // the one wait of an evaluation: the kernel has written the pinned block
     memcpy(residuals_host, a.res, sizeof(float) * (size_t)B * N);
     memcpy(counts_host, a.counts, sizeof(int32_t) * B);
+    return MOCAP_OK;
+}
+
+int mocap_fundamental_ransac(mocap_ctx_t c, int n_pairs, const double* pts_a, const double* pts_b, const int32_t* pair_offset_host,
+                             const int32_t* samples, int H, double threshold, int refit, double* F_sample, double* F_refit,
+                             uint8_t* inlier, int32_t* status, int32_t* counts, void* stream)
+{
+    if (!c || !pts_a || !pts_b || !pair_offset_host || !samples || !F_sample || !inlier || !status || (refit && !F_refit))
+        return fail(MOCAP_E_INVALID, "null argument");
+    if (n_pairs < 1 || H < 1 || (long long)n_pairs * H > (1LL << 26)) return fail(MOCAP_E_INVALID, "n_pairs=%d H=%d", n_pairs, H);
+    if (n_pairs > 65535) return fail(MOCAP_E_INVALID, "n_pairs=%d: at most 65535 pairs per call", n_pairs);
+    if (!(threshold > 0.0) || !(threshold * threshold <= 1.7976931348623157e308)) return fail(MOCAP_E_INVALID, "threshold %g is not a positive finite number", threshold);
+    if (pair_offset_host[0] < 0) return fail(MOCAP_E_INVALID, "pair_offset[0] = %d", pair_offset_host[0]);
+    int max_n = 0;
+    for (int p = 0; p < n_pairs; p++) {
+        const long long n = (long long)pair_offset_host[p + 1] - pair_offset_host[p];
+        if (n < 8) return fail(MOCAP_E_INVALID, "pair %d: offsets %d .. %d leave %lld points, 8 are needed", p, pair_offset_host[p], pair_offset_host[p + 1], n);
+        if (n > (1 << 26)) return fail(MOCAP_E_INVALID, "pair %d: %lld points, at most 2^26 per pair", p, n);
+        if (n > max_n) max_n = (int)n;
+    }
+    if (set_device(c)) return MOCAP_E_HIP;
+    std::lock_guard<std::mutex> lk(c->mu);
+    // scratch: F_all [n_pairs][H][9] doubles | counts [n_pairs][H] | pair_err [n_pairs] | offset [n_pairs + 1]
+    const size_t nh = (size_t)n_pairs * H, f_bytes = sizeof(double) * 9 * nh, cnt_bytes = (sizeof(int32_t) * nh + 15) & ~(size_t)15;
+    const size_t err_bytes = (sizeof(int32_t) * n_pairs + 15) & ~(size_t)15, off_bytes = sizeof(int32_t) * ((size_t)n_pairs + 1);
+    const size_t need = f_bytes + cnt_bytes + err_bytes + off_bytes;
+    if (need > c->fund_scratch_bytes) {
+        if (c->fund_scratch) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(c->fund_scratch)); c->fund_scratch = nullptr; c->fund_scratch_bytes = 0; }
+        HIP_TRY(hipMalloc(&c->fund_scratch, need * 2));
+        c->fund_scratch_bytes = need * 2;
+    }
+    char* const base = (char*)c->fund_scratch;
+    int32_t* const cnt_own = (int32_t*)(base + f_bytes);
+    int32_t* const pair_err = (int32_t*)(base + f_bytes + cnt_bytes);
+    int32_t* const offset_dev = (int32_t*)(base + f_bytes + cnt_bytes + err_bytes);
+    hipStream_t s = (hipStream_t)stream;
+    // pageable host memory: the copy has left the caller's array when this returns
+    HIP_TRY(hipMemcpyAsync(offset_dev, pair_offset_host, off_bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(cnt_own, 0, cnt_bytes + err_bytes, s));
+    if (counts) HIP_TRY(hipMemsetAsync(counts, 0, sizeof(int32_t) * nh, s));
+    FundArgs a{pts_a, pts_b, offset_dev, samples, n_pairs, H, max_n, threshold * threshold, (double*)base, counts ? counts : cnt_own,
+               pair_err, F_sample, refit ? F_refit : nullptr, inlier, status};
+    launch_fundamental_ransac(a, s);
+    HIP_TRY(hipGetLastError());
     return MOCAP_OK;
 }
 

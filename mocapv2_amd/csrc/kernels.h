@@ -310,7 +310,27 @@ struct BaArgs {
     int32_t* counts;           // [B]
 };
 
+// fundamental matrices of n_pairs camera pairs by RANSAC over host-drawn samples (fundamental.hip)
+struct FundArgs {
+    const double* pts_a;       // [total][2] first camera's points, the pairs' lists one after another
+    const double* pts_b;       // [total][2] the same markers in the second camera
+    const int32_t* offset;     // [n_pairs + 1] device copy: pair p owns points offset[p] .. offset[p + 1] - 1
+    const int32_t* samples;    // [n_pairs][H][8] point indices local to the pair
+    int n_pairs, H, max_n;     // max_n: points of the largest pair (sizes the grids)
+    double thr2;               // threshold squared
+    double* F_all;             // scratch [n_pairs][H][9] every hypothesis' unit-norm matrix (all NaN = invalid)
+    int32_t* counts;           // [n_pairs][H] zeroed before the launch: inliers of every hypothesis
+    int32_t* pair_err;         // scratch [n_pairs] zeroed before the launch: nonzero = a sample index outside the pair
+    double* F_sample;          // [n_pairs][9]
+    double* F_refit;           // [n_pairs][9] or null: no refit
+    uint8_t* inlier;           // [total]
+    int32_t* status;           // [n_pairs][2] (winner, inliers) or (FUND_ERR_*, 0)
+};
+
 enum { CORR_ERR_GROUPS = -2, CORR_ERR_TRUNCATED = -3, CORR_ERR_BLOB = -4 };
+enum { FUND_ERR_SAMPLE = -2, FUND_ERR_DEGENERATE = -3 };
+
+void launch_fundamental_ransac(const FundArgs& a, hipStream_t s);
 
 void launch_correspond(const CorrArgs& a, hipStream_t s);
 size_t correspond_smem_bytes(int P, int C);

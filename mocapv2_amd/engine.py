@@ -324,6 +324,61 @@ class MocapContext:
                                                   _ptr(mse), _ptr(ok), _stream()))
         return mse.cpu().numpy(), ok.cpu().numpy()
 
+    def fundamental_ransac(self, pairs, samples, threshold, refit=True, with_counts=False):
+        """Fundamental matrices of a batch of camera pairs by RANSAC (mocap_fundamental_ransac; reference
+        CalculateCameraPoses.py:189 per pair): one upload, ONE call, one sync.
+        pairs: list of (a [N_p, 2], b [N_p, 2]) host arrays, the same markers in the first and the second camera (N_p >= 8);
+        samples: int32 [n_pairs, H, 8] (or a list of [H, 8] tables, e.g. calibrate.sample_table): 8 distinct point indices per
+        hypothesis, local to the pair.  Returns one dict per pair: F_sample, F_refit (3x3, unit Frobenius norm, x_b^T F x_a =
+        0; F_refit None without refit), mask (uint8 [N_p]: inliers of the best sample), best (its index), n_inliers, and counts
+        (int32 [H]) with with_counts.  A failed pair has best < 0 (MOCAP_FUND_E_*), no matrices and an all-zero mask."""
+        n_pairs = len(pairs)
+        if n_pairs < 1:
+            raise ValueError("no pairs")
+        lists_a, lists_b, offset = [], [], [0]
+        for p, (a, b) in enumerate(pairs):
+            a = np.ascontiguousarray(a, np.float64)
+            b = np.ascontiguousarray(b, np.float64)
+            if a.ndim != 2 or a.shape[1] != 2 or a.shape != b.shape:
+                raise ValueError(f"pair {p}: point lists must both be [N][2], got {a.shape} and {b.shape}")
+            lists_a.append(a)
+            lists_b.append(b)
+            offset.append(offset[-1] + len(a))
+        smp = np.ascontiguousarray(np.stack([np.asarray(s) for s in samples]) if isinstance(samples, (list, tuple)) else samples,
+                                   np.int32)
+        if smp.ndim != 3 or smp.shape[0] != n_pairs or smp.shape[2] != 8:
+            raise ValueError(f"samples must be [n_pairs = {n_pairs}][H][8], got {smp.shape}")
+        H = smp.shape[1]
+        offset = np.array(offset, np.int32)
+        total = int(offset[-1])
+        dev = self.device
+        d_a = torch.from_numpy(np.concatenate(lists_a)).to(dev)
+        d_b = torch.from_numpy(np.concatenate(lists_b)).to(dev)
+        d_s = torch.from_numpy(smp).to(dev)
+        F_s = torch.full((n_pairs, 9), float("nan"), dtype=torch.float64, device=dev)
+        F_r = torch.full((n_pairs, 9), float("nan"), dtype=torch.float64, device=dev) if refit else None
+        mask = torch.empty((max(total, 1),), dtype=torch.uint8, device=dev)
+        status = torch.empty((n_pairs, 2), dtype=torch.int32, device=dev)
+        counts = torch.empty((n_pairs, H), dtype=torch.int32, device=dev) if with_counts else None
+        _abi.check(self.lib.mocap_fundamental_ransac(self._h, n_pairs, _ptr(d_a), _ptr(d_b), offset.ctypes.data_as(C.POINTER(C.c_int)),
+                                                     _ptr(d_s), H, float(threshold), int(bool(refit)), _ptr(F_s), _ptr(F_r),
+                                                     _ptr(mask), _ptr(status), _ptr(counts), _stream()))
+        self.sync()
+        F_s, status, mask = F_s.cpu().numpy(), status.cpu().numpy(), mask.cpu().numpy()
+        F_r = F_r.cpu().numpy() if refit else None
+        counts = counts.cpu().numpy() if with_counts else None
+        out = []
+        for p in range(n_pairs):
+            ok = status[p, 0] >= 0
+            r = {"best": int(status[p, 0]), "n_inliers": int(status[p, 1]) if ok else 0,
+                 "F_sample": F_s[p].reshape(3, 3).copy() if ok else None,
+                 "F_refit": F_r[p].reshape(3, 3).copy() if ok and refit else None,
+                 "mask": mask[offset[p]:offset[p + 1]].copy()}
+            if with_counts:
+                r["counts"] = counts[p].copy()
+            out.append(r)
+        return out
+
     def ba_problem(self, pts, valid=None):
         """Bundle-adjustment residuals with the image points resident on the GPU (see BAProblem)."""
         return BAProblem(self, pts, valid)
