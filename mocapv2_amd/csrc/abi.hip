@@ -37,6 +37,38 @@ static int fail(int code, const char* fmt, ...)
         hipError_t e_ = (expr);                                                                               \
         if (e_ != hipSuccess) return fail(MOCAP_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));        \
     } while (0)
+#define TRY(expr) do { if (int rc_ = (expr)) return rc_; } while (0) // for the file's own functions, which return fail()'s code
+
+// The one owner of a block of device memory (Pinned: of page-locked host memory): every allocation and every free of this file happens
+// in here.  `n` is what reserve() was last asked for, in elements, and is set only once the block is ready for use.
+template <class T, bool Pinned = false>
+struct Buf {
+    T* p = nullptr;
+    size_t n = 0;
+    Buf() = default;
+    Buf(Buf&& o) : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
+    Buf& operator=(Buf&& o) { if (this != &o) { release(); p = o.p; n = o.n; o.p = nullptr; o.n = 0; } return *this; }
+    ~Buf() { release(); }
+    operator T*() const { return p; }
+    T* operator->() const { return p; }
+    void release()
+    {
+        if (p) (void)(Pinned ? hipHostFree(p) : hipFree(p));
+        p = nullptr; n = 0;
+    }
+    // Room for `count` elements, zero-filled if asked.  A block that is large enough stays; a smaller one is REPLACED, its contents are
+    // not carried over (every caller fills what it reads).  Batches in flight on other streams may still read the old block, hence
+    // the device-wide wait before it is freed.  Callers that share a context take c->mu around a growth.
+    int reserve(size_t count, bool zero = false)
+    {
+        if (count <= n) return 0;
+        if (p) { HIP_TRY(hipDeviceSynchronize()); release(); }
+        HIP_TRY(Pinned ? hipHostMalloc((void**)&p, sizeof(T) * count) : hipMalloc((void**)&p, sizeof(T) * count));
+        if (zero) HIP_TRY(hipMemset(p, 0, sizeof(T) * count));
+        n = count;
+        return 0;
+    }
+};
 
 struct EvPair { hipEvent_t a, b; };
 // the scan's probe counters (BrightArgs::probe): 128 pairs, each pair in a cache line of its own (PROBE_STRIDE words apart) -- packed
@@ -145,55 +177,58 @@ static Tuning tuning_from_env()
 }
 
 struct mocap_ctx {
-    int device, W, H, n_slots, wpr;
-    int box_grid;             // workgroups of the box kernel: the resident ones (box_filter_blocks_per_cu() per CU)
-    int n_cu;                 // compute units of the device
-    mocap_blob_params prm;
+    int device = 0, W = 0, H = 0, n_slots = 0, wpr = 0;
+    int box_grid = 2048;      // workgroups of the box kernel: the resident ones (box_filter_blocks_per_cu() per CU)
+    int n_cu = 256;           // compute units of the device
+    mocap_blob_params prm{5, 5, 255 * 0.85, 500.0, 0.5};
     Tuning tune;
-    uint32_t* maps;           // [2][n_slots][H][W]: tap positions, then blend weights (general form)
-    uint32_t* map4;           // [n_slots][H][W] (+ 4 words): compact table of the box kernel
-    ushort4* srcbox;          // [n_slots][ceil(H/8)][ceil(W/8)]: source box per 8x8 output cell (box kernel)
-    ushort4* rowbox;          // [n_slots][H][n_strips]: source box per row and strip (staged row pipeline)
-    uint32_t* map_flags;      // [n_slots] device
+    Buf<uint32_t> maps;       // [2][n_slots][H][W]: tap positions, then blend weights (general form)
+    Buf<uint32_t> map4;       // [n_slots][H][W] (+ 4 words): compact table of the box kernel
+    Buf<ushort4> srcbox;      // [n_slots][ceil(H/8)][ceil(W/8)]: source box per 8x8 output cell (box kernel)
+    Buf<ushort4> rowbox;      // [n_slots][H][n_strips]: source box per row and strip (staged row pipeline)
+    Buf<uint32_t> map_flags;  // [n_slots] device
     std::vector<int> slot_state; // 0 unset, 1 identity, 2 remap
     std::vector<int> slot_compact; // 1 = the slot's displacements fit the compact table (identity: always)
     std::vector<uint32_t> slot_wmax; // largest total blend weight of a source pixel (1024 = identity); 0 = early-out not provable
-    uint2* reach;             // [n_slots][ceil(H/8)][ceil(W/8)] per 8x8 source cell: box of the output pixels that read it
-    uint8_t* cflags;          // [n_slots][cells] border-cut window flags per source cell (see BrightArgs)
-    uint32_t* mask; size_t mask_images;
-    bool mask_dirty;                       // the general kernel wrote the mask whole: clear it before the box path runs again
-    uint32_t* cells; size_t cells_images; // occupancy cells written by the filter kernels for c->mask
-    int last_images;                       // images of the most recent batch that wrote c->cells
-    uint32_t* hotmap;                      // [mask_images][hot_map_words(H, W, 1)] the scan's hot map (BrightArgs::hotmap)
-    uint32_t* tile_rows;                   // [2][mask_images][tiles][4] the scan's box per tile (see BoxArgs): two arrays, alternating
-    int tile_rows_flip;                    //   per batch: the one the scan widens and settle reads / the one settle empties
-    int tile_rows_hold[2];                 //   images whose boxes each of the two may still hold (batches of varying size)
-    uint32_t* cur_box;                     // [mask_images][tiles][4] output region / scan box of the last batch per tile (BoxArgs)
-    BoxItem* items; uint32_t* n_items; uint32_t cap_items; // work list of the box kernel
-    uint4* wide_tiles; uint32_t cap_wide;                  // list of the tiles with wide boxes (filter_mask_kernel, list form)
-    hipStream_t side; hipEvent_t ev_fork, ev_join;         // the wide tiles are filtered beside the box kernel: side stream, fork / join events
+    Buf<uint2> reach;         // [n_slots][ceil(H/8)][ceil(W/8)] per 8x8 source cell: box of the output pixels that read it
+    Buf<uint8_t> cflags;      // [n_slots][cells] border-cut window flags per source cell (see BrightArgs)
+    // The mask group: grown together by ensure_mask to mask_images images, the count stored once all of them stand.
+    Buf<uint32_t> mask; size_t mask_images = 0;
+    bool mask_dirty = false;               // the general kernel wrote the mask whole: clear it before the box path runs again
+    Buf<uint32_t> cells;                   // occupancy cells written by the filter kernels for c->mask
+    int last_images = 0;                   // images of the most recent batch that wrote c->cells
+    Buf<uint32_t> hotmap;                  // [mask_images][hot_map_words(H, W, 1)] the scan's hot map (BrightArgs::hotmap)
+    Buf<uint32_t> tile_rows;               // [2][mask_images][tiles][4] the scan's box per tile (see BoxArgs): two arrays, alternating
+    int tile_rows_flip = 0;                //   per batch: the one the scan widens and settle reads / the one settle empties
+    int tile_rows_hold[2] = {0, 0};        //   images whose boxes each of the two may still hold (batches of varying size)
+    Buf<uint32_t> cur_box;                 // [mask_images][tiles][4] output region / scan box of the last batch per tile (BoxArgs)
+    Buf<BoxItem> items;                    // work list of the box kernel
+    Buf<uint4> wide_tiles;                 // list of the tiles with wide boxes (filter_mask_kernel, list form)
+    Buf<uint32_t> n_items;                 // item count + the 8 head words of the box kernel's runs (not part of the group: fixed size)
+    hipStream_t side = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr; // the wide tiles are filtered beside the box kernel: side stream, fork / join events
     // excess base of the scan, adapted between batches: two candidates (tight / tolerant of bright backgrounds), the current
     // one, and a probe now and then that counts the hot cells both would leave (BrightArgs::probe)
-    int base_sel; int probe_age; bool probe_pending; uint32_t* probe_dev; uint32_t* probe_host; hipEvent_t probe_ev;
-    bool walk_count_zeroed;                // the filter stage of the current batch has zeroed walk_count (settle_tiles_kernel)
-    int probe_images;                      // images the pending probe counted on (every 16th of its batch)
-    bool hot_dense;                        // the last probe found a crowded scene (many hot cells per image): the scan leaves a hot map
-    uint32_t* cells_ext; uint32_t* cur_box_ext; size_t cells_ext_images; // the same for caller-owned masks (mocap_filter_mask)
+    int base_sel = 1; int probe_age = 0; bool probe_pending = false; Buf<uint32_t> probe_dev; Buf<uint32_t, true> probe_host; hipEvent_t probe_ev = nullptr;
+    bool walk_count_zeroed = false;        // the filter stage of the current batch has zeroed walk_count (settle_tiles_kernel)
+    int probe_images = 0;                  // images the pending probe counted on (every 16th of its batch)
+    bool hot_dense = false;                // the last probe found a crowded scene (many hot cells per image): the scan leaves a hot map
+    Buf<uint32_t> cells_ext, cur_box_ext; size_t cells_ext_images = 0; // the external group: the same for caller-owned masks (mocap_filter_mask)
     // the caller's row-major masks pass through masks of the internal layout (kernels.h: mask_word_index), converted at the boundary:
-    uint32_t* mask_out; size_t mask_out_images; // mocap_filter_mask filters into this one (a caller-owned mask for run_filter)
-    uint32_t* mask_in; size_t mask_in_images;   // mocap_contours_from_mask reads the caller's mask from this one
-    uint8_t* gray_scratch; size_t gray_scratch_bytes; // mocap_blob_centroids_bayer without a gray buffer, where the gray-less path
-                                                      //   cannot run: the gray frames go here (grown to the largest batch)
-    void* cwork; size_t cwork_images;      // contour kernel workspace, contour_work_bytes() per image
-    uint64_t* walk_list; uint64_t* link_list; uint32_t* walk_count; // contour stage, split form: the batch's border walks / link walks
-                                                                    //   (grown with cwork) and their counters
-    CameraTable* cams; int n_cam, n_F;
-    double* scratch; size_t scratch_elems;
-    double* ba_obj; size_t ba_obj_elems;   // object points of mocap_ba_residuals, [B][N][3]
-    void* fund_scratch; size_t fund_scratch_bytes; // mocap_fundamental_ransac: every hypothesis' matrix, the counters, the pair offsets
-    void* ba_pinned; size_t ba_pinned_bytes; // its host-side hand-over: parameters in, residuals + counts out (the kernel reads / writes it directly)
+    Buf<uint32_t> mask_out;                // mocap_filter_mask filters into this one (a caller-owned mask for run_filter)
+    Buf<uint32_t> mask_in;                 // mocap_contours_from_mask reads the caller's mask from this one
+    Buf<uint8_t> gray_scratch;             // mocap_blob_centroids_bayer without a gray buffer, where the gray-less path
+                                           //   cannot run: the gray frames go here (grown to the largest batch)
+    // The contour group: grown together by run_contours to cwork_images images.
+    Buf<uint8_t> cwork; size_t cwork_images = 0; // contour kernel workspace, contour_work_bytes() per image
+    Buf<uint64_t> walk_list, link_list;    // contour stage, split form: the batch's border walks / link walks
+    Buf<uint32_t> walk_count;              //   their counters (fixed size, allocated with the group's first growth)
+    Buf<CameraTable> cams; int n_cam = 0, n_F = 0;
+    Buf<double> scratch;                   // error scratch of mocap_correspond
+    Buf<double> ba_obj;                    // object points of mocap_ba_residuals, [B][N][3]
+    Buf<char> fund_scratch;                // mocap_fundamental_ransac: every hypothesis' matrix, the counters, the pair offsets
+    Buf<char, true> ba_pinned;             // mocap_ba_residuals' host-side hand-over: parameters in, residuals + counts out (the kernel reads / writes it directly)
     std::shared_ptr<struct SharedComm> comm; // RCCL communicator of mocap_comm_init / mocap_comm_share, else null
-    bool profiling;
+    bool profiling = false;
     std::vector<EvPair> ev[5];
     std::mutex mu;
 };
@@ -219,6 +254,10 @@ static Tiling tiling(const mocap_ctx* c)
 
 static size_t source_cells(const mocap_ctx* c) { return (size_t)((c->H + 7) / 8) * ((c->W + 7) / 8); }
 static size_t cells_per_image(const mocap_ctx* c) { Tiling t = tiling(c); return (size_t)t.n_cgroups * 4 * t.n_strips; }
+// a slot's part of the undistort tables (null before the first mocap_set_undistort): tap positions, blend weights, compact table
+static uint32_t* slot_map(const mocap_ctx* c, int slot) { return c->maps ? c->maps + (size_t)slot * c->H * c->W : nullptr; }
+static uint32_t* slot_mapw(const mocap_ctx* c, int slot) { return c->maps ? c->maps + (size_t)(c->n_slots + slot) * c->H * c->W : nullptr; }
+static uint32_t* slot_map4(const mocap_ctx* c, int slot) { return c->map4 ? c->map4 + (size_t)slot * c->H * c->W : nullptr; }
 
 // ---- RCCL, bound at run time -----------------------------------------------------------------------------------
 // The path's one exchange is an ncclAllGather of centroid records.  librccl is looked up with dlopen
@@ -276,25 +315,12 @@ int mocap_ctx_create(int device_id, int width, int height, int n_slots, mocap_ct
     HIP_TRY(hipGetDeviceCount(&ndev));
     if (device_id < 0 || device_id >= ndev) return fail(MOCAP_E_HIP, "mocap_ctx_create: no HIP device %d (%d visible)", device_id, ndev);
     HIP_TRY(hipSetDevice(device_id));
-    mocap_ctx* c = new mocap_ctx();
+    std::unique_ptr<mocap_ctx, int (*)(mocap_ctx*)> c(new mocap_ctx(), mocap_ctx_destroy); // (destroyed by every early return)
     c->device = device_id; c->W = width; c->H = height; c->n_slots = n_slots; c->wpr = (width + 31) / 32;
-    c->prm = mocap_blob_params{5, 5, 255 * 0.85, 500.0, 0.5};
-    c->maps = nullptr; c->map4 = nullptr; c->srcbox = nullptr; c->rowbox = nullptr; c->reach = nullptr; c->cflags = nullptr; c->map_flags = nullptr;
-    c->mask = nullptr; c->mask_images = 0; c->mask_dirty = false; c->cells = nullptr; c->cells_images = 0; c->last_images = 0;
-    c->hotmap = nullptr; c->tile_rows = nullptr; c->tile_rows_flip = 0; c->tile_rows_hold[0] = c->tile_rows_hold[1] = 0; c->cur_box = nullptr; c->items = nullptr; c->n_items = nullptr; c->cap_items = 0; c->wide_tiles = nullptr; c->cap_wide = 0;
-    c->cells_ext = nullptr; c->cur_box_ext = nullptr; c->cells_ext_images = 0;
-    c->gray_scratch = nullptr; c->gray_scratch_bytes = 0;
-    c->mask_out = nullptr; c->mask_out_images = 0; c->mask_in = nullptr; c->mask_in_images = 0; c->cwork = nullptr; c->cwork_images = 0; c->walk_list = nullptr; c->link_list = nullptr; c->walk_count = nullptr;
-    c->cams = nullptr; c->n_cam = 0; c->n_F = 0; c->scratch = nullptr; c->scratch_elems = 0; c->profiling = false;
-    c->ba_obj = nullptr; c->ba_obj_elems = 0; c->ba_pinned = nullptr; c->ba_pinned_bytes = 0;
-    c->fund_scratch = nullptr; c->fund_scratch_bytes = 0;
-    c->comm.reset();
-    c->side = nullptr; c->ev_fork = nullptr; c->ev_join = nullptr;
     c->tune = tuning_from_env();
-    c->base_sel = c->tune.base_sel; c->probe_age = 0; c->probe_pending = false; c->probe_images = 0; c->hot_dense = false; c->probe_dev = nullptr; c->probe_host = nullptr; c->probe_ev = nullptr;
+    c->base_sel = c->tune.base_sel;
     {
         hipDeviceProp_t prop;
-        c->box_grid = 2048; c->n_cu = 256;
         if (hipGetDeviceProperties(&prop, device_id) == hipSuccess && prop.multiProcessorCount > 0) {
             c->box_grid = box_filter_blocks_per_cu() * prop.multiProcessorCount;
             c->n_cu = prop.multiProcessorCount;
@@ -304,24 +330,17 @@ int mocap_ctx_create(int device_id, int width, int height, int n_slots, mocap_ct
     c->slot_state.assign(n_slots, 0);
     c->slot_compact.assign(n_slots, 0);
     c->slot_wmax.assign(n_slots, 0);
-    hipError_t e = hipMalloc(&c->map_flags, sizeof(uint32_t) * n_slots + 256);
-    if (e == hipSuccess) e = hipMemset(c->map_flags, 0, sizeof(uint32_t) * n_slots + 256);
-    if (e == hipSuccess) e = hipMalloc(&c->n_items, 1024); // item count + the 8 head words of the box kernel's runs
-    if (e == hipSuccess) e = hipMemset(c->n_items, 0, 1024);
-    if (e == hipSuccess) e = hipMalloc(&c->probe_dev, PROBE_BYTES);
-    if (e == hipSuccess) e = hipHostMalloc(&c->probe_host, PROBE_BYTES);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->probe_ev, hipEventDisableTiming);
+    TRY(c->map_flags.reserve(n_slots + 64, true));
+    TRY(c->n_items.reserve(256, true)); // item count + the 8 head words of the box kernel's runs
+    TRY(c->probe_dev.reserve(PROBE_BYTES / sizeof(uint32_t)));
+    TRY(c->probe_host.reserve(PROBE_BYTES / sizeof(uint32_t)));
+    HIP_TRY(hipEventCreateWithFlags(&c->probe_ev, hipEventDisableTiming));
     // (the side stream of wide_fork is created on first use: every stream a process holds is dealt onto one of a few hardware
     // queues, and a stream nobody uses can end up sharing a queue with a batch's own stream)
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipMalloc(&c->cams, sizeof(CameraTable));
-    if (e == hipSuccess) e = hipMemset(c->cams, 0, sizeof(CameraTable));
-    if (e != hipSuccess) {
-        mocap_ctx_destroy(c);
-        return fail(MOCAP_E_HIP, "mocap_ctx_create: %s", hipGetErrorString(e));
-    }
-    *out = c;
+    HIP_TRY(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
+    HIP_TRY(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
+    TRY(c->cams.reserve(1, true));
+    *out = c.release();
     return MOCAP_OK;
 }
 
@@ -334,39 +353,9 @@ int mocap_ctx_destroy(mocap_ctx_t c)
     if (c->side) { (void)hipStreamSynchronize(c->side); (void)hipStreamDestroy(c->side); }
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
+    // before probe_host / probe_dev go away: an asynchronous copy into the pinned block may be in flight
     if (c->probe_ev) { (void)hipEventSynchronize(c->probe_ev); (void)hipEventDestroy(c->probe_ev); }
-    if (c->probe_dev) (void)hipFree(c->probe_dev);
-    if (c->probe_host) (void)hipHostFree(c->probe_host);
-    if (c->maps) (void)hipFree(c->maps);
-    if (c->map4) (void)hipFree(c->map4);
-    if (c->srcbox) (void)hipFree(c->srcbox);
-    if (c->rowbox) (void)hipFree(c->rowbox);
-    if (c->cur_box) (void)hipFree(c->cur_box);
-    if (c->cur_box_ext) (void)hipFree(c->cur_box_ext);
-    if (c->items) (void)hipFree(c->items);
-    if (c->wide_tiles) (void)hipFree(c->wide_tiles);
-    if (c->gray_scratch) (void)hipFree(c->gray_scratch);
-    if (c->n_items) (void)hipFree(c->n_items);
-    if (c->reach) (void)hipFree(c->reach);
-    if (c->cflags) (void)hipFree(c->cflags);
-    if (c->cells_ext) (void)hipFree(c->cells_ext);
-    if (c->map_flags) (void)hipFree(c->map_flags);
-    if (c->mask) (void)hipFree(c->mask);
-    if (c->mask_out) (void)hipFree(c->mask_out);
-    if (c->mask_in) (void)hipFree(c->mask_in);
-    if (c->cells) (void)hipFree(c->cells);
-    if (c->tile_rows) (void)hipFree(c->tile_rows);
-    if (c->hotmap) (void)hipFree(c->hotmap);
-    if (c->cwork) (void)hipFree(c->cwork);
-    if (c->walk_list) (void)hipFree(c->walk_list);
-    if (c->link_list) (void)hipFree(c->link_list);
-    if (c->walk_count) (void)hipFree(c->walk_count);
-    if (c->cams) (void)hipFree(c->cams);
-    if (c->scratch) (void)hipFree(c->scratch);
-    if (c->ba_obj) (void)hipFree(c->ba_obj);
-    if (c->fund_scratch) (void)hipFree(c->fund_scratch);
-    if (c->ba_pinned) (void)hipHostFree(c->ba_pinned);
-    delete c;
+    delete c; // releases every buffer
     return MOCAP_OK;
 }
 
@@ -405,19 +394,19 @@ int mocap_set_undistort(mocap_ctx_t c, int slot, const double K[9], const double
     if (set_device(c)) return MOCAP_E_HIP;
     std::lock_guard<std::mutex> lk(c->mu);
     size_t per = (size_t)c->H * c->W;
-    if (!c->maps) HIP_TRY(hipMalloc(&c->maps, sizeof(uint32_t) * per * c->n_slots * 2));
-    if (!c->map4) HIP_TRY(hipMalloc(&c->map4, sizeof(uint32_t) * (per * c->n_slots + 4))); // + 4: a quad load at the last pixel stays inside
+    TRY(c->maps.reserve(per * c->n_slots * 2));
+    TRY(c->map4.reserve(per * c->n_slots + 4)); // + 4: a quad load at the last pixel stays inside
     const int ncx_ = (c->W + 7) / 8, ncy_ = (c->H + 7) / 8;
-    if (!c->srcbox) HIP_TRY(hipMalloc(&c->srcbox, sizeof(ushort4) * (size_t)ncx_ * ncy_ * c->n_slots));
+    TRY(c->srcbox.reserve((size_t)ncx_ * ncy_ * c->n_slots));
     const int n_strips_ = tiling(c).n_strips;
-    if (!c->rowbox) HIP_TRY(hipMalloc(&c->rowbox, sizeof(ushort4) * (size_t)c->H * n_strips_ * c->n_slots));
+    TRY(c->rowbox.reserve((size_t)c->H * n_strips_ * c->n_slots));
     MapArgs m;
     memcpy(m.K, K, sizeof(m.K));
     memcpy(m.dist, dist, sizeof(m.dist));
     m.H = c->H; m.W = c->W;
-    m.map = c->maps + per * slot;
-    m.mapw = c->maps + per * (c->n_slots + slot);
-    m.map4 = c->map4 + per * slot;
+    m.map = slot_map(c, slot);
+    m.mapw = slot_mapw(c, slot);
+    m.map4 = slot_map4(c, slot);
     m.flags = c->map_flags + slot;
     HIP_TRY(hipMemset(m.flags, 0, sizeof(uint32_t)));
     launch_undistort_map(m, 0);
@@ -436,23 +425,19 @@ int mocap_set_undistort(mocap_ctx_t c, int slot, const double K[9], const double
     for (size_t i = 0; i < reach32.size(); i += 2) { reach32[i] = 0x7fffffff; reach32[i + 1] = -0x7fffffff - 1; }
     if (c->slot_state[slot] == 2) {
         // statistics for the dark-tile early-out (see blob_filter.hip): total weight per source pixel, tap extents
-        uint32_t* tmp = nullptr;
+        Buf<uint32_t> tmp; // (released at every return)
         const size_t edge_words = edge.size();
-        HIP_TRY(hipMalloc(&tmp, sizeof(uint32_t) * (per + 4 + edge_words + reach32.size())));
-        hipError_t e2 = hipMemset(tmp, 0, sizeof(uint32_t) * (per + 4 + edge_words));
+        TRY(tmp.reserve(per + 4 + edge_words + reach32.size()));
+        HIP_TRY(hipMemset(tmp, 0, sizeof(uint32_t) * (per + 4 + edge_words)));
         int* reach_dev = (int*)(tmp + per + 4 + edge_words);
-        if (e2 == hipSuccess) e2 = hipMemcpy(reach_dev, reach32.data(), sizeof(int) * reach32.size(), hipMemcpyHostToDevice);
+        HIP_TRY(hipMemcpy(reach_dev, reach32.data(), sizeof(int) * reach32.size(), hipMemcpyHostToDevice));
         uint32_t st3[3] = {0, 0, 0};
-        if (e2 == hipSuccess) {
-            StatArgs sg{m.map, m.mapw, tmp, tmp + per, c->H, c->W, tmp + per + 4, reach_dev};
-            launch_remap_stats(sg, 0);
-            e2 = hipGetLastError();
-            if (e2 == hipSuccess) e2 = hipMemcpy(st3, tmp + per, sizeof(st3), hipMemcpyDeviceToHost);
-            if (e2 == hipSuccess) e2 = hipMemcpy(edge.data(), tmp + per + 4, sizeof(uint32_t) * edge.size(), hipMemcpyDeviceToHost);
-            if (e2 == hipSuccess) e2 = hipMemcpy(reach32.data(), reach_dev, sizeof(int) * reach32.size(), hipMemcpyDeviceToHost);
-        }
-        (void)hipFree(tmp);
-        if (e2 != hipSuccess) return fail(MOCAP_E_HIP, "undistort statistics: %s", hipGetErrorString(e2));
+        StatArgs sg{m.map, m.mapw, tmp, tmp + per, c->H, c->W, tmp + per + 4, reach_dev};
+        launch_remap_stats(sg, 0);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpy(st3, tmp + per, sizeof(st3), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(edge.data(), tmp + per + 4, sizeof(uint32_t) * edge.size(), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(reach32.data(), reach_dev, sizeof(int) * reach32.size(), hipMemcpyDeviceToHost));
         if (st3[1] <= 9 && st3[2] <= 9 && c->W >= 8) c->slot_wmax[slot] = st3[0];
     }
     {   // Dark-tile early-out tables per 8x8 source cell: the reach (which output pixels read the cell: from the map itself
@@ -476,9 +461,9 @@ int mocap_set_undistort(mocap_ctx_t c, int slot, const double K[9], const double
                 else reach[i] = make_uint2((uint32_t)x0 | ((uint32_t)x1 << 16), (uint32_t)y0 | ((uint32_t)y1 << 16));
                 cflags[i] = (edge[i] & 2u) ? 2 : (edge[i] & 1u) ? 1 : 0;
             }
-        if (!c->reach) HIP_TRY(hipMalloc(&c->reach, sizeof(uint2) * reach.size() * c->n_slots));
+        TRY(c->reach.reserve(reach.size() * c->n_slots));
         HIP_TRY(hipMemcpy(c->reach + reach.size() * slot, reach.data(), sizeof(uint2) * reach.size(), hipMemcpyHostToDevice));
-        if (!c->cflags) HIP_TRY(hipMalloc(&c->cflags, cflags.size() * c->n_slots));
+        TRY(c->cflags.reserve(cflags.size() * c->n_slots));
         HIP_TRY(hipMemcpy(c->cflags + cflags.size() * slot, cflags.data(), cflags.size(), hipMemcpyHostToDevice));
     }
     if (identity_out) *identity_out = c->slot_state[slot] == 1;
@@ -618,269 +603,339 @@ static int excess_base(int thr_mul, int sel)
 
 static int ensure_gray_scratch(mocap_ctx* c, size_t bytes)
 {
-    if (bytes <= c->gray_scratch_bytes) return 0;
+    if (bytes <= c->gray_scratch.n) return 0;
     std::lock_guard<std::mutex> lk(c->mu);
-    if (bytes <= c->gray_scratch_bytes) return 0;
-    if (c->gray_scratch) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(c->gray_scratch)); c->gray_scratch = nullptr; c->gray_scratch_bytes = 0; }
-    HIP_TRY(hipMalloc(&c->gray_scratch, bytes));
-    c->gray_scratch_bytes = bytes;
-    return 0;
+    return c->gray_scratch.reserve(bytes);
 }
 
-// bayer != nullptr: `frames` (= bayer->dst) does not exist yet -- the Bayer -> gray pass that writes it runs first, fused
+// floor(thresh) + 1: blurred > thresh  <=>  S >= thr_mul * taps
+static int threshold_mul(const mocap_ctx* c)
+{
+    const double ft = floor(c->prm.thresh);
+    return ft < -1.0 ? 0 : (ft > 255.0 ? 256 : (int)ft + 1);
+}
+
+// The row pipeline's arguments for a batch on the undistort slots from slot_base on (slot_base < 0: no tables): every member defined;
+// geometry, tiling, the first slot's tables.  The callers add what differs (the tile list, the staged form, test switches).
+static FilterArgs filter_args(const mocap_ctx* c, const void* src, size_t image_stride, int pitch, uint32_t* mask, uint32_t* cells,
+                              int slot_base, int cam_mod, int n_images, int thr_mul)
+{
+    const Tiling tl = tiling(c);
+    FilterArgs a{};
+    a.src = (const uint8_t*)src; a.image_stride = image_stride; a.pitch = pitch; a.H = c->H; a.W = c->W;
+    a.mask = mask; a.words_per_row = c->wpr; a.cam_mod = cam_mod; a.cells = cells;
+    a.n_images = n_images; a.n_steps = (n_images + cam_mod - 1) / cam_mod;
+    a.thr_mul = thr_mul;
+    a.n_strips = tl.n_strips; a.rows_per_chunk = tl.rows; a.n_cgroups = tl.n_cgroups;
+    a.pipelined = c->W >= 4 && (c->W & 3) == 0 && c->H >= 2;
+    if (slot_base >= 0) {
+        a.map = slot_map(c, slot_base); a.mapw = slot_mapw(c, slot_base); a.map4 = slot_map4(c, slot_base);
+        a.rowbox = c->rowbox ? c->rowbox + (size_t)slot_base * c->H * tl.n_strips : nullptr;
+    }
+    return a;
+}
+
+// ---- run_filter and its steps, in the order they run ------------------------------------------------------------
+// one call's batch, as the steps hand it on
+struct Batch {
+    int n_images, cam_mod, slot_base;
+    size_t image_stride; int pitch;
+    uint32_t* mask; uint32_t* cells;
+    bool own_mask;       // the context's mask keeps "zero outside the recorded regions" from batch to batch
+    hipStream_t s;
+};
+
+// the last probe's counts have arrived: which excess base the next scans use (base_sel), who marks the tiles (hot_dense)
+static void read_probe(mocap_ctx* c, int thr_mul)
+{
+    if (!c->probe_pending || hipEventQuery(c->probe_ev) != hipSuccess) return;
+    unsigned long long n_cur = 0, n_alt = 0;
+    for (int i = 0; i < 128; i++) { n_cur += c->probe_host[PROBE_STRIDE * i]; n_alt += c->probe_host[PROBE_STRIDE * i + 1]; }
+    if (c->tune.probe_debug) fprintf(stderr, "[probe] base %d: %llu hot cells, alternative %d: %llu\n", excess_base(thr_mul, c->base_sel), n_cur, excess_base(thr_mul, c->base_sel ^ 1), n_alt);
+    // The tight base (sel 0) leaves tighter boxes around the markers for the same number of hot cells (measured: 33k against
+    // 45k marked tiles per 3072 images of the benchmark scene), so it is preferred unless the background makes its hot cells
+    // explode: use it iff it leaves at most 1.25x the hot cells of the tolerant base.
+    const unsigned long long n_lo = c->base_sel == 0 ? n_cur : n_alt, n_hi = c->base_sel == 0 ? n_alt : n_cur;
+    c->base_sel = (n_lo * 4 <= n_hi * 5) ? 0 : 1;
+    // Who marks the tiles (scan_hotmap = 1: whichever is cheaper).  A hot cell costs the scan two dependent round trips behind
+    // its loads; the hot map moves them into mark_tiles_kernel, which costs ~0.04 ms per 3072 images whatever the scene holds.
+    // Measured (profiles/history/r4_run7_scan_wide_serial.log): scan + mark + settle 1.03 against 1.00 ms at 8 markers per frame
+    // (~190 hot cells per image), 1.07 against 1.21 at 32 (~750): the map pays above a few hundred hot cells per image.
+    const unsigned long long n_now = c->base_sel == 0 ? n_lo : n_hi;
+    c->hot_dense = c->probe_images > 0 && n_now > 400ull * (unsigned long long)c->probe_images;
+    c->probe_pending = false;
+}
+
+// dark-tile early-out: largest doubled excess sum 2E (E = sum of max(0, p - base)) per 16x16 block that still proves an
+// all-zero mask:   2E * Wmax < 1024 * taps_min * (2 * thr_mul - 2 * base - 1)     (derivation: blob_filter.hip)
+struct ScanBounds {
+    int thr_mul;
+    int fixed_base;      // >= 0: the pinned base (excess_base switch)
+    int base, base_alt;  // the excess base in use / the one a probe counts beside it
+    int allow, allow_cut1, allow_cut2, allow_alt; // -1 = no early-out
+};
+static ScanBounds scan_bounds(const mocap_ctx* c, int slot_base, int cam_mod, int thr_mul)
+{
+    ScanBounds b{thr_mul, c->tune.excess_base, 0, 0, -1, -1, -1, -1};
+    if (b.fixed_base >= 0) { if (b.fixed_base > thr_mul - 1) b.fixed_base = thr_mul - 1; if (b.fixed_base > 254) b.fixed_base = 254; if (b.fixed_base < 0) b.fixed_base = 0; }
+    b.base = b.fixed_base >= 0 ? b.fixed_base : excess_base(thr_mul, c->base_sel);
+    b.base_alt = excess_base(thr_mul, c->base_sel ^ 1);
+    long long wmax = 0;
+    bool ok = true;
+    for (int sl = slot_base; sl < slot_base + cam_mod; sl++) {
+        if (c->slot_wmax[sl] == 0) ok = false;
+        wmax = c->slot_wmax[sl] > wmax ? c->slot_wmax[sl] : wmax;
+    }
+    auto t5 = [](int n) { return (n - 1 < 2 ? n - 1 : 2) + 1; }; // taps of a window at the border, per axis
+    auto t5full = [](int n) { return n < 5 ? n : 5; };
+    const long long per_tap = 1024LL * (2LL * thr_mul - 2LL * b.base - 1), per_tap_alt = 1024LL * (2LL * thr_mul - 2LL * b.base_alt - 1);
+    if (!c->tile_rows || !c->reach || !c->cflags) ok = false;
+    if (ok && wmax > 0 && per_tap > 0) {
+        b.allow = (int)((per_tap * t5full(c->W) * t5full(c->H) - 1) / wmax); // windows with all their taps
+        const long long taps1 = t5(c->W) * t5full(c->H) < t5full(c->W) * t5(c->H) ? t5(c->W) * t5full(c->H) : t5full(c->W) * t5(c->H);
+        b.allow_cut1 = (int)((per_tap * taps1 - 1) / wmax);                  // smallest window cut in one axis
+        b.allow_cut2 = (int)((per_tap * t5(c->W) * t5(c->H) - 1) / wmax);    // smallest window cut in both
+        if (per_tap_alt > 0) b.allow_alt = (int)((per_tap_alt * t5full(c->W) * t5full(c->H) - 1) / wmax);
+    }
+    if (!c->tune.skip_dark) b.allow = -1;
+    return b;
+}
+
+// Which kernels serve the batch.
+// bayer != nullptr: the frames (= bayer->dst) do not exist yet -- the Bayer -> gray pass that writes them runs first, fused
 // with the streaming scan where the geometry allows (it has the gray bytes in registers anyway).
 // bayer->dst == nullptr (no gray buffer): the gray-less path where it can run -- the fused scan without its write-back, every
 // marked tile as items of the box kernel's Bayer form, which forms the gray values it reads from the Bayer frames (no wide tiles:
 // the row pipeline has no Bayer form) --, else the gray frames go to the context's scratch buffer and the path above runs.
-static int run_filter(mocap_ctx* c, const void* frames, int n_images, int cam_mod, int slot_base, size_t image_stride,
-                      int pitch, uint32_t* mask, uint32_t* cells, hipStream_t s, const BayerArgs* bayer = nullptr)
+struct FilterPath {
+    bool remap;          // a slot of the batch is remapped
+    bool compact;        // the sparse path: scan, settle, box kernel (+ wide tiles); else the dense kernel
+    bool rows_staged;    // the row pipeline's staged form (compact table, source pixels through LDS): dense path and wide tiles alike
+    bool direct;         // the gray-less path
+    bool bayer;          // a Bayer -> gray pass belongs to the batch: `bl`
+    uint64_t remap_bits;
+    int rows_dw;
+    const void* frames;  // what the filter kernels read: gray frames (the caller's, or the scratch buffer), or the Bayer frames (direct)
+    BayerArgs bl;
+};
+static int choose_path(mocap_ctx* c, const Batch& bt, const void* frames, const BayerArgs* bayer, int allow, FilterPath& p)
 {
-    c->walk_count_zeroed = false;
-    double ft = floor(c->prm.thresh);
-    const int thr_mul = ft < -1.0 ? 0 : (ft > 255.0 ? 256 : (int)ft + 1);
-    Tiling tl = tiling(c);
-    const bool own_mask = mask == c->mask; // the context's mask keeps "zero outside the recorded regions" from batch to batch
-    bool remap = false, compact = c->W >= 8 && cam_mod <= 64;
-    uint64_t remap_bits = 0;
-    for (int sl = slot_base; sl < slot_base + cam_mod; sl++) {
-        if (c->slot_state[sl] == 2) { remap = true; if (sl - slot_base < 64) remap_bits |= 1ull << (sl - slot_base); }
-        if (c->slot_state[sl] == 2 && !c->slot_compact[sl]) compact = false;
+    p = FilterPath{};
+    p.compact = c->W >= 8 && bt.cam_mod <= 64;
+    for (int sl = bt.slot_base; sl < bt.slot_base + bt.cam_mod; sl++) {
+        if (c->slot_state[sl] == 2) { p.remap = true; if (sl - bt.slot_base < 64) p.remap_bits |= 1ull << (sl - bt.slot_base); }
+        if (c->slot_state[sl] == 2 && !c->slot_compact[sl]) p.compact = false;
     }
-    if (c->tune.general_filter) compact = false; // test switch: the general kernel
-    // the row pipeline's staged form (compact table, source pixels through LDS) serves the dense path and the wide tiles alike
-    bool rows_staged = remap && c->tune.rows_staged && c->map4 && c->rowbox && (c->W & 15) == 0 && c->H >= 2; // (16-byte staging units)
-    for (int sl = slot_base; sl < slot_base + cam_mod; sl++)
-        if (!c->slot_compact[sl]) rows_staged = false;
-    const int rows_dw = c->tune.rows_stage_dw < 0 || c->tune.rows_stage_dw > rows_stage_dwords() ? rows_stage_dwords() : c->tune.rows_stage_dw;
-    if (cells == c->cells) c->last_images = n_images;
-    EvPair p; bool on;
-    // dark-tile early-out: largest doubled excess sum 2E (E = sum of max(0, p - base)) per 16x16 block that still proves an
-    // all-zero mask:   2E * Wmax < 1024 * taps_min * (2 * thr_mul - 2 * base - 1)     (derivation: blob_filter.hip)
-    int fixed_base = c->tune.excess_base;
-    if (fixed_base >= 0) { if (fixed_base > thr_mul - 1) fixed_base = thr_mul - 1; if (fixed_base > 254) fixed_base = 254; if (fixed_base < 0) fixed_base = 0; }
-    if (c->probe_pending && hipEventQuery(c->probe_ev) == hipSuccess) { // the last probe's counts have arrived
-        unsigned long long n_cur = 0, n_alt = 0;
-        for (int i = 0; i < 128; i++) { n_cur += c->probe_host[PROBE_STRIDE * i]; n_alt += c->probe_host[PROBE_STRIDE * i + 1]; }
-        if (c->tune.probe_debug) fprintf(stderr, "[probe] base %d: %llu hot cells, alternative %d: %llu\n", excess_base(thr_mul, c->base_sel), n_cur, excess_base(thr_mul, c->base_sel ^ 1), n_alt);
-        // The tight base (sel 0) leaves tighter boxes around the markers for the same number of hot cells (measured: 33k against
-        // 45k marked tiles per 3072 images of the benchmark scene), so it is preferred unless the background makes its hot cells
-        // explode: use it iff it leaves at most 1.25x the hot cells of the tolerant base.
-        const unsigned long long n_lo = c->base_sel == 0 ? n_cur : n_alt, n_hi = c->base_sel == 0 ? n_alt : n_cur;
-        c->base_sel = (n_lo * 4 <= n_hi * 5) ? 0 : 1;
-        // Who marks the tiles (scan_hotmap = 1: whichever is cheaper).  A hot cell costs the scan two dependent round trips behind
-        // its loads; the hot map moves them into mark_tiles_kernel, which costs ~0.04 ms per 3072 images whatever the scene holds.
-        // Measured (profiles/history/r4_run7_scan_wide_serial.log): scan + mark + settle 1.03 against 1.00 ms at 8 markers per frame
-        // (~190 hot cells per image), 1.07 against 1.21 at 32 (~750): the map pays above a few hundred hot cells per image.
-        const unsigned long long n_now = c->base_sel == 0 ? n_lo : n_hi;
-        c->hot_dense = c->probe_images > 0 && n_now > 400ull * (unsigned long long)c->probe_images;
-        c->probe_pending = false;
-    }
-    const int base = fixed_base >= 0 ? fixed_base : excess_base(thr_mul, c->base_sel);
-    const int base_alt = excess_base(thr_mul, c->base_sel ^ 1);
-    int allow = -1, allow_cut1 = -1, allow_cut2 = -1, allow_alt = -1;
-    {
-        long long wmax = 0;
-        bool ok = true;
-        for (int sl = slot_base; sl < slot_base + cam_mod; sl++) {
-            if (c->slot_wmax[sl] == 0) ok = false;
-            wmax = c->slot_wmax[sl] > wmax ? c->slot_wmax[sl] : wmax;
-        }
-        auto t5 = [](int n) { return (n - 1 < 2 ? n - 1 : 2) + 1; }; // taps of a window at the border, per axis
-        auto t5full = [](int n) { return n < 5 ? n : 5; };
-        const long long per_tap = 1024LL * (2LL * thr_mul - 2LL * base - 1), per_tap_alt = 1024LL * (2LL * thr_mul - 2LL * base_alt - 1);
-        if (!c->tile_rows || !c->reach || !c->cflags) ok = false;
-        if (ok && wmax > 0 && per_tap > 0) {
-            allow = (int)((per_tap * t5full(c->W) * t5full(c->H) - 1) / wmax); // windows with all their taps
-            const long long taps1 = t5(c->W) * t5full(c->H) < t5full(c->W) * t5(c->H) ? t5(c->W) * t5full(c->H) : t5full(c->W) * t5(c->H);
-            allow_cut1 = (int)((per_tap * taps1 - 1) / wmax);                  // smallest window cut in one axis
-            allow_cut2 = (int)((per_tap * t5(c->W) * t5(c->H) - 1) / wmax);    // smallest window cut in both
-            if (per_tap_alt > 0) allow_alt = (int)((per_tap_alt * t5full(c->W) * t5full(c->H) - 1) / wmax);
-        }
-        if (!c->tune.skip_dark) allow = -1;
-    }
+    if (c->tune.general_filter) p.compact = false; // test switch: the general kernel
+    p.rows_staged = p.remap && c->tune.rows_staged && c->map4 && c->rowbox && (c->W & 15) == 0 && c->H >= 2; // (16-byte staging units)
+    for (int sl = bt.slot_base; sl < bt.slot_base + bt.cam_mod; sl++)
+        if (!c->slot_compact[sl]) p.rows_staged = false;
+    p.rows_dw = c->tune.rows_stage_dw < 0 || c->tune.rows_stage_dw > rows_stage_dwords() ? rows_stage_dwords() : c->tune.rows_stage_dw;
     // every tile has to be filtered anyway: the dense kernel's sliding row pipeline does that with less work per pixel
     // than the box kernel (MOCAP_DENSE_BOXES=1: the box kernel on whole tiles, a test switch)
-    if (allow < 0 && !c->tune.dense_boxes) compact = false;
-    BayerArgs bl;
-    bool direct = false; // the gray-less path
+    if (allow < 0 && !c->tune.dense_boxes) p.compact = false;
+    p.frames = frames;
+    p.bayer = bayer != nullptr;
+    if (bayer) p.bl = *bayer;
     if (bayer && !bayer->dst) {
-        bl = *bayer;
-        direct = compact && allow >= 0 && own_mask && bayer_scan_direct(bl);
-        if (!direct) { // the dense path, W % 16 or H % 8 not 0, unaligned frames, MOCAP_SKIP_DARK=0 / MOCAP_GENERAL_FILTER=1
-            const size_t bytes = (size_t)(n_images - 1) * image_stride + (size_t)(c->H - 1) * pitch + c->W;
-            if (int rc = ensure_gray_scratch(c, bytes)) return rc;
-            bl.dst = c->gray_scratch;
+        p.direct = p.compact && allow >= 0 && bt.own_mask && bayer_scan_direct(p.bl);
+        if (!p.direct) { // the dense path, W % 16 or H % 8 not 0, unaligned frames, MOCAP_SKIP_DARK=0 / MOCAP_GENERAL_FILTER=1
+            const size_t bytes = (size_t)(bt.n_images - 1) * bt.image_stride + (size_t)(c->H - 1) * bt.pitch + c->W;
+            TRY(ensure_gray_scratch(c, bytes));
+            p.bl.dst = c->gray_scratch;
         }
-        frames = direct ? (const void*)bl.src : (const void*)bl.dst;
-        bayer = &bl;
+        p.frames = p.direct ? (const void*)p.bl.src : (const void*)p.bl.dst;
     }
-    if (!compact) {
-        // general dense kernel (tiny images, tables beyond the compact format): every tile, every mask byte
-        FilterArgs a;
-        a.src = (const uint8_t*)frames; a.image_stride = image_stride; a.pitch = pitch; a.H = c->H; a.W = c->W;
-        a.mask = mask; a.words_per_row = c->wpr; a.cam_mod = cam_mod; a.cells = cells;
-        a.map = c->maps ? c->maps + (size_t)slot_base * c->H * c->W : nullptr;
-        a.mapw = c->maps ? c->maps + (size_t)(c->n_slots + slot_base) * c->H * c->W : nullptr;
-        a.n_images = n_images; a.n_steps = (n_images + cam_mod - 1) / cam_mod;
-        a.thr_mul = thr_mul;
-        a.n_strips = tl.n_strips; a.rows_per_chunk = tl.rows; a.n_cgroups = tl.n_cgroups;
-        a.pipelined = c->W >= 4 && (c->W & 3) == 0 && c->H >= 2;
-        if (!c->tune.remap_pipeline) a.pipelined = 0; // test switch: the per-pixel gather
-        a.staged = rows_staged; a.stage_dw = rows_dw;
-        a.map4 = c->map4 ? c->map4 + (size_t)slot_base * c->H * c->W : nullptr;
-        a.rowbox = c->rowbox ? c->rowbox + (size_t)slot_base * c->H * tl.n_strips : nullptr;
-        if (bayer) { launch_bayer_gray(*bayer, s); HIP_TRY(hipGetLastError()); }
-        if (own_mask) c->mask_dirty = true;
-        prof_begin(c, 0, s, p, on);
-        launch_filter_mask(a, remap, s);
-        prof_end(c, 0, s, p, on);
-        HIP_TRY(hipGetLastError());
-        return 0;
-    }
-    if (own_mask && c->mask_dirty) { // the general kernel wrote the whole mask last time: back to "zero outside the regions"
-        HIP_TRY(hipMemsetAsync(c->mask, 0, sizeof(uint32_t) * c->mask_images * mask_image_words(c->H, c->wpr), s));
-        std::vector<uint32_t> init(c->mask_images * cells_per_image(c) * 4);
-        for (size_t i = 0; i < init.size(); i += 4) { init[i] = 1u; init[i + 1] = 1u; init[i + 2] = 1u; init[i + 3] = 1u; }
-        HIP_TRY(hipStreamSynchronize(s));
-        HIP_TRY(hipMemcpy(c->cur_box, init.data(), sizeof(uint32_t) * init.size(), hipMemcpyHostToDevice));
-        c->mask_dirty = false;
-    }
-    BoxArgs a;
-    a.src = (const uint8_t*)frames; a.image_stride = image_stride; a.pitch = pitch; a.H = c->H; a.W = c->W;
-    a.mask = mask; a.words_per_row = c->wpr; a.cells = cells;
-    a.map4 = c->map4 ? c->map4 + (size_t)slot_base * c->H * c->W : nullptr;
-    a.srcbox = c->srcbox ? c->srcbox + (size_t)slot_base * source_cells(c) : nullptr;
-    a.remap_bits = remap_bits;
-    a.cam_mod = cam_mod; a.n_images = n_images; a.n_steps = (n_images + cam_mod - 1) / cam_mod;
-    a.thr_mul = thr_mul;
+    return 0;
+}
+
+// general dense kernel (tiny images, tables beyond the compact format): every tile, every mask byte
+static int filter_dense(mocap_ctx* c, const Batch& bt, const FilterPath& p, int thr_mul)
+{
+    FilterArgs a = filter_args(c, p.frames, bt.image_stride, bt.pitch, bt.mask, bt.cells, bt.slot_base, bt.cam_mod, bt.n_images, thr_mul);
+    if (!c->tune.remap_pipeline) a.pipelined = 0; // test switch: the per-pixel gather
+    a.staged = p.rows_staged; a.stage_dw = p.rows_dw;
+    if (p.bayer) { launch_bayer_gray(p.bl, bt.s); HIP_TRY(hipGetLastError()); }
+    if (bt.own_mask) c->mask_dirty = true;
+    EvPair ev; bool on;
+    prof_begin(c, 0, bt.s, ev, on);
+    launch_filter_mask(a, p.remap, bt.s);
+    prof_end(c, 0, bt.s, ev, on);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// what settle and the box kernel get (timing and zero8 are added by their steps)
+static BoxArgs box_args(const mocap_ctx* c, const Batch& bt, const FilterPath& p, const ScanBounds& sb)
+{
+    const Tiling tl = tiling(c);
+    BoxArgs a{};
+    a.src = (const uint8_t*)p.frames; a.image_stride = bt.image_stride; a.pitch = bt.pitch; a.H = c->H; a.W = c->W;
+    a.mask = bt.mask; a.words_per_row = c->wpr; a.cells = bt.cells;
+    a.map4 = slot_map4(c, bt.slot_base);
+    a.srcbox = c->srcbox ? c->srcbox + (size_t)bt.slot_base * source_cells(c) : nullptr;
+    a.remap_bits = p.remap_bits;
+    a.cam_mod = bt.cam_mod; a.n_images = bt.n_images; a.n_steps = (bt.n_images + bt.cam_mod - 1) / bt.cam_mod;
+    a.thr_mul = sb.thr_mul;
     a.rows_per_chunk = tl.rows; a.n_strips = tl.n_strips; a.n_chunks = tl.n_cgroups * 4;
     const size_t tr_words = c->mask_images * cells_per_image(c) * 4;
-    uint32_t* const tr_cur = c->tile_rows + (c->tile_rows_flip ? tr_words : 0);
-    a.tile_rows = tr_cur;
+    a.tile_rows = c->tile_rows + (c->tile_rows_flip ? tr_words : 0);
     a.tile_rows_next = c->tile_rows + (c->tile_rows_flip ? 0 : tr_words);
     a.n_clear = c->tile_rows_hold[c->tile_rows_flip ^ 1];
     a.cluster = c->tune.cluster;
-    a.cur_box = own_mask ? c->cur_box : c->cur_box_ext;
-    a.items = c->items; a.n_items = c->n_items; a.cap_items = c->cap_items;
-    a.dense = allow < 0;
+    a.cur_box = bt.own_mask ? c->cur_box : c->cur_box_ext;
+    a.items = c->items; a.n_items = c->n_items; a.cap_items = (uint32_t)c->items.n;
+    a.dense = sb.allow < 0;
     // Boxes wider than this many patch quads go through the sliding row pipeline instead (whole tile width, the box's rows):
     // the box kernel's cost grows with the patch area (~30 cycles per quad-row), the row pipeline's with the rows only
     // (~850 cycles per row with the gather).  Measured optimum on the benchmark scenes (8 and 32 markers, both lens models):
     // 38-46 quads; without the routing the 32-marker scene's filter takes 1.77 ms instead of 1.25, the 8-marker scene's
     // 0.53 instead of 0.49.  MOCAP_WIDE_QUADS="remap,identity" overrides (A/B switch; 1000 = never).
-    a.wide_tiles = c->wide_tiles; a.cap_wide = c->cap_wide; a.wide_quads_remap = c->tune.wide_quads_remap; a.wide_quads_identity = c->tune.wide_quads_identity;
+    a.wide_tiles = c->wide_tiles; a.cap_wide = (uint32_t)c->wide_tiles.n; a.wide_quads_remap = c->tune.wide_quads_remap; a.wide_quads_identity = c->tune.wide_quads_identity;
     a.wide_bands = c->tune.wide_bands; // measured: 2 / 4 bands 0.50 / 0.55 ms against 0.475 (8 markers), 1.33 / 1.58 against 1.22 (32 markers): the kernel is work-bound
-    if (c->W < 4 || direct) a.wide_tiles = nullptr;
-    a.bayer = direct ? bl : BayerArgs{}; // (a.src = the Bayer frames)
+    if (c->W < 4 || p.direct) a.wide_tiles = nullptr;
+    a.bayer = p.direct ? p.bl : BayerArgs{}; // (a.src = the Bayer frames)
     a.stage_bytes = c->tune.box_stage_bytes; // test switch
     a.prio = c->tune.box_prio;
-    a.ext_mask = own_mask ? 0 : 1;
-    if ((size_t)n_images * cells_per_image(c) * BOX_MAX_PARTS > (size_t)c->cap_items) return fail(MOCAP_E_STATE, "work list smaller than the batch");
-    // the counter block (item counts, run heads) must be zero before settle: the scan's first workgroup does that on its way -- a fill
-    // launch of its own is one more tiny kernel that waits for a place beside the other batches' kernels -- unless no plain scan runs
-    const bool scan_zeroes = !a.dense && !bayer && c->tune.scan_blocks_per_cu == 0 && c->tune.scan_slices <= 1;
-    if (!scan_zeroes) HIP_TRY(hipMemsetAsync(c->n_items, 0, 1024, s));
-    a.zero8 = own_mask ? c->walk_count : nullptr; // (the contour stage of this batch follows on the same stream; null before its first batch)
-    c->walk_count_zeroed = a.zero8 != nullptr;
-    BrightArgs mark_args{}; bool mark_after_scan = false;
-    if (!a.dense) { // one streaming pass over the frames marks the tiles (and their boxes) that can hold set pixels
-        // floor(i / ncx) = umulhi(i, ceil(2^32 / ncx)) is exact while i * ncx < 2^32
-        uint64_t ncx64 = (uint64_t)((c->W + 7) / 8);
-        const uint64_t ncells = ncx64 * (uint64_t)((c->H + 7) / 8);
-        int wide = (c->W % 16 == 0) && (pitch % 16 == 0) && (image_stride % 16 == 0) && (((uintptr_t)frames & 15) == 0) && ncx64 >= 4;
-        if (wide && ncells * (ncx64 / 2) >= (1ull << 32)) wide = 0;
-        if (!c->tune.scan_wide) wide = 0; // A/B switch
-        if (wide) ncx64 /= 2; // the wide kernel divides pair indices by the pairs per cell row
-        const uint32_t ncx_magic = (ncx64 > 1 && ncells * ncx64 < (1ull << 32)) ? (uint32_t)(((1ull << 32) + ncx64 - 1) / ncx64) : 0u;
-        BrightArgs b{(const uint8_t*)frames, image_stride, pitch, c->H, c->W, n_images, cam_mod, ncx_magic, wide, base, allow / 4, allow_cut1 / 4, allow_cut2 / 4,
-                     c->reach + (size_t)slot_base * source_cells(c), c->cflags + (size_t)slot_base * source_cells(c),
-                     tr_cur, tl.n_cgroups * 4, tl.n_strips, (uint32_t)(((1u << 23) + tl.rows - 1) / tl.rows),
-                     mask, own_mask ? 0 : (size_t)n_images * mask_image_words(c->H, c->wpr), ((uintptr_t)mask & 15) == 0, nullptr, base_alt, allow_alt / 4, 0};
-        b.prio = c->tune.scan_prio; // A/B switch
-        b.max_blocks = c->tune.scan_blocks_per_cu * c->n_cu; b.blocks_x = 0;
-        b.zero_counters = scan_zeroes ? c->n_items : nullptr;
-        b.block_ctr = c->n_items + 160; // (words 160..223 of the counter block zeroed above: one per slice)
-        b.slices = c->tune.scan_slices; b.image0 = 0; b.slice_images = n_images;
-        const bool probe = fixed_base < 0 && !c->probe_pending && allow_alt >= 0 && base_alt != base && !bayer &&
-                           (c->probe_age == 0 || c->probe_age >= 32);
-        if (probe) {
-            HIP_TRY(hipMemsetAsync(c->probe_dev, 0, PROBE_BYTES, s));
-            b.probe = c->probe_dev;
-        }
-        c->probe_age = probe ? 1 : c->probe_age + 1;
-        const bool fused = bayer && own_mask && (direct || bayer_scan_fusable(*bayer)); // direct: the scan without the gray write-back
-        // the streaming scan leaves a hot map (two bits per cell, no table lookups or atomics behind its loads) that
-        // mark_tiles_kernel turns into tile boxes; the fused Bayer pass marks the tiles itself (MOCAP_SCAN_HOTMAP=0: so does the scan)
-        const bool two_step = !fused && c->hotmap && (c->tune.scan_hotmap == 2 || (c->tune.scan_hotmap == 1 && c->hot_dense));
-        if (two_step) { b.hotmap = c->hotmap; b.hot_words = hot_map_words(c->H, c->W, wide); b.mark_grid = c->tune.mark_blocks_per_cu * c->n_cu; }
-        ScanTurn* turn = c->tune.scan_serial && c->device >= 0 && c->device < 64 ? &g_scan_turn[c->device] : nullptr;
-        std::unique_lock<std::mutex> turn_lock;
-        if (turn) {
-            turn_lock = std::unique_lock<std::mutex>(turn->mu);
-            if (!turn->done) HIP_TRY(hipEventCreateWithFlags(&turn->done, hipEventDisableTiming));
-            if (turn->have) HIP_TRY(hipStreamWaitEvent(s, turn->done, 0));
-        }
-        prof_begin(c, 3, s, p, on);
-        if (fused) launch_bayer_gray_scan(*bayer, b, s);
-        else {
-            if (bayer) launch_bayer_gray(*bayer, s);
-            launch_bright_cells(b, s);
-        }
-        prof_end(c, 3, s, p, on);
-        HIP_TRY(hipGetLastError());
-        if (turn) {
-            HIP_TRY(hipEventRecord(turn->done, s));
-            turn->have = true;
-            turn_lock.unlock();
-        }
-        mark_args = b; mark_after_scan = two_step; // (launched with settle, inside its timer: both turn the scan's output into work lists)
-        if (probe) {
-            HIP_TRY(hipMemcpyAsync(c->probe_host, c->probe_dev, PROBE_BYTES, hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipEventRecord(c->probe_ev, s));
-            c->probe_pending = true;
-            c->probe_images = (n_images + 15) / 16;
-        }
+    a.ext_mask = bt.own_mask ? 0 : 1;
+    return a;
+}
+
+// the scan's arguments, without probe and hot map
+static BrightArgs bright_args(const mocap_ctx* c, const Batch& bt, const FilterPath& p, const ScanBounds& sb, uint32_t* tile_rows, bool scan_zeroes)
+{
+    const Tiling tl = tiling(c);
+    // floor(i / ncx) = umulhi(i, ceil(2^32 / ncx)) is exact while i * ncx < 2^32
+    uint64_t ncx64 = (uint64_t)((c->W + 7) / 8);
+    const uint64_t ncells = ncx64 * (uint64_t)((c->H + 7) / 8);
+    int wide = (c->W % 16 == 0) && (bt.pitch % 16 == 0) && (bt.image_stride % 16 == 0) && (((uintptr_t)p.frames & 15) == 0) && ncx64 >= 4;
+    if (wide && ncells * (ncx64 / 2) >= (1ull << 32)) wide = 0;
+    if (!c->tune.scan_wide) wide = 0; // A/B switch
+    if (wide) ncx64 /= 2; // the wide kernel divides pair indices by the pairs per cell row
+    const uint32_t ncx_magic = (ncx64 > 1 && ncells * ncx64 < (1ull << 32)) ? (uint32_t)(((1ull << 32) + ncx64 - 1) / ncx64) : 0u;
+    BrightArgs b{(const uint8_t*)p.frames, bt.image_stride, bt.pitch, c->H, c->W, bt.n_images, bt.cam_mod, ncx_magic, wide, sb.base, sb.allow / 4, sb.allow_cut1 / 4, sb.allow_cut2 / 4,
+                 c->reach + (size_t)bt.slot_base * source_cells(c), c->cflags + (size_t)bt.slot_base * source_cells(c),
+                 tile_rows, tl.n_cgroups * 4, tl.n_strips, (uint32_t)(((1u << 23) + tl.rows - 1) / tl.rows),
+                 bt.mask, bt.own_mask ? 0 : (size_t)bt.n_images * mask_image_words(c->H, c->wpr), ((uintptr_t)bt.mask & 15) == 0, nullptr, sb.base_alt, sb.allow_alt / 4, 0};
+    b.prio = c->tune.scan_prio; // A/B switch
+    b.max_blocks = c->tune.scan_blocks_per_cu * c->n_cu; b.blocks_x = 0;
+    b.zero_counters = scan_zeroes ? c->n_items.p : nullptr;
+    b.block_ctr = c->n_items + 160; // (words 160..223 of the counter block zeroed above: one per slice)
+    b.slices = c->tune.scan_slices; b.image0 = 0; b.slice_images = bt.n_images;
+    return b;
+}
+
+// One streaming pass over the frames marks the tiles (and their boxes) that can hold set pixels.  `b` keeps what it ran with,
+// for mark_tiles_kernel when that one has to follow (`mark_after_scan`).
+static int scan_tiles(mocap_ctx* c, const Batch& bt, const FilterPath& p, const ScanBounds& sb, uint32_t* tile_rows, bool scan_zeroes,
+                      BrightArgs& b, bool& mark_after_scan)
+{
+    const hipStream_t s = bt.s;
+    b = bright_args(c, bt, p, sb, tile_rows, scan_zeroes);
+    const bool probe = sb.fixed_base < 0 && !c->probe_pending && sb.allow_alt >= 0 && sb.base_alt != sb.base && !p.bayer &&
+                       (c->probe_age == 0 || c->probe_age >= 32);
+    if (probe) {
+        HIP_TRY(hipMemsetAsync(c->probe_dev, 0, PROBE_BYTES, s));
+        b.probe = c->probe_dev;
     }
-    else if (bayer) { // no early-out (not provable for this table, or MOCAP_SKIP_DARK=0): the plain gray pass
-        launch_bayer_gray(*bayer, s);
-        HIP_TRY(hipGetLastError());
+    c->probe_age = probe ? 1 : c->probe_age + 1;
+    const bool fused = p.bayer && bt.own_mask && (p.direct || bayer_scan_fusable(p.bl)); // direct: the scan without the gray write-back
+    // the streaming scan leaves a hot map (two bits per cell, no table lookups or atomics behind its loads) that
+    // mark_tiles_kernel turns into tile boxes; the fused Bayer pass marks the tiles itself (MOCAP_SCAN_HOTMAP=0: so does the scan)
+    const bool two_step = !fused && c->hotmap && (c->tune.scan_hotmap == 2 || (c->tune.scan_hotmap == 1 && c->hot_dense));
+    if (two_step) { b.hotmap = c->hotmap; b.hot_words = hot_map_words(c->H, c->W, b.wide); b.mark_grid = c->tune.mark_blocks_per_cu * c->n_cu; }
+    ScanTurn* turn = c->tune.scan_serial && c->device >= 0 && c->device < 64 ? &g_scan_turn[c->device] : nullptr;
+    std::unique_lock<std::mutex> turn_lock; // held from the wait to the record: the chain's order is the lock's order
+    if (turn) {
+        turn_lock = std::unique_lock<std::mutex>(turn->mu);
+        if (!turn->done) HIP_TRY(hipEventCreateWithFlags(&turn->done, hipEventDisableTiming));
+        if (turn->have) HIP_TRY(hipStreamWaitEvent(s, turn->done, 0));
     }
-    prof_begin(c, 4, s, p, on);
+    EvPair ev; bool on;
+    prof_begin(c, 3, s, ev, on);
+    if (fused) launch_bayer_gray_scan(p.bl, b, s);
+    else {
+        if (p.bayer) launch_bayer_gray(p.bl, s);
+        launch_bright_cells(b, s);
+    }
+    prof_end(c, 3, s, ev, on);
+    HIP_TRY(hipGetLastError());
+    if (turn) {
+        HIP_TRY(hipEventRecord(turn->done, s));
+        turn->have = true;
+        turn_lock.unlock();
+    }
+    mark_after_scan = two_step; // (launched with settle, inside its timer: both turn the scan's output into work lists)
+    if (probe) {
+        HIP_TRY(hipMemcpyAsync(c->probe_host, c->probe_dev, PROBE_BYTES, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipEventRecord(c->probe_ev, s));
+        c->probe_pending = true;
+        c->probe_images = (bt.n_images + 15) / 16;
+    }
+    return 0;
+}
+
+// the scan's output becomes work lists: mark_tiles_kernel (when the scan left a hot map) and settle_tiles_kernel
+static int settle_tiles(mocap_ctx* c, const BoxArgs& a, const BrightArgs& mark_args, bool mark_after_scan, hipStream_t s)
+{
+    EvPair ev; bool on;
+    prof_begin(c, 4, s, ev, on);
     if (mark_after_scan) {
         launch_mark_tiles(mark_args, s);
         HIP_TRY(hipGetLastError());
     }
     launch_settle_tiles(a, s);
-    prof_end(c, 4, s, p, on);
+    prof_end(c, 4, s, ev, on);
     HIP_TRY(hipGetLastError());
     if (!a.dense) { // only now: settle (queued) has emptied the array the next batch's scan will widen
-        if (n_images > c->tile_rows_hold[c->tile_rows_flip]) c->tile_rows_hold[c->tile_rows_flip] = n_images;
+        if (a.n_images > c->tile_rows_hold[c->tile_rows_flip]) c->tile_rows_hold[c->tile_rows_flip] = a.n_images;
         c->tile_rows_hold[c->tile_rows_flip ^ 1] = 0;
         c->tile_rows_flip ^= 1;
     }
-    a.timing = nullptr;
-    const bool box_timing = c->tune.box_timing != 0;
-    if (box_timing) { // debugging aid: synchronous, prints the mean duration of the box kernel's phases
-        HIP_TRY(hipMalloc(&a.timing, sizeof(uint64_t) * 6 * c->box_grid));
-        HIP_TRY(hipMemsetAsync(a.timing, 0, sizeof(uint64_t) * 6 * c->box_grid, s));
+    return 0;
+}
+
+// debugging aid (box_timing): synchronous, prints the mean duration of the box kernel's phases
+static int report_box_timing(mocap_ctx* c, const uint64_t* timing, hipStream_t s)
+{
+    std::vector<uint64_t> t((size_t)6 * c->box_grid);
+    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipMemcpy(t.data(), timing, sizeof(uint64_t) * t.size(), hipMemcpyDeviceToHost));
+    double sum[6] = {0, 0, 0, 0, 0, 0}, mx = 0;
+    for (int b = 0; b < c->box_grid; b++) {
+        double tot = 0;
+        for (int i = 0; i < 6; i++) { sum[i] += (double)t[6 * b + i]; if (i < 5) tot += (double)t[6 * b + i]; }
+        mx = tot > mx ? tot : mx;
     }
-    prof_begin(c, 0, s, p, on);
+    const double n = sum[5] > 0 ? sum[5] : 1;
+    uint32_t cnt[16];
+    HIP_TRY(hipMemcpy(cnt, c->n_items, sizeof(cnt), hipMemcpyDeviceToHost));
+    fprintf(stderr, "[box] list: %u items, %u wide-tile entries\n", cnt[0], cnt[8]);
+    fprintf(stderr, "[box] items %.0f (%.1f per wave) | cycles per item: header+wait %.0f, stage %.0f, patch %.0f, threshold %.0f, majority+next %.0f | busiest wave %.0f cycles\n",
+            sum[5], sum[5] / c->box_grid, sum[0] / n, sum[1] / n, sum[2] / n, sum[3] / n, sum[4] / n, mx);
+    return 0;
+}
+
+// the box kernel over the items, and the row pipeline over the list of tiles with wide boxes
+static int filter_boxes(mocap_ctx* c, const Batch& bt, const FilterPath& p, BoxArgs& a)
+{
+    const hipStream_t s = bt.s;
+    Buf<uint64_t> timing;
+    if (c->tune.box_timing) {
+        TRY(timing.reserve((size_t)6 * c->box_grid));
+        HIP_TRY(hipMemsetAsync(timing, 0, sizeof(uint64_t) * 6 * c->box_grid, s));
+    }
+    a.timing = timing;
+    EvPair ev; bool on;
+    prof_begin(c, 0, s, ev, on);
     // MOCAP_WIDE_FORK=1: the wide-tile kernel on a side stream beside the box kernel (fork / join by events).  Measured: the pair takes
     // 0.53 ms instead of 0.49 alone and the three-batch pipeline 310k instead of 319k frames/s, so it is off.
     const bool fork_wide = c->tune.wide_fork != 0;
     if (a.wide_tiles) { // the tiles with wide boxes: the row pipeline over their list, beside the box kernel (both only read what
                         // settle left and write disjoint tiles): forked onto the context's side stream, joined before the contours
-        FilterArgs f;
-        f.src = a.src; f.image_stride = image_stride; f.pitch = pitch; f.H = c->H; f.W = c->W;
-        f.mask = mask; f.words_per_row = c->wpr; f.cam_mod = cam_mod; f.cells = cells;
-        f.map = c->maps ? c->maps + (size_t)slot_base * c->H * c->W : nullptr;
-        f.mapw = c->maps ? c->maps + (size_t)(c->n_slots + slot_base) * c->H * c->W : nullptr;
-        f.n_images = n_images; f.n_steps = a.n_steps; f.thr_mul = thr_mul;
-        f.n_strips = tl.n_strips; f.rows_per_chunk = tl.rows; f.n_cgroups = tl.n_cgroups;
-        f.tiles = c->wide_tiles; f.n_tiles = c->n_items + 8; f.cap_tiles = c->cap_wide;
-        f.pipelined = (c->W & 3) == 0 && c->H >= 2;
-        f.staged = rows_staged; f.stage_dw = rows_dw; f.map4 = a.map4;
-        f.rowbox = c->rowbox ? c->rowbox + (size_t)slot_base * c->H * tl.n_strips : nullptr;
+        FilterArgs f = filter_args(c, a.src, bt.image_stride, bt.pitch, bt.mask, bt.cells, bt.slot_base, bt.cam_mod, bt.n_images, a.thr_mul);
+        f.tiles = c->wide_tiles; f.n_tiles = c->n_items + 8; f.cap_tiles = a.cap_wide;
+        f.staged = p.rows_staged; f.stage_dw = p.rows_dw;
         hipStream_t ws = s;
         if (fork_wide) {
             HIP_TRY(hipEventRecord(c->ev_fork, s));
@@ -888,33 +943,53 @@ static int run_filter(mocap_ctx* c, const void* frames, int n_images, int cam_mo
             HIP_TRY(hipStreamWaitEvent(c->side, c->ev_fork, 0));
             ws = c->side;
         }
-        launch_filter_tiles(f, remap, c->tune.wide_blocks_per_cu * c->n_cu, ws);
+        launch_filter_tiles(f, p.remap, c->tune.wide_blocks_per_cu * c->n_cu, ws);
         HIP_TRY(hipGetLastError());
         if (fork_wide) HIP_TRY(hipEventRecord(c->ev_join, c->side));
     }
-    launch_box_filter(a, c->box_grid, s, direct);
+    launch_box_filter(a, c->box_grid, s, p.direct);
     HIP_TRY(hipGetLastError());
     if (a.wide_tiles && fork_wide) HIP_TRY(hipStreamWaitEvent(s, c->ev_join, 0));
-    prof_end(c, 0, s, p, on);
-    if (box_timing) {
-        std::vector<uint64_t> t((size_t)6 * c->box_grid);
+    prof_end(c, 0, s, ev, on);
+    return timing ? report_box_timing(c, timing, s) : 0;
+}
+
+static int run_filter(mocap_ctx* c, const void* frames, int n_images, int cam_mod, int slot_base, size_t image_stride,
+                      int pitch, uint32_t* mask, uint32_t* cells, hipStream_t s, const BayerArgs* bayer = nullptr)
+{
+    const Batch bt{n_images, cam_mod, slot_base, image_stride, pitch, mask, cells, mask == c->mask, s};
+    c->walk_count_zeroed = false;
+    if (cells == c->cells) c->last_images = n_images;
+    const int thr_mul = threshold_mul(c);
+    read_probe(c, thr_mul);
+    const ScanBounds sb = scan_bounds(c, slot_base, cam_mod, thr_mul);
+    FilterPath p;
+    TRY(choose_path(c, bt, frames, bayer, sb.allow, p));
+    if (!p.compact) return filter_dense(c, bt, p, thr_mul);
+    if (bt.own_mask && c->mask_dirty) { // the general kernel wrote the whole mask last time: back to "zero outside the regions"
+        HIP_TRY(hipMemsetAsync(c->mask, 0, sizeof(uint32_t) * c->mask_images * mask_image_words(c->H, c->wpr), s));
+        std::vector<uint32_t> init(c->mask_images * cells_per_image(c) * 4);
+        for (size_t i = 0; i < init.size(); i += 4) { init[i] = 1u; init[i + 1] = 1u; init[i + 2] = 1u; init[i + 3] = 1u; }
         HIP_TRY(hipStreamSynchronize(s));
-        HIP_TRY(hipMemcpy(t.data(), a.timing, sizeof(uint64_t) * t.size(), hipMemcpyDeviceToHost));
-        (void)hipFree(a.timing);
-        double sum[6] = {0, 0, 0, 0, 0, 0}, mx = 0;
-        for (int b = 0; b < c->box_grid; b++) {
-            double tot = 0;
-            for (int i = 0; i < 6; i++) { sum[i] += (double)t[6 * b + i]; if (i < 5) tot += (double)t[6 * b + i]; }
-            mx = tot > mx ? tot : mx;
-        }
-        const double n = sum[5] > 0 ? sum[5] : 1;
-        uint32_t cnt[16];
-        HIP_TRY(hipMemcpy(cnt, c->n_items, sizeof(cnt), hipMemcpyDeviceToHost));
-        fprintf(stderr, "[box] list: %u items, %u wide-tile entries\n", cnt[0], cnt[8]);
-        fprintf(stderr, "[box] items %.0f (%.1f per wave) | cycles per item: header+wait %.0f, stage %.0f, patch %.0f, threshold %.0f, majority+next %.0f | busiest wave %.0f cycles\n",
-                sum[5], sum[5] / c->box_grid, sum[0] / n, sum[1] / n, sum[2] / n, sum[3] / n, sum[4] / n, mx);
+        HIP_TRY(hipMemcpy(c->cur_box, init.data(), sizeof(uint32_t) * init.size(), hipMemcpyHostToDevice));
+        c->mask_dirty = false;
     }
-    return 0;
+    BoxArgs a = box_args(c, bt, p, sb);
+    if ((size_t)n_images * cells_per_image(c) * BOX_MAX_PARTS > c->items.n) return fail(MOCAP_E_STATE, "work list smaller than the batch");
+    // the counter block (item counts, run heads) must be zero before settle: the scan's first workgroup does that on its way -- a fill
+    // launch of its own is one more tiny kernel that waits for a place beside the other batches' kernels -- unless no plain scan runs
+    const bool scan_zeroes = !a.dense && !p.bayer && c->tune.scan_blocks_per_cu == 0 && c->tune.scan_slices <= 1;
+    if (!scan_zeroes) HIP_TRY(hipMemsetAsync(c->n_items, 0, 1024, s));
+    a.zero8 = bt.own_mask ? c->walk_count.p : nullptr; // (the contour stage of this batch follows on the same stream; null before its first batch)
+    c->walk_count_zeroed = a.zero8 != nullptr;
+    BrightArgs mark_args{}; bool mark_after_scan = false;
+    if (!a.dense) TRY(scan_tiles(c, bt, p, sb, a.tile_rows, scan_zeroes, mark_args, mark_after_scan));
+    else if (p.bayer) { // no early-out (not provable for this table, or MOCAP_SKIP_DARK=0): the plain gray pass
+        launch_bayer_gray(p.bl, s);
+        HIP_TRY(hipGetLastError());
+    }
+    TRY(settle_tiles(c, a, mark_args, mark_after_scan, s));
+    return filter_boxes(c, bt, p, a);
 }
 
 // the tiles' output regions / scan boxes of the batch just filtered into the context's mask (settle_tiles_kernel), when the
@@ -922,6 +997,72 @@ static int run_filter(mocap_ctx* c, const void* frames, int n_images, int cam_mo
 static const uint32_t* contour_boxes(mocap_ctx* c)
 {
     return (c->mask_dirty || !c->tune.contour_boxes) ? nullptr : c->cur_box;
+}
+
+// the contour group: workspace per image, the batch's walk lists (in whole 8-byte words), their counters
+static int ensure_contour_work(mocap_ctx* c, size_t n_images)
+{
+    if (n_images <= c->cwork_images) return 0;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (n_images <= c->cwork_images) return 0;
+    c->cwork_images = 0;
+    int rc = c->cwork.reserve(contour_work_bytes() * n_images);
+    if (!rc) rc = c->walk_list.reserve((contour_walk_bytes() * n_images + 7) / 8);
+    if (!rc) rc = c->link_list.reserve(((contour_link_bytes() + sizeof(uint32_t)) * n_images + 7) / 8); // + the wait list behind it
+    if (!rc) rc = c->walk_count.reserve(64);
+    if (rc) { c->cwork.release(); c->walk_list.release(); c->link_list.release(); return rc; } // not half a group: the next call starts over
+    c->cwork_images = n_images;
+    return 0;
+}
+
+// debugging aid (follow_timing): synchronous, the follow kernel's phase clock per wave
+static int report_follow_timing(const uint64_t* follow_dbg, int follow_grid, hipStream_t s)
+{
+    std::vector<uint64_t> t((size_t)8 * follow_grid);
+    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipMemcpy(t.data(), follow_dbg, sizeof(uint64_t) * t.size(), hipMemcpyDeviceToHost));
+    double sum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, mx[3] = {0, 0, 0}, mxsteps = 0; int used = 0;
+    for (int b = 0; b < follow_grid; b++) {
+        if (t[8 * b + 5] == 0) continue;
+        used++;
+        for (int i = 0; i < 8; i++) sum[i] += (double)t[8 * b + i];
+        for (int i = 0; i < 3; i++) mx[i] = (double)t[8 * b + i] > mx[i] ? (double)t[8 * b + i] : mx[i];
+        mxsteps = (double)t[8 * b + 3] > mxsteps ? (double)t[8 * b + 3] : mxsteps;
+    }
+    const double u = used ? used : 1;
+    fprintf(stderr, "[follow] %d of %d waves had work | per wave (mean / max us): store %.1f / %.1f, refill %.1f / %.1f, walk %.1f / %.1f | wave steps %.0f (max %.0f), "
+                    "lanes alive per step %.1f, walks %.1f, refills %.1f | us per wave step %.3f\n",
+            used, follow_grid, sum[0] / u / 100, mx[0] / 100, sum[1] / u / 100, mx[1] / 100, sum[2] / u / 100, mx[2] / 100, sum[3] / u, mxsteps,
+            sum[3] > 0 ? sum[4] / sum[3] : 0.0, sum[5] / u, sum[6] / u, sum[3] > 0 ? sum[2] / 100 / sum[3] : 0.0);
+    return 0;
+}
+
+// debugging aid (contour_timing): synchronous, prints the mean duration of the kernel's phases
+static int report_contour_timing(const uint64_t* timing, int n_images, hipStream_t s)
+{
+    std::vector<uint64_t> t((size_t)8 * n_images);
+    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipMemcpy(t.data(), timing, sizeof(uint64_t) * t.size(), hipMemcpyDeviceToHost));
+    double sum[4] = {0, 0, 0, 0}, mx = 0; uint64_t lo = ~0ull, hi = 0;
+    for (int i = 0; i < n_images; i++) {
+        for (int k = 0; k < 4; k++) sum[k] += (double)(t[8 * i + k + 1] - t[8 * i + k]);
+        double tot = (double)(t[8 * i + 4] - t[8 * i]); mx = tot > mx ? tot : mx;
+        lo = t[8 * i] < lo ? t[8 * i] : lo; hi = t[8 * i + 4] > hi ? t[8 * i + 4] : hi;
+    }
+    {
+        int worst = 0; double wt = 0, sc = 0, ss = 0;
+        for (int i = 0; i < n_images; i++) {
+            double tot = (double)(t[8 * i + 4] - t[8 * i]);
+            if (tot > wt) { wt = tot; worst = i; }
+            sc += (double)t[8 * i + 5]; ss += (double)t[8 * i + 6];
+        }
+        fprintf(stderr, "[contours] slowest image %d: %.1f us, candidates %llu, longest border %llu steps, borders %llu | mean candidates %.1f, mean longest border %.1f steps\n",
+                worst, wt / 100, (unsigned long long)t[8 * worst + 5], (unsigned long long)t[8 * worst + 6], (unsigned long long)t[8 * worst + 7],
+                sc / n_images, ss / n_images);
+    }
+    fprintf(stderr, "[contours] mean us per block: candidates %.1f follow %.1f link %.1f order %.1f | slowest block %.1f | first start to last end %.1f\n",
+            sum[0] / n_images / 100, sum[1] / n_images / 100, sum[2] / n_images / 100, sum[3] / n_images / 100, mx / 100, (double)(hi - lo) / 100);
+    return 0;
 }
 
 static int run_contours(mocap_ctx* c, const uint32_t* mask, const uint32_t* cells, const uint32_t* boxes, int n_images, int32_t* out_xy, long xy_stride,
@@ -938,17 +1079,7 @@ static int run_contours(mocap_ctx* c, const uint32_t* mask, const uint32_t* cell
     Tiling tl = tiling(c);
     a.cells = cells; a.boxes = boxes; a.rows_per_chunk = tl.rows; a.n_chunks = tl.n_cgroups * 4; a.n_strips = tl.n_strips;
     if ((long long)a.n_chunks * a.n_strips * ((tl.rows + 7) / 8) > 65535 || c->wpr > 4096) a.cells = nullptr; // cell ids are 16-bit, first words 12-bit in the kernel: scan every row instead
-    if ((size_t)n_images > c->cwork_images) {
-        std::lock_guard<std::mutex> lk(c->mu);
-        if (c->cwork) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(c->cwork)); c->cwork = nullptr; c->cwork_images = 0; }
-        if (c->walk_list) { HIP_TRY(hipFree(c->walk_list)); c->walk_list = nullptr; }
-        if (c->link_list) { HIP_TRY(hipFree(c->link_list)); c->link_list = nullptr; }
-        HIP_TRY(hipMalloc(&c->cwork, contour_work_bytes() * (size_t)n_images));
-        HIP_TRY(hipMalloc(&c->walk_list, contour_walk_bytes() * (size_t)n_images));
-        HIP_TRY(hipMalloc(&c->link_list, (contour_link_bytes() + sizeof(uint32_t)) * (size_t)n_images)); // + the wait list behind it
-        if (!c->walk_count) HIP_TRY(hipMalloc(&c->walk_count, 256));
-        c->cwork_images = n_images;
-    }
+    TRY(ensure_contour_work(c, n_images));
     a.work = c->cwork;
     // The split form (candidates per image -> all walks of the batch, 64 to a wave -> tree per image) is the default;
     // MOCAP_CONTOURS_SPLIT=0 runs the one-kernel-per-image form (A/B switch; same results).
@@ -964,127 +1095,90 @@ static int run_contours(mocap_ctx* c, const uint32_t* mask, const uint32_t* cell
     // launch costs up to 0.3 ms (profiles/history/r4_timeline_depth3.txt) -- or walked in place by the first tree pass (one wave per
     // link: 0.1-0.2 ms when a crowded batch holds a long one).  contour_defer = 1: deferred only once a probe found the scene crowded.
     a.defer_links = c->tune.contour_defer == 2 || (c->tune.contour_defer == 1 && c->hot_dense);
-    a.wait_list = (uint32_t*)((uint8_t*)c->link_list + contour_link_bytes() * c->cwork_images);
-    a.follow_list = 0; a.tree_pass = 0; a.follow_dbg = nullptr; a.follow_dbg_list = c->tune.follow_timing == 2 ? 1 : 0;
+    a.wait_list = (uint32_t*)((uint8_t*)c->link_list.p + contour_link_bytes() * c->cwork_images);
+    a.follow_list = 0; a.tree_pass = 0; a.follow_dbg_list = c->tune.follow_timing == 2 ? 1 : 0;
+    Buf<uint64_t> follow_dbg, timing; // debugging aids: synchronous
     if (c->tune.follow_timing && split) {
-        HIP_TRY(hipMalloc(&a.follow_dbg, sizeof(uint64_t) * 8 * a.follow_grid));
-        HIP_TRY(hipMemsetAsync(a.follow_dbg, 0, sizeof(uint64_t) * 8 * a.follow_grid, s));
+        TRY(follow_dbg.reserve((size_t)8 * a.follow_grid));
+        HIP_TRY(hipMemsetAsync(follow_dbg, 0, sizeof(uint64_t) * 8 * a.follow_grid, s));
     }
+    a.follow_dbg = follow_dbg;
     a.prio = c->tune.contour_prio; // A/B switch (no effect measured)
-    a.timing = nullptr;
-    const bool phase_timing = c->tune.contour_timing != 0;
-    if (phase_timing) { // debugging aid: synchronous, prints the mean duration of the kernel's phases
-        HIP_TRY(hipMalloc(&a.timing, sizeof(uint64_t) * 8 * n_images));
-        HIP_TRY(hipMemsetAsync(a.timing, 0, sizeof(uint64_t) * 8 * n_images, s));
+    if (c->tune.contour_timing) {
+        TRY(timing.reserve((size_t)8 * n_images));
+        HIP_TRY(hipMemsetAsync(timing, 0, sizeof(uint64_t) * 8 * n_images, s));
     }
+    a.timing = timing;
     EvPair p; bool on;
     prof_begin(c, 1, s, p, on);
     launch_contours(a, s);
     prof_end(c, 1, s, p, on);
     HIP_TRY(hipGetLastError());
-    if (a.follow_dbg) {
-        std::vector<uint64_t> t((size_t)8 * a.follow_grid);
-        HIP_TRY(hipStreamSynchronize(s));
-        HIP_TRY(hipMemcpy(t.data(), a.follow_dbg, sizeof(uint64_t) * t.size(), hipMemcpyDeviceToHost));
-        (void)hipFree(a.follow_dbg);
-        double sum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, mx[3] = {0, 0, 0}, mxsteps = 0; int used = 0;
-        for (int b = 0; b < a.follow_grid; b++) {
-            if (t[8 * b + 5] == 0) continue;
-            used++;
-            for (int i = 0; i < 8; i++) sum[i] += (double)t[8 * b + i];
-            for (int i = 0; i < 3; i++) mx[i] = (double)t[8 * b + i] > mx[i] ? (double)t[8 * b + i] : mx[i];
-            mxsteps = (double)t[8 * b + 3] > mxsteps ? (double)t[8 * b + 3] : mxsteps;
-        }
-        const double u = used ? used : 1;
-        fprintf(stderr, "[follow] %d of %d waves had work | per wave (mean / max us): store %.1f / %.1f, refill %.1f / %.1f, walk %.1f / %.1f | wave steps %.0f (max %.0f), "
-                        "lanes alive per step %.1f, walks %.1f, refills %.1f | us per wave step %.3f\n",
-                used, a.follow_grid, sum[0] / u / 100, mx[0] / 100, sum[1] / u / 100, mx[1] / 100, sum[2] / u / 100, mx[2] / 100, sum[3] / u, mxsteps,
-                sum[3] > 0 ? sum[4] / sum[3] : 0.0, sum[5] / u, sum[6] / u, sum[3] > 0 ? sum[2] / 100 / sum[3] : 0.0);
-    }
-    if (phase_timing) {
-        std::vector<uint64_t> t((size_t)8 * n_images);
-        HIP_TRY(hipStreamSynchronize(s));
-        HIP_TRY(hipMemcpy(t.data(), a.timing, sizeof(uint64_t) * t.size(), hipMemcpyDeviceToHost));
-        (void)hipFree(a.timing);
-        double sum[4] = {0, 0, 0, 0}, mx = 0; uint64_t lo = ~0ull, hi = 0;
-        for (int i = 0; i < n_images; i++) {
-            for (int k = 0; k < 4; k++) sum[k] += (double)(t[8 * i + k + 1] - t[8 * i + k]);
-            double tot = (double)(t[8 * i + 4] - t[8 * i]); mx = tot > mx ? tot : mx;
-            lo = t[8 * i] < lo ? t[8 * i] : lo; hi = t[8 * i + 4] > hi ? t[8 * i + 4] : hi;
-        }
-        {
-            int worst = 0; double wt = 0, sc = 0, ss = 0;
-            for (int i = 0; i < n_images; i++) {
-                double tot = (double)(t[8 * i + 4] - t[8 * i]);
-                if (tot > wt) { wt = tot; worst = i; }
-                sc += (double)t[8 * i + 5]; ss += (double)t[8 * i + 6];
-            }
-            fprintf(stderr, "[contours] slowest image %d: %.1f us, candidates %llu, longest border %llu steps, borders %llu | mean candidates %.1f, mean longest border %.1f steps\n",
-                    worst, wt / 100, (unsigned long long)t[8 * worst + 5], (unsigned long long)t[8 * worst + 6], (unsigned long long)t[8 * worst + 7],
-                    sc / n_images, ss / n_images);
-        }
-        fprintf(stderr, "[contours] mean us per block: candidates %.1f follow %.1f link %.1f order %.1f | slowest block %.1f | first start to last end %.1f\n",
-                sum[0] / n_images / 100, sum[1] / n_images / 100, sum[2] / n_images / 100, sum[3] / n_images / 100, mx / 100, (double)(hi - lo) / 100);
-    }
+    if (follow_dbg) TRY(report_follow_timing(follow_dbg, a.follow_grid, s));
+    if (timing) TRY(report_contour_timing(timing, n_images, s));
     return 0;
 }
 
+// The mask group (what the context's own mask needs: occupancy cells, tile boxes, hot map, work lists) for n_images images.
+static int grow_mask_group(mocap_ctx* c, size_t n_images)
+{
+    const size_t tiles = n_images * cells_per_image(c);
+    TRY(c->mask.reserve(n_images * mask_image_words(c->H, c->wpr), true));
+    TRY(c->cells.reserve(tiles, true));
+    // every tile starts with the empty box (0xffffffff, 0) and an empty recorded region (x0 = 1 > x1 = 0)
+    std::vector<uint32_t> init(tiles * 4);
+    for (size_t i = 0; i < init.size(); i += 2) { init[i] = 0xffffffffu; init[i + 1] = 0u; }
+    TRY(c->tile_rows.reserve(2 * init.size()));
+    HIP_TRY(hipMemcpy(c->tile_rows, init.data(), sizeof(uint32_t) * init.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->tile_rows + init.size(), init.data(), sizeof(uint32_t) * init.size(), hipMemcpyHostToDevice));
+    // the hot map, sized for either scan form
+    const int hw0 = hot_map_words(c->H, c->W, 0), hw1 = hot_map_words(c->H, c->W, 1);
+    TRY(c->hotmap.reserve(n_images * (hw0 > hw1 ? hw0 : hw1), true)); // all zeros between batches: the scan stores hot words only, mark_tiles_kernel clears them
+    for (size_t i = 0; i < init.size(); i++) init[i] = 1u;
+    TRY(c->cur_box.reserve(init.size()));
+    HIP_TRY(hipMemcpy(c->cur_box, init.data(), sizeof(uint32_t) * init.size(), hipMemcpyHostToDevice));
+    const size_t cap = tiles * BOX_MAX_PARTS; // settle_tiles_kernel cuts a tile into at most that many items
+    if (cap > 0xffffffffull) return fail(MOCAP_E_UNSUPPORTED, "batch too large for the work list");
+    TRY(c->items.reserve(cap));
+    return c->wide_tiles.reserve(4 * tiles); // up to 4 row bands per tile
+}
 static int ensure_mask(mocap_ctx* c, int n_images)
 {
     if ((size_t)n_images <= c->mask_images) return 0;
     std::lock_guard<std::mutex> lk(c->mu);
     if ((size_t)n_images <= c->mask_images) return 0;
-    if (c->mask) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(c->mask)); c->mask = nullptr; c->mask_images = 0; c->last_images = 0; }
-    size_t bytes = sizeof(uint32_t) * (size_t)n_images * mask_image_words(c->H, c->wpr);
-    HIP_TRY(hipMalloc(&c->mask, bytes));
-    HIP_TRY(hipMemset(c->mask, 0, bytes));
-    c->mask_images = n_images;
-    if (c->cells) { HIP_TRY(hipFree(c->cells)); c->cells = nullptr; }
-    size_t cbytes = sizeof(uint32_t) * (size_t)n_images * cells_per_image(c);
-    HIP_TRY(hipMalloc(&c->cells, cbytes));
-    HIP_TRY(hipMemset(c->cells, 0, cbytes));
-    c->cells_images = n_images;
-    if (c->tile_rows) { HIP_TRY(hipFree(c->tile_rows)); c->tile_rows = nullptr; }
-    if (c->hotmap) { HIP_TRY(hipFree(c->hotmap)); c->hotmap = nullptr; }
-    if (c->cur_box) { HIP_TRY(hipFree(c->cur_box)); c->cur_box = nullptr; }
-    if (c->items) { HIP_TRY(hipFree(c->items)); c->items = nullptr; c->cap_items = 0; }
-    if (c->wide_tiles) { HIP_TRY(hipFree(c->wide_tiles)); c->wide_tiles = nullptr; c->cap_wide = 0; }
-    {   // every tile starts with the empty box (0xffffffff, 0) and an empty recorded region (x0 = 1 > x1 = 0)
-        std::vector<uint32_t> init((size_t)n_images * cells_per_image(c) * 4);
-        for (size_t i = 0; i < init.size(); i += 2) { init[i] = 0xffffffffu; init[i + 1] = 0u; }
-        HIP_TRY(hipMalloc(&c->tile_rows, 2 * sizeof(uint32_t) * init.size()));
-        HIP_TRY(hipMemcpy(c->tile_rows, init.data(), sizeof(uint32_t) * init.size(), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c->tile_rows + init.size(), init.data(), sizeof(uint32_t) * init.size(), hipMemcpyHostToDevice));
-        c->tile_rows_flip = 0; c->tile_rows_hold[0] = c->tile_rows_hold[1] = 0;
-        // the hot map, sized for either scan form
-        const int hw0 = hot_map_words(c->H, c->W, 0), hw1 = hot_map_words(c->H, c->W, 1);
-        HIP_TRY(hipMalloc(&c->hotmap, sizeof(uint32_t) * (size_t)n_images * (hw0 > hw1 ? hw0 : hw1)));
-        HIP_TRY(hipMemset(c->hotmap, 0, sizeof(uint32_t) * (size_t)n_images * (hw0 > hw1 ? hw0 : hw1))); // all zeros between batches: the scan stores hot words only, mark_tiles_kernel clears them
-        for (size_t i = 0; i < init.size(); i++) init[i] = 1u;
-        HIP_TRY(hipMalloc(&c->cur_box, sizeof(uint32_t) * init.size()));
-        HIP_TRY(hipMemcpy(c->cur_box, init.data(), sizeof(uint32_t) * init.size(), hipMemcpyHostToDevice));
-        const size_t cap = (size_t)n_images * cells_per_image(c) * BOX_MAX_PARTS; // settle_tiles_kernel cuts a tile into at most that many items
-        if (cap > 0xffffffffull) return fail(MOCAP_E_UNSUPPORTED, "batch too large for the work list");
-        HIP_TRY(hipMalloc(&c->items, sizeof(BoxItem) * cap));
-        c->cap_items = (uint32_t)cap;
-        HIP_TRY(hipMalloc(&c->wide_tiles, sizeof(uint4) * 4 * (size_t)n_images * cells_per_image(c))); // up to 4 row bands per tile
-        c->cap_wide = (uint32_t)(4 * (size_t)n_images * cells_per_image(c));
-        c->mask_dirty = false;
+    c->mask_images = 0; c->last_images = 0;
+    if (int rc = grow_mask_group(c, n_images)) { // not half a group: the error is returned once, the next call starts over
+        c->mask.release(); c->cells.release(); c->tile_rows.release(); c->hotmap.release(); c->cur_box.release();
+        c->items.release(); c->wide_tiles.release();
+        return rc;
     }
+    c->tile_rows_flip = 0; c->tile_rows_hold[0] = c->tile_rows_hold[1] = 0;
+    c->mask_dirty = false;
+    c->mask_images = n_images;
     return 0;
 }
 
 // a zeroed mask of the internal layout for n_images (the padding rows stay zero: nothing writes them)
-static int ensure_blocked(mocap_ctx* c, uint32_t** m, size_t* images, int n_images)
+static int ensure_blocked(mocap_ctx* c, Buf<uint32_t>& m, int n_images)
 {
-    if ((size_t)n_images <= *images) return 0;
+    const size_t words = (size_t)n_images * mask_image_words(c->H, c->wpr);
+    if (words <= m.n) return 0;
     std::lock_guard<std::mutex> lk(c->mu);
-    if ((size_t)n_images <= *images) return 0;
-    if (*m) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(*m)); *m = nullptr; *images = 0; }
-    const size_t bytes = sizeof(uint32_t) * (size_t)n_images * mask_image_words(c->H, c->wpr);
-    HIP_TRY(hipMalloc(m, bytes));
-    HIP_TRY(hipMemset(*m, 0, bytes));
-    *images = n_images;
+    return m.reserve(words, true);
+}
+
+// the external group: occupancy words and tile regions of a caller-owned mask, never mixed with the context's own
+static int ensure_ext(mocap_ctx* c, int n_images)
+{
+    if ((size_t)n_images <= c->cells_ext_images) return 0;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if ((size_t)n_images <= c->cells_ext_images) return 0;
+    c->cells_ext_images = 0;
+    int rc = c->cells_ext.reserve((size_t)n_images * cells_per_image(c));
+    if (!rc) rc = c->cur_box_ext.reserve(4 * (size_t)n_images * cells_per_image(c));
+    if (rc) { c->cells_ext.release(); c->cur_box_ext.release(); return rc; }
+    c->cells_ext_images = n_images;
     return 0;
 }
 
@@ -1096,15 +1190,8 @@ int mocap_filter_mask(mocap_ctx_t c, const void* frames, int n_images, int cam_m
     if (!mask_dev) return fail(MOCAP_E_INVALID, "null mask");
     if (set_device(c)) return MOCAP_E_HIP;
     if ((rc = ensure_mask(c, n_images))) return rc; // for the tile flags
-    if ((size_t)n_images > c->cells_ext_images) { // occupancy words of a caller-owned mask: never mixed with the context's own
-        std::lock_guard<std::mutex> lk(c->mu);
-        if (c->cells_ext) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(c->cells_ext)); c->cells_ext = nullptr; c->cells_ext_images = 0; }
-        HIP_TRY(hipMalloc(&c->cells_ext, sizeof(uint32_t) * (size_t)n_images * cells_per_image(c)));
-        if (c->cur_box_ext) { HIP_TRY(hipFree(c->cur_box_ext)); c->cur_box_ext = nullptr; }
-        HIP_TRY(hipMalloc(&c->cur_box_ext, sizeof(uint32_t) * 4 * (size_t)n_images * cells_per_image(c)));
-        c->cells_ext_images = n_images;
-    }
-    if ((rc = ensure_blocked(c, &c->mask_out, &c->mask_out_images, n_images))) return rc;
+    if ((rc = ensure_ext(c, n_images))) return rc;
+    if ((rc = ensure_blocked(c, c->mask_out, n_images))) return rc;
     // filtered as a caller-owned mask (cleared by the scan, or written whole), then written whole into the caller's row-major one
     if ((rc = run_filter(c, frames, n_images, cam_mod, slot_base, image_stride, pitch, c->mask_out, c->cells_ext, (hipStream_t)stream)))
         return rc;
@@ -1122,7 +1209,7 @@ int mocap_contours_from_mask(mocap_ctx_t c, const uint32_t* mask_dev, int n_imag
         return fail(MOCAP_E_INVALID, "n_images=%d max_blobs=%d strides %ld %ld", n_images, max_blobs, xy_stride, count_stride);
     if ((dbg != nullptr) != (dbg_count != nullptr) || (dbg && dbg_cap < 1)) return fail(MOCAP_E_INVALID, "inconsistent debug buffers");
     if (set_device(c)) return MOCAP_E_HIP;
-    int rc = ensure_blocked(c, &c->mask_in, &c->mask_in_images, n_images);
+    int rc = ensure_blocked(c, c->mask_in, n_images);
     if (rc) return rc;
     launch_mask_convert(mask_dev, c->mask_in, n_images, c->H, c->wpr, true, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
@@ -1174,8 +1261,7 @@ int mocap_undistort_u8(mocap_ctx_t c, int slot, const void* src, void* dst, int 
     if (slot < 0 || slot >= c->n_slots || c->slot_state[slot] == 0) return fail(MOCAP_E_STATE, "undistort slot %d not set", slot);
     if (spitch < c->W || dpitch < c->W) return fail(MOCAP_E_INVALID, "pitch < width");
     if (set_device(c)) return MOCAP_E_HIP;
-    launch_undistort((const uint8_t*)src, (uint8_t*)dst, c->H, c->W, spitch, dpitch, c->maps + (size_t)slot * c->H * c->W,
-                     c->maps + (size_t)(c->n_slots + slot) * c->H * c->W, (hipStream_t)stream);
+    launch_undistort((const uint8_t*)src, (uint8_t*)dst, c->H, c->W, spitch, dpitch, slot_map(c, slot), slot_mapw(c, slot), (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return MOCAP_OK;
 }
@@ -1188,8 +1274,7 @@ int mocap_image_filter_u8(mocap_ctx_t c, const void* src, void* dst, int spitch,
     if (slot >= c->n_slots || (slot >= 0 && c->slot_state[slot] == 0)) return fail(MOCAP_E_STATE, "undistort slot %d not set", slot);
     if (set_device(c)) return MOCAP_E_HIP;
     hipStream_t s = (hipStream_t)stream;
-    double ft = floor(c->prm.thresh);
-    int ithresh = ft < -1.0 ? -1 : (ft > 255.0 ? 255 : (int)ft);
+    const int thr_mul = threshold_mul(c), ithresh = thr_mul - 1;
     if (order == 1) {
         const uint8_t* in = (const uint8_t*)src;
         int ip = spitch;
@@ -1203,16 +1288,7 @@ int mocap_image_filter_u8(mocap_ctx_t c, const void* src, void* dst, int spitch,
     int rc = ensure_mask(c, 1);
     if (rc) return rc;
     // the general kernel with a one-image batch; slot < 0 = no undistortion
-    FilterArgs a;
-    a.src = (const uint8_t*)src; a.image_stride = 0; a.pitch = spitch; a.H = c->H; a.W = c->W;
-    a.mask = c->mask; a.words_per_row = c->wpr; a.cam_mod = 1; a.n_images = 1; a.n_steps = 1;
-    a.cells = c->cells;
-    a.map = slot >= 0 ? c->maps + (size_t)slot * c->H * c->W : nullptr;
-    a.mapw = slot >= 0 ? c->maps + (size_t)(c->n_slots + slot) * c->H * c->W : nullptr;
-    a.thr_mul = ithresh + 1;
-    Tiling tl = tiling(c);
-    a.n_strips = tl.n_strips; a.rows_per_chunk = tl.rows; a.n_cgroups = tl.n_cgroups;
-    a.pipelined = c->W >= 4 && (c->W & 3) == 0 && c->H >= 2;
+    const FilterArgs a = filter_args(c, src, 0, spitch, c->mask, c->cells, slot, 1, 1, thr_mul);
     c->mask_dirty = true; c->last_images = 1;
     launch_filter_mask(a, slot >= 0 && c->slot_state[slot] == 2, s);
     HIP_TRY(hipGetLastError());
@@ -1302,10 +1378,8 @@ int mocap_comm_init(mocap_ctx_t c, const void* id, int rank, int world)
     IdBytes idb;
     memcpy(idb.internal, id, sizeof(idb.internal));
     int r_ = g_rccl.CommInitRank(&sc->comm, world, idb, rank);
-    if (r_ != 0) {
-        (void)hipEventDestroy(sc->last);
+    if (r_ != 0) // (~SharedComm destroys the event: one owner)
         return fail(MOCAP_E_HIP, "ncclCommInitRank failed: %s", g_rccl.GetErrorString(r_));
-    }
     sc->rank = rank; sc->world = world; sc->device = c->device;
     sc->destroy_comm = [](void* comm) { return g_rccl.lib && g_rccl.CommDestroy(comm) == 0; };
     c->comm = sc;
@@ -1377,11 +1451,9 @@ int mocap_correspond(mocap_ctx_t c, const void* pts, long pt_st, long pt_sc, con
     if (budget > (size_t)P * max_groups) budget = (size_t)P * max_groups;
     if (budget > 0x7fffffff) budget = 0x7fffffff;
     size_t need = (size_t)T * budget;
-    if (need > c->scratch_elems) {
+    if (need > c->scratch.n) {
         std::lock_guard<std::mutex> lk(c->mu);
-        if (c->scratch) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(c->scratch)); c->scratch = nullptr; c->scratch_elems = 0; }
-        HIP_TRY(hipMalloc(&c->scratch, sizeof(double) * need));
-        c->scratch_elems = need;
+        TRY(c->scratch.reserve(need));
     }
     CorrArgs a;
     a.cams = c->cams; a.pts = pts; a.counts = counts; a.pts_f64 = pts_f64; a.T = T; a.C = C; a.P = P;
@@ -1421,17 +1493,10 @@ int mocap_ba_residuals(mocap_ctx_t c, const double* params_host, int B, const do
     std::lock_guard<std::mutex> lk(c->mu);
     const size_t np_ = (size_t)B * 6 * (C - 1), pbytes = (sizeof(double) * np_ + 15) & ~(size_t)15;
     const size_t rbytes = (sizeof(float) * (size_t)B * N + 15) & ~(size_t)15, need = pbytes + rbytes + sizeof(int32_t) * B;
-    if (need > c->ba_pinned_bytes) {
-        if (c->ba_pinned) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipHostFree(c->ba_pinned)); c->ba_pinned = nullptr; c->ba_pinned_bytes = 0; }
-        HIP_TRY(hipHostMalloc(&c->ba_pinned, need * 2));
-        c->ba_pinned_bytes = need * 2;
-    }
-    if ((size_t)B * N * 3 > c->ba_obj_elems) {
-        if (c->ba_obj) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(c->ba_obj)); c->ba_obj = nullptr; c->ba_obj_elems = 0; }
-        HIP_TRY(hipMalloc(&c->ba_obj, sizeof(double) * (size_t)B * N * 3 * 2));
-        c->ba_obj_elems = (size_t)B * N * 3 * 2;
-    }
-    char* const pin = (char*)c->ba_pinned;
+    // (grown to twice what the call needs: a series of growing calls allocates a few times, not every time)
+    if (need > c->ba_pinned.n) TRY(c->ba_pinned.reserve(need * 2));
+    if ((size_t)B * N * 3 > c->ba_obj.n) TRY(c->ba_obj.reserve((size_t)B * N * 3 * 2));
+    char* const pin = c->ba_pinned;
     memcpy(pin, params_host, sizeof(double) * np_);
     BaArgs a{c->cams, (const double*)pin, pts, valid, N, C, B, c->ba_obj, (float*)(pin + pbytes), (int32_t*)(pin + pbytes + rbytes)};
     launch_ba_residuals(a, (hipStream_t)stream);
@@ -1465,12 +1530,8 @@ int mocap_fundamental_ransac(mocap_ctx_t c, int n_pairs, const double* pts_a, co
     const size_t nh = (size_t)n_pairs * H, f_bytes = sizeof(double) * 9 * nh, cnt_bytes = (sizeof(int32_t) * nh + 15) & ~(size_t)15;
     const size_t err_bytes = (sizeof(int32_t) * n_pairs + 15) & ~(size_t)15, off_bytes = sizeof(int32_t) * ((size_t)n_pairs + 1);
     const size_t need = f_bytes + cnt_bytes + err_bytes + off_bytes;
-    if (need > c->fund_scratch_bytes) {
-        if (c->fund_scratch) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(c->fund_scratch)); c->fund_scratch = nullptr; c->fund_scratch_bytes = 0; }
-        HIP_TRY(hipMalloc(&c->fund_scratch, need * 2));
-        c->fund_scratch_bytes = need * 2;
-    }
-    char* const base = (char*)c->fund_scratch;
+    if (need > c->fund_scratch.n) TRY(c->fund_scratch.reserve(need * 2));
+    char* const base = c->fund_scratch;
     int32_t* const cnt_own = (int32_t*)(base + f_bytes);
     int32_t* const pair_err = (int32_t*)(base + f_bytes + cnt_bytes);
     int32_t* const offset_dev = (int32_t*)(base + f_bytes + cnt_bytes + err_bytes);
