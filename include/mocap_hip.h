@@ -255,6 +255,53 @@ MOCAP_API int mocap_fundamental_ransac(mocap_ctx_t ctx, int n_pairs, const doubl
                                        int refit, double* F_sample_dev, double* F_refit_dev, uint8_t* inlier_dev,
                                        int32_t* status_dev, int32_t* counts_dev, void* stream);
 
+/* Bundle adjustment of a whole rig: the poses of cameras 1..C-1 and all N 3-D points, over exactly the observations that
+ * exist, by sparse Levenberg-Marquardt on the device (Schur complement on the points, analytic Jacobian, Nielsen's damping
+ * rule; FP64 throughout; definition in DESIGN.md section 2, restated by tests/rig_ba_ref.py).  Generalises the interface of
+ * lib/Helpers.py:158-176 (bundle_adjustment: two cameras, SciPy over 6 parameters, points every camera must have seen); the
+ * reference has no N-camera counterpart.  Both entries were added without a change to any existing one, so
+ * MOCAP_ABI_VERSION stays 7: a caller built against the earlier header runs unchanged.
+ *   C, N, n_obs           2..32 cameras, N points, n_obs observations
+ *   obs_offset_dev        int32 [N + 1]: point n owns observations obs_offset[n] .. obs_offset[n + 1] - 1; obs_offset[0] = 0,
+ *                         obs_offset[N] = n_obs; every point has 2..C observations
+ *   obs_cam_dev           int32 [n_obs]: the TRUE camera number of each observation (K and dist of mocap_set_cameras are
+ *                         indexed with it), strictly ascending within a point
+ *   obs_uv_dev            float64 [n_obs][2] pixels, distorted as the camera delivers them
+ *   poses_dev             float64 [C][12] in / out: R row-major then t, world -> camera; camera 0 is taken as identity, zero
+ *   points_dev            float64 [N][3] in / out
+ *   max_iters, ftol, lambda0  the stopping rules and the first damping (50, 1e-12, 1e-3 in the Python surface)
+ *   history_dev           float64 [max_iters][4], one row per iteration done: cost after it, the lambda it was solved with,
+ *                         1 = accepted, length of the step; rows of iterations not done are zero
+ *   result_dev            float64 [4]: status, iterations done, cost of the state handed in, final cost (1/2 sum r^2).
+ *                         status > 0 names the rule that stopped the loop (MOCAP_RIG_STOP_*); status < 0 (MOCAP_RIG_E_*):
+ *                         poses_dev and points_dev are left as they were.  Nothing is ever returned silently wrong
+ * On return every t and every point is scaled so that |t_1| is what it was on entry (the scale is free while iterating).
+ * Asynchronous on `stream`: all max_iters iterations are enqueued, the kernels of the iterations after the stop return at
+ * once, and no array of the iteration crosses to the host.  No floating-point atomics: the same call gives the same bits.
+ * The scratch belongs to the context and grows on demand: calls on one context must be ordered on one stream. */
+enum {
+    MOCAP_RIG_STOP_MAX_ITERS = 1, /* max_iters iterations done */
+    MOCAP_RIG_STOP_FTOL = 2,      /* an accepted step lowered the cost by less than ftol, relatively */
+    MOCAP_RIG_STOP_LAMBDA = 3,    /* the damping grew beyond 1e16 */
+    MOCAP_RIG_STOP_CHOLESKY = 4,  /* the reduced camera matrix was not positive definite twice in a row (once: the step counts as rejected) */
+    MOCAP_RIG_E_LAYOUT = -2,      /* the observation arrays break one of the rules above */
+    MOCAP_RIG_E_BEHIND = -3       /* in the state handed in, a point is not in front of a camera that sees it, or the cost is not finite */
+};
+MOCAP_API int mocap_rig_bundle_adjust(mocap_ctx_t ctx, int C, int N, int n_obs, const int32_t* obs_offset_dev,
+                                      const int32_t* obs_cam_dev, const double* obs_uv_dev, double* poses_dev, double* points_dev,
+                                      int max_iters, double ftol, double lambda0, double* history_dev, double* result_dev,
+                                      void* stream);
+/* The pieces of one iteration of mocap_rig_bundle_adjust at a given state and damping, for tests and tuning (the residual
+ * and Jacobian of lib/Helpers.py:158-176's problem, generalised as above, in normal-equation form): cost_dev [1] = 1/2 sum
+ * r^2; gradient_dev [6 (C - 1) + 3 N] = J^T r (cameras 1.., 6 each: rotation, translation; then the points);
+ * S_dev [6 (C - 1)][6 (C - 1)] the damped reduced camera matrix U* - sum_n W_n V*_n^-1 W_n^T; rhs_dev [6 (C - 1)] the
+ * reduced right-hand side -g_c + sum_n W_n V*_n^-1 g_n; status_dev int32 [2] = (layout error, a point not in front of a
+ * camera that sees it), both 0 when all is well.  poses_dev and points_dev are only read.  Asynchronous on `stream`. */
+MOCAP_API int mocap_rig_linearize(mocap_ctx_t ctx, int C, int N, int n_obs, const int32_t* obs_offset_dev,
+                                  const int32_t* obs_cam_dev, const double* obs_uv_dev, const double* poses_dev,
+                                  const double* points_dev, double lambda, double* cost_dev, double* gradient_dev, double* S_dev,
+                                  double* rhs_dev, int32_t* status_dev, void* stream);
+
 /* The path's one exchange step: with the cameras sharded over GPUs (one process per GPU), every rank
  * contributes the fixed-size centroid records of its images and receives all ranks' records, in rank order, before
  * correspondence -- one ncclAllGather (RCCL over xGMI) per batch.  The reference has no counterpart: its camera

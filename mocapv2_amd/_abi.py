@@ -60,6 +60,8 @@ SIGNATURES = {
     "mocap_epipolar_scores": [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp],
     "mocap_ba_residuals": [_vp, _dp, _i, _vp, _vp, _i, _i, C.POINTER(C.c_float), _ip, _vp],
     "mocap_fundamental_ransac": [_vp, _i, _vp, _vp, _ip, _vp, _i, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp],
+    "mocap_rig_bundle_adjust": [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _d, _d, _vp, _vp, _vp],
+    "mocap_rig_linearize": [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp, _vp, _vp],
     "mocap_triangulate_batch": [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp],
     "mocap_reproject_batch": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp],
     "mocap_comm_unique_id": [_vp],

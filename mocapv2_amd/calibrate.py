@@ -14,6 +14,9 @@ What is batched that the reference loops over:
     camera) is ONE triangulation launch + ONE reprojection launch over 7 N groups instead of 6 x 2 x N Python calls;
     steps and rounding are SciPy's, so the optimiser walks the same iterates as the reference's
     `least_squares(..., jac='2-point')`.
+Beyond the reference (whose calibration is two-camera at heart): `calibrate_rig` = `rig_initial_poses` (all camera pairs'
+fundamental matrices in one RANSAC call, a spanning tree with a common scale) + `bundle_adjust_rig` (all poses and all points
+on the GPU over exactly the observations that exist, csrc/rig_ba.hip; definition in DESIGN.md section 2).
 Image capture and the plotting / JSON writing of that script are outside the path.  `calculate_extrinsics` is the
 script's function of that name (:162-255) from image points to poses; the pieces still take fundamental matrices as
 arguments.
@@ -264,6 +267,216 @@ def extrinsics_from_fundamentals(image_points, Fs, camera_params, ctx=None):
     return poses
 
 
+# ---- the whole rig: initial poses over a spanning tree, then bundle adjustment on the GPU ------------------------------------
+def undistort_points(pts, K, dist, normalized=False):
+    """`cv.undistortPoints(pts, K, dist, P=K)` on the host: the pinhole pixel each distorted pixel [..., 2] would have, by
+    cv2's fixed-point iteration (5 rounds) on the Brown model.  normalized=True: the normalised coordinates (cv2 without P).
+    Only the rig path uses it, for the linear steps of its initialisation (fundamental matrices, triangulation), which know
+    no distortion; the bundle adjustment itself works on the distorted pixels."""
+    pts = np.asarray(pts, float)
+    K = np.asarray(K, float).reshape(3, 3)
+    k1, k2, p1, p2, k3 = np.asarray(dist, float).ravel()[:5]
+    x0, y0 = (pts[..., 0] - K[0, 2]) / K[0, 0], (pts[..., 1] - K[1, 2]) / K[1, 1]
+    x, y = x0, y0
+    for _ in range(5):
+        r2 = x * x + y * y
+        icd = 1.0 / (1 + ((k3 * r2 + k2) * r2 + k1) * r2)
+        dx, dy = 2 * p1 * x * y + p2 * (r2 + 2 * x * x), p1 * (r2 + 2 * y * y) + 2 * p2 * x * y
+        x, y = (x0 - dx) * icd, (y0 - dy) * icd
+    if normalized:
+        return np.stack([x, y], -1)
+    return np.stack([K[0, 0] * x + K[0, 2], K[1, 1] * y + K[1, 2]], -1)
+
+
+def _rig_inputs(image_points, valid, camera_params):
+    ip = np.asarray(image_points, float)
+    if ip.ndim != 3 or ip.shape[2] != 2 or not 2 <= ip.shape[0] <= 32:
+        raise ValueError(f"image_points must be [2..32 cameras][N][2], got {ip.shape}")
+    Cn, N = ip.shape[:2]
+    vis = np.ones((Cn, N), bool) if valid is None else np.asarray(valid).astype(bool).reshape(Cn, N)
+    if len(camera_params) < Cn:
+        raise ValueError(f"{Cn} cameras but {len(camera_params)} sets of camera parameters (they are indexed by camera number)")
+    if not np.isfinite(ip[vis]).all():
+        raise ValueError("image points marked valid must be finite")
+    K, d = _intrinsics(camera_params, Cn)
+    return np.where(vis[..., None], ip, 0.0), vis, K, d
+
+
+def rig_initial_poses(image_points, valid, camera_params, threshold=10.0, hypotheses=1000, seed=0, ctx=None, details=False):
+    """Consistent initial poses for every camera of a rig, camera 0 at the origin.  (The reference chains consecutive cameras
+    link by link, CalculateCameraPoses.py:166-235, each link with a translation of length 1: for more than two cameras the
+    chain has no common scale.)  image_points [C][N][2] distorted pixels, valid [C][N], camera_params indexed by camera.
+      1. every camera pair with >= 8 common points: fundamental matrix by ONE batched GPU RANSAC (`find_fundamental_matrices`)
+         on undistorted points;
+      2. maximum spanning tree over the inlier counts from camera 0 (Prim; on a tie the lowest camera index, then the lowest
+         parent index);
+      3. per tree edge a -> b, breadth first: E = K_b^T F K_a, `decompose_essential`, the four candidates triangulated in one
+         launch, the winner has strictly the most inliers in front of BOTH cameras (first on ties); R_b = R_ab R_a,
+         t_b = R_ab t_a + s t_ab with s = 1 on the first edge and afterwards the median, over the edge's inliers that at least
+         two cameras posed so far see, of (depth in camera a of the point triangulated from those cameras) / (its depth in
+         the unit-baseline triangulation of the edge).
+    Raises ValueError naming the camera when the graph is disconnected or no common point fixes a scale.  Returns the list
+    of poses {"R": 3x3, "t": 3x1}; details=True: (poses, dict with tree [(a, b)], inliers, scales, votes)."""
+    ip, vis, K, d = _rig_inputs(image_points, valid, camera_params)
+    ctx = ctx or default_context()
+    Cn, N = vis.shape
+    und = np.stack([undistort_points(ip[c], K[c], d[c]) for c in range(Cn)])
+    pairs = [(a, b) for a in range(Cn) for b in range(a + 1, Cn) if int((vis[a] & vis[b]).sum()) >= 8]
+    res = find_fundamental_matrices(und, pairs, vis, threshold, hypotheses, seed, True, ctx, details=True) if pairs else []
+    weight = np.zeros((Cn, Cn), np.int64)
+    found = {}
+    for (a, b), (F, mask, r) in zip(pairs, res):
+        if F is not None:
+            weight[a, b] = weight[b, a] = r["n_inliers"]
+            found[(a, b)] = (np.asarray(r["F_refit"], float), mask[:, 0].astype(bool))
+    parent = {0: None}
+    while len(parent) < Cn:  # Prim
+        best = None
+        for b in range(Cn):
+            if b in parent:
+                continue
+            for a in sorted(parent):
+                if weight[a, b] > 0 and (best is None or weight[a, b] > best[0]):
+                    best = (weight[a, b], a, b)
+        if best is None:
+            missing = [c for c in range(Cn) if c not in parent]
+            raise ValueError(f"camera {missing[0]} shares no fundamental matrix (>= 8 common points, RANSAC succeeded) with the "
+                             f"cameras connected to camera 0; not connected: {missing}")
+        parent[best[2]] = best[1]
+    edges, queue = [], [0]
+    while queue:  # breadth first, children in ascending order
+        a = queue.pop(0)
+        for b in sorted(c for c, p in parent.items() if p == a):
+            edges.append((a, b))
+            queue.append(b)
+    R = {0: np.eye(3)}
+    t = {0: np.zeros(3)}
+    info = {"tree": edges, "inliers": [], "scales": [], "votes": []}
+    for k, (a, b) in enumerate(edges):
+        F, inl = found[(a, b)] if a < b else found[(b, a)]
+        F_ab = F if a < b else F.T
+        R1, R2, tu = decompose_essential(K[b].T @ F_ab @ K[a])
+        tu = tu.reshape(3)
+        cand = [(R1, tu), (R1, -tu), (R2, tu), (R2, -tu)]
+        idx = np.flatnonzero(inl)
+        n = len(idx)
+        # relative frame: camera a at the origin (slot 0), the four candidates for camera b in slots 1..4; group (i, point)
+        ctx.set_cameras(np.array([K[a]] + [K[b]] * 4), np.zeros((5, 5)), np.array([np.eye(3)] + [c[0] for c in cand]),
+                        np.array([np.zeros(3)] + [c[1] for c in cand]))
+        pts = np.zeros((4 * n, 5, 2))
+        val = np.zeros((4 * n, 5), np.uint8)
+        for i in range(4):
+            pts[i * n:(i + 1) * n, 0], pts[i * n:(i + 1) * n, 1 + i] = und[a][idx], und[b][idx]
+            val[i * n:(i + 1) * n, 0] = val[i * n:(i + 1) * n, 1 + i] = 1
+        xyz, ok = ctx.triangulate_batch(pts, val, compact_k=False)
+        xyz, ok = xyz.reshape(4, n, 3), ok.reshape(4, n).astype(bool)
+        votes = [int((ok[i] & (xyz[i][:, 2] > 0) & ((xyz[i] @ cand[i][0].T + cand[i][1])[:, 2] > 0)).sum()) for i in range(4)]
+        win = int(np.argmax(votes))  # the first of equal maxima
+        if votes[win] == 0:
+            raise ValueError(f"camera {b}: no candidate pose places a point in front of cameras {a} and {b}")
+        R_ab, t_ab = cand[win]
+        s = 1.0
+        if k > 0:
+            posed = sorted(R)
+            seen = vis[posed][:, idx].sum(0) >= 2
+            if not seen.any():
+                raise ValueError(f"camera {b}: no inlier of the pair {a} -> {b} is seen by two cameras posed before it; its scale is free")
+            Kp, dp_ = np.array([K[c] for c in posed]), np.zeros((len(posed), 5))
+            ctx.set_cameras(Kp, dp_, np.array([R[c] for c in posed]), np.array([t[c] for c in posed]))
+            sel = idx[seen]
+            g = np.ascontiguousarray(np.transpose(und[posed][:, sel], (1, 0, 2)))
+            Xw, okw = ctx.triangulate_batch(g, vis[posed][:, sel].T.astype(np.uint8), compact_k=False)
+            depth_w = (Xw @ R[a].T + t[a])[:, 2]
+            depth_r = xyz[win][seen][:, 2]
+            good = okw.astype(bool) & ok[win][seen] & (depth_w > 0) & (depth_r > 0)
+            if not good.any():
+                raise ValueError(f"camera {b}: no common point in front of camera {a} fixes the scale of the edge {a} -> {b}")
+            s = float(np.median(depth_w[good] / depth_r[good]))
+        R[b] = R_ab @ R[a]
+        t[b] = R_ab @ t[a] + s * t_ab
+        info["inliers"].append(n)
+        info["scales"].append(s)
+        info["votes"].append(votes)
+    poses = [{"R": R[c], "t": t[c].reshape(3, 1)} for c in range(Cn)]
+    return (poses, info) if details else poses
+
+
+def bundle_adjust_rig(image_points, valid, poses, camera_params, points=None, max_iters=50, ftol=1e-12, ctx=None):
+    """Bundle adjustment of ALL cameras of a rig and all 3-D points on the GPU, over exactly the observations that exist
+    (engine.MocapContext.rig_bundle_adjust -> mocap_rig_bundle_adjust; definition in DESIGN.md section 2).  The reference's
+    `bundle_adjustment` (lib/Helpers.py:158-176) refines camera 1 of two and drops every point a camera missed; it stays
+    available unchanged.  image_points [C][N][2] distorted pixels, valid [C][N], poses: C poses {"R", "t"} to start from
+    (`rig_initial_poses`), camera_params indexed by camera; points [N][3]: start points (None: triangulated from the start
+    poses on undistorted pixels).  Residuals use the full Brown model of each camera, in FP64.  Camera 0 keeps its pose;
+    the scale is fixed by |t_1 - R_1 R_0^T t_0|, the distance the start poses put between cameras 0 and 1.
+    Returns dict: poses (list of {"R": 3x3, "t": 3x1}), points [N][3] (NaN where not used), used [N] bool (False: fewer than
+    two views, or no start point in front of its cameras), cost_initial, cost (1/2 sum r^2), rms_px (per coordinate),
+    iterations, history [iterations][4] (cost, lambda, accepted, |step|), status (MOCAP_RIG_STOP_*: 1 max_iters, 2 ftol,
+    3 lambda, 4 Cholesky), mirrored (the start had every point behind every camera and was adjusted as its mirror image,
+    see below)."""
+    ip, vis, K, d = _rig_inputs(image_points, valid, camera_params)
+    Cn, N = vis.shape
+    if len(poses) != Cn:
+        raise ValueError(f"{len(poses)} poses for {Cn} cameras")
+    ctx = ctx or default_context()
+    Rw = np.array([np.asarray(p["R"], float).reshape(3, 3) for p in poses])
+    tw = np.array([np.asarray(p["t"], float).reshape(3) for p in poses])
+    # the device works with camera 0 as the world frame
+    R0, t0 = Rw[0].copy(), tw[0].copy()
+    R = np.array([Rw[c] @ R0.T for c in range(Cn)])
+    t = np.array([tw[c] - R[c] @ t0 for c in range(Cn)])
+    R[0], t[0] = np.eye(3), 0.0
+    used = vis.sum(0) >= 2
+    if points is None:
+        und = np.stack([undistort_points(ip[c], K[c], d[c]) for c in range(Cn)])
+        ctx.set_cameras(K, d, R, t)
+        X, ok = ctx.triangulate_batch(np.ascontiguousarray(np.transpose(und, (1, 0, 2))), vis.T.astype(np.uint8), compact_k=False)
+        used &= ok.astype(bool)
+    else:
+        X = np.asarray(points, float).reshape(N, 3) @ R0.T + t0
+    with np.errstate(invalid="ignore"):
+        depth = np.array([(X @ R[c].T + t[c])[:, 2] for c in range(Cn)])
+        # (R, -t, -X) projects like (R, t, X) with every depth negated.  A start with EVERY point behind EVERY camera that sees
+        # it is that mirror image of a proper one (the reference's candidate vote produces it for its bundled capture): it is
+        # adjusted as its mirror image and handed back mirrored again, in the caller's convention.
+        mirror = bool(used.any() and (depth[:, used][vis[:, used]] < 0).all())
+        if mirror:
+            t, X, depth = -t, -X, -depth
+        front = ((depth > 0) | ~vis).all(0)
+    used &= front & np.isfinite(X).all(1)
+    if not used.any():
+        raise ValueError("no point with two views and a start position in front of its cameras")
+    sel = np.flatnonzero(used)
+    v = vis[:, sel]
+    n_idx, c_idx = np.nonzero(v.T)  # point-major, cameras ascending
+    offset = np.zeros(len(sel) + 1, np.int32)
+    np.cumsum(v.sum(0), out=offset[1:])
+    uv = ip[c_idx, sel[n_idx]]
+    ctx.set_cameras(K, d, R, t)
+    out = ctx.rig_bundle_adjust(offset, c_idx.astype(np.int32), uv, np.c_[R.reshape(Cn, 9), t], X[sel], max_iters, ftol)
+    Rn, tn, Xn = out["poses"][:, :9].reshape(Cn, 3, 3), out["poses"][:, 9:], out["points"]
+    if mirror:
+        tn, Xn = -tn, -Xn
+    pts = np.full((N, 3), np.nan)
+    pts[sel] = (Xn - t0) @ R0  # back to the caller's world frame
+    new = [{"R": Rn[c] @ R0, "t": (tn[c] + Rn[c] @ t0).reshape(3, 1)} for c in range(Cn)]
+    return {"poses": new, "points": pts, "used": used, "cost_initial": out["cost_initial"], "cost": out["cost"],
+            "rms_px": float(np.sqrt(out["cost"] / len(uv))), "iterations": out["iterations"], "history": out["history"],
+            "status": out["status"], "mirrored": mirror}
+
+
+def calibrate_rig(image_points, valid, camera_params, threshold=10.0, hypotheses=1000, seed=0, max_iters=50, ftol=1e-12, ctx=None):
+    """From the wand points of a whole rig to its extrinsics: `rig_initial_poses`, then `bundle_adjust_rig`.  The N-camera
+    counterpart of `calculate_extrinsics` (which keeps the reference's two-camera behaviour).  Returns `bundle_adjust_rig`'s
+    dict plus poses_initial and init (the initialisation's details); its poses and points go to `set_origin`, `set_floor` and
+    `save_extrinsics` as the reference's do."""
+    ctx = ctx or default_context()
+    initial, info = rig_initial_poses(image_points, valid, camera_params, threshold, hypotheses, seed, ctx, details=True)
+    out = bundle_adjust_rig(image_points, valid, initial, camera_params, None, max_iters, ftol, ctx)
+    out["poses_initial"], out["init"] = initial, info
+    return out
+
+
 # ---- bundle adjustment: residual and Jacobian in batched launches ---------------------------------------------------
 def residuals_batched(image_points, param_sets, camera_params, ctx=None, problem=None):
     """Residual vectors (per-point reprojection MSE, float32 -- reference lib/Helpers.py:161-167) of S parameter
@@ -470,4 +683,5 @@ __all__ = ["poses_to_fundamental_matrix", "decompose_essential", "select_relativ
            "residuals_batched", "forward_difference_steps", "residual_and_jacobian", "bundle_adjustment", "set_origin",
            "calculate_normal", "rotation_matrix_from_vectors", "set_floor", "get_points", "save_extrinsics", "save_objects",
            "save_fundamentals", "pair_fundamentals", "sample_table", "find_fundamental_matrix", "find_fundamental_matrices",
-           "tracker_fundamentals", "calculate_extrinsics"]
+           "tracker_fundamentals", "calculate_extrinsics", "undistort_points", "rig_initial_poses", "bundle_adjust_rig",
+           "calibrate_rig"]

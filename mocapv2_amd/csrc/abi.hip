@@ -226,6 +226,7 @@ struct mocap_ctx {
     Buf<double> scratch;                   // error scratch of mocap_correspond
     Buf<double> ba_obj;                    // object points of mocap_ba_residuals, [B][N][3]
     Buf<char> fund_scratch;                // mocap_fundamental_ransac: every hypothesis' matrix, the counters, the pair offsets
+    Buf<char> rig_scratch;                 // mocap_rig_bundle_adjust / mocap_rig_linearize: the state record, both state buffers, the blocks and partial sums
     Buf<char, true> ba_pinned;             // mocap_ba_residuals' host-side hand-over: parameters in, residuals + counts out (the kernel reads / writes it directly)
     std::shared_ptr<struct SharedComm> comm; // RCCL communicator of mocap_comm_init / mocap_comm_share, else null
     bool profiling = false;
@@ -1543,6 +1544,91 @@ int mocap_fundamental_ransac(mocap_ctx_t c, int n_pairs, const double* pts_a, co
     FundArgs a{pts_a, pts_b, offset_dev, samples, n_pairs, H, max_n, threshold * threshold, (double*)base, counts ? counts : cnt_own,
                pair_err, F_sample, refit ? F_refit : nullptr, inlier, status};
     launch_fundamental_ransac(a, s);
+    HIP_TRY(hipGetLastError());
+    return MOCAP_OK;
+}
+
+// The scratch of a rig bundle adjustment, carved out of one block the context owns (grown to twice what a call needs).  The
+// partition depends on the problem's sizes alone, never on the block's: a call's results do not depend on earlier calls.
+static int rig_args(mocap_ctx* c, int C, int N, int n_obs, const int32_t* obs_offset, const int32_t* obs_cam, const double* obs_uv,
+                    double* poses, double* points, RigArgs& a)
+{
+    if (C < 2 || C > 32 || N < 1 || N > (1 << 24) || n_obs < 2 * (long long)N || n_obs > (long long)N * C)
+        return fail(MOCAP_E_INVALID, "C=%d N=%d n_obs=%d: 2..32 cameras, 1..2^24 points, 2..C observations per point", C, N, n_obs);
+    if (c->n_cam < C) return fail(MOCAP_E_STATE, "mocap_set_cameras: %d cameras set, %d needed (their K and dist are used)", c->n_cam, C);
+    a = RigArgs{};
+    a.cams = c->cams; a.obs_offset = obs_offset; a.obs_cam = obs_cam; a.obs_uv = obs_uv; a.C = C; a.N = N; a.n_obs = n_obs;
+    a.n_pairs = (C - 1) * C / 2; a.n_lin_blocks = rig_lin_blocks(N); a.n_chunks = rig_schur_chunks(N);
+    a.poses_io = poses; a.points_io = points;
+    const size_t D = 6 * (size_t)(C - 1);
+    size_t used = 0;
+    auto take = [&used](size_t bytes) { const size_t at = used; used += (bytes + 15) & ~(size_t)15; return at; };
+    const size_t o_state = take(sizeof(RigState)), o_poses = take(8 * 2 * 12 * (size_t)C), o_points = take(8 * 2 * 3 * (size_t)N);
+    const size_t o_mask = take(4 * (size_t)N), o_W = take(8 * 18 * (size_t)n_obs), o_Vinv = take(8 * 6 * (size_t)N);
+    const size_t o_vdiag = take(8 * 3 * (size_t)N), o_gp = take(8 * 3 * (size_t)N);
+    const size_t o_lin = take(8 * 27 * (size_t)a.n_lin_blocks * (C - 1)), o_cost = take(8 * (size_t)a.n_lin_blocks);
+    const size_t o_schur = take(8 * 42 * (size_t)a.n_chunks * a.n_pairs), o_S = take(8 * D * D), o_rhs = take(8 * D), o_gc = take(8 * D);
+    const size_t o_udiag = take(8 * D), o_chol = take(8 * D * (D + 1) / 2), o_delta = take(8 * D);
+    const size_t o_upd = take(8 * 3 * (size_t)a.n_lin_blocks), o_scal = take(8 * RIG_N_SCALARS);
+    if (used > c->rig_scratch.n) TRY(c->rig_scratch.reserve(used * 2));
+    char* const b = c->rig_scratch;
+    a.state = (RigState*)(b + o_state); a.poses = (double*)(b + o_poses); a.points = (double*)(b + o_points);
+    a.mask = (uint32_t*)(b + o_mask); a.W = (double*)(b + o_W); a.Vinv = (double*)(b + o_Vinv); a.vdiag = (double*)(b + o_vdiag);
+    a.gp = (double*)(b + o_gp); a.lin_part = (double*)(b + o_lin); a.cost_part = (double*)(b + o_cost);
+    a.schur_part = (double*)(b + o_schur); a.S = (double*)(b + o_S); a.rhs = (double*)(b + o_rhs); a.gc = (double*)(b + o_gc);
+    a.udiag = (double*)(b + o_udiag); a.chol = (double*)(b + o_chol); a.delta_c = (double*)(b + o_delta);
+    a.upd_part = (double*)(b + o_upd); a.scalars = (double*)(b + o_scal);
+    return 0;
+}
+
+int mocap_rig_linearize(mocap_ctx_t c, int C, int N, int n_obs, const int32_t* obs_offset, const int32_t* obs_cam, const double* obs_uv,
+                        const double* poses, const double* points, double lambda, double* cost, double* gradient, double* S,
+                        double* rhs, int32_t* status, void* stream)
+{
+    if (!c || !obs_offset || !obs_cam || !obs_uv || !poses || !points || !cost || !gradient || !S || !rhs || !status)
+        return fail(MOCAP_E_INVALID, "null argument");
+    if (!(lambda >= 0.0) || !(lambda <= 1e300)) return fail(MOCAP_E_INVALID, "lambda = %g", lambda);
+    if (set_device(c)) return MOCAP_E_HIP;
+    std::lock_guard<std::mutex> lk(c->mu);
+    RigArgs a;
+    // (the state handed in is only read: the init kernel copies it, no finish kernel runs)
+    TRY(rig_args(c, C, N, n_obs, obs_offset, obs_cam, obs_uv, const_cast<double*>(poses), const_cast<double*>(points), a));
+    hipStream_t s = (hipStream_t)stream;
+    const size_t D = 6 * (size_t)(C - 1);
+    HIP_TRY(hipMemsetAsync(a.state, 0, sizeof(RigState), s));
+    launch_rig_init(a, lambda, s);
+    launch_rig_linearize(a, s);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(cost, a.scalars + RIG_LIN_COST, 8, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(gradient, a.gc, 8 * D, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(gradient + D, a.gp, 8 * 3 * (size_t)N, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(S, a.S, 8 * D * D, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(rhs, a.rhs, 8 * D, hipMemcpyDeviceToDevice, s));
+    // status: (layout error, a point not in front of a camera that sees it)
+    HIP_TRY(hipMemcpyAsync(status, &a.state->layout_err, 4, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(status + 1, &a.state->behind, 4, hipMemcpyDeviceToDevice, s));
+    return MOCAP_OK;
+}
+
+int mocap_rig_bundle_adjust(mocap_ctx_t c, int C, int N, int n_obs, const int32_t* obs_offset, const int32_t* obs_cam,
+                            const double* obs_uv, double* poses, double* points, int max_iters, double ftol, double lambda0,
+                            double* history, double* result, void* stream)
+{
+    if (!c || !obs_offset || !obs_cam || !obs_uv || !poses || !points || !history || !result) return fail(MOCAP_E_INVALID, "null argument");
+    if (max_iters < 1 || max_iters > 10000 || !(ftol >= 0.0) || !(lambda0 > 0.0) || !(lambda0 <= 1e16))
+        return fail(MOCAP_E_INVALID, "max_iters=%d ftol=%g lambda0=%g", max_iters, ftol, lambda0);
+    if (set_device(c)) return MOCAP_E_HIP;
+    std::lock_guard<std::mutex> lk(c->mu);
+    RigArgs a;
+    TRY(rig_args(c, C, N, n_obs, obs_offset, obs_cam, obs_uv, poses, points, a));
+    a.history = history; a.result = result;
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(hipMemsetAsync(a.state, 0, sizeof(RigState), s));
+    HIP_TRY(hipMemsetAsync(history, 0, 8 * 4 * (size_t)max_iters, s));
+    launch_rig_init(a, lambda0, s);
+    // every iteration is enqueued; the kernels of an iteration after the stop return at once
+    for (int it = 0; it < max_iters; it++) launch_rig_iteration(a, it, max_iters, ftol, s);
+    launch_rig_finish(a, s);
     HIP_TRY(hipGetLastError());
     return MOCAP_OK;
 }

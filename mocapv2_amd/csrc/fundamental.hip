@@ -226,18 +226,6 @@ __device__ __forceinline__ bool is_inlier(const double F[9], double x, double y,
     return (n1 * n1 <= thr2 * d1) && (n2 * n2 <= thr2 * d2) && d1 > 0.0 && d2 > 0.0;
 }
 
-// sum over the 256 threads of a workgroup by a fixed tree: lanes of a wave by shuffles (offsets 32 .. 1), the four waves in
-// order through LDS.  The same input gives the same bits on every run.  Every thread calls it; every thread gets the sum.
-__device__ __forceinline__ double block_sum(double v, double* s_part /*[4]*/)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    __syncthreads(); // the previous round's readers are done with s_part
-    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (s_part[0] + s_part[1]) + (s_part[2] + s_part[3]);
-}
-
 } // namespace
 
 // One lane per hypothesis, one wave per workgroup.

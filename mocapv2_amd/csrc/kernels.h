@@ -21,6 +21,26 @@ __host__ __device__ __forceinline__ uint32_t mask_byte_index(int y, int b, int w
     return mask_word_index(y, b >> 2, wpr) * 4u + (uint32_t)(b & 3);
 }
 __host__ __device__ __forceinline__ size_t mask_image_words(int H, int wpr) { return (size_t)((H + 31) >> 5) * 32 * (size_t)wpr; }
+
+// Sums with a fixed order, for results that must have the same bits on every run (no floating-point atomics): the lanes of a
+// wave by shuffles (offsets 32 .. 1; lane 0 holds the sum) ...
+__device__ __forceinline__ double wave_sum(double v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    return v;
+}
+// ... and the 256 threads of a workgroup: wave_sum, then the four waves in order through LDS.  Every thread calls it; every
+// thread gets the sum.
+__device__ __forceinline__ double block_sum(double v, double* s_part /*[4]*/)
+{
+    v = wave_sum(v);
+    __syncthreads(); // the previous round's readers are done with s_part
+    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (s_part[0] + s_part[1]) + (s_part[2] + s_part[3]);
+}
+
 void launch_mask_convert(const uint32_t* src, uint32_t* dst, int n_images, int H, int wpr, bool to_blocked, hipStream_t s);
 
 // The dense filter kernel (any geometry, any lens model): every tile of every image, the undistortion as a gather in the
@@ -326,6 +346,59 @@ struct FundArgs {
     uint8_t* inlier;           // [total]
     int32_t* status;           // [n_pairs][2] (winner, inliers) or (FUND_ERR_*, 0)
 };
+
+// bundle adjustment of a rig (rig_ba.hip).  The state record of one call: written by single-workgroup kernels only (the two
+// flags `behind` and `trial_behind` by integer atomicOr), read by every kernel of the iterations that follow.
+struct RigState {
+    double lambda, nu;         // Marquardt damping and Nielsen's growth factor
+    double cost, cost0;        // 1/2 sum r^2 of the current state, and of the state handed in
+    double t1_norm;            // |t_1| handed in: the gauge restored on return
+    int32_t stop, status;      // stop != 0: every later kernel returns at once; status: RIG_STOP_* / RIG_ERR_*
+    int32_t iters, cur;        // iterations done; which of the two pose / point buffers holds the current state
+    int32_t chol_fail, chol_fail_prev, behind, trial_behind, layout_err, pad;
+};
+enum { RIG_LIN_COST = 0, RIG_PRED_CAM = 1, RIG_NORM2_CAM = 2, RIG_N_SCALARS = 4 };
+enum { RIG_STOP_MAX_ITERS = 1, RIG_STOP_FTOL = 2, RIG_STOP_LAMBDA = 3, RIG_STOP_CHOLESKY = 4, RIG_ERR_LAYOUT = -2, RIG_ERR_BEHIND = -3 };
+
+struct RigArgs {
+    const CameraTable* cams;   // K and dist of cameras 0..C-1, by true camera number
+    const int32_t* obs_offset; // [N + 1] point n owns observations obs_offset[n] .. obs_offset[n + 1] - 1
+    const int32_t* obs_cam;    // [n_obs] ascending within a point
+    const double* obs_uv;      // [n_obs][2]
+    int C, N, n_obs;
+    int n_pairs, n_lin_blocks, n_chunks; // (C - 1) C / 2 pairs of free cameras; workgroups of the point kernels; of the Schur kernel
+    double* poses_io;          // [C][12] the caller's: R row-major, then t
+    double* points_io;         // [N][3] the caller's
+    // scratch of the context
+    RigState* state;
+    double* poses;             // [2][C][12] current and trial state (state->cur)
+    double* points;            // [2][N][3]
+    uint32_t* mask;            // [N] bit c: camera c sees the point
+    double* W;                 // [n_obs][18] W_nc, 6x3 row-major (unused for camera 0)
+    double* Vinv;              // [N][6] damped V^-1, upper triangle
+    double* vdiag;             // [N][3] diagonal of the undamped V
+    double* gp;                // [N][3] g_n
+    double* lin_part;          // [n_lin_blocks][C - 1][27] per-workgroup U_c (21) and g_c (6)
+    double* cost_part;         // [n_lin_blocks]
+    double* schur_part;        // [n_chunks][n_pairs][42]
+    double* S;                 // [D][D], D = 6 (C - 1): the damped reduced camera matrix
+    double* rhs;               // [D] reduced right-hand side
+    double* gc;                // [D] camera gradient
+    double* udiag;             // [D] diagonal of the undamped U
+    double* chol;              // [D (D + 1) / 2] the factor when it does not fit LDS
+    double* delta_c;           // [D] camera step
+    double* upd_part;          // [n_lin_blocks][3] trial cost, predicted reduction, |step|^2 of the points
+    double* scalars;           // [RIG_N_SCALARS]
+    double* history;           // [max_iters][4] the caller's (or null for a linearisation alone)
+    double* result;            // [4] the caller's
+};
+
+void launch_rig_init(const RigArgs& a, double lambda0, hipStream_t s);
+void launch_rig_linearize(const RigArgs& a, hipStream_t s);
+void launch_rig_iteration(const RigArgs& a, int it, int max_iters, double ftol, hipStream_t s);
+void launch_rig_finish(const RigArgs& a, hipStream_t s);
+int rig_lin_blocks(int N);
+int rig_schur_chunks(int N);
 
 enum { CORR_ERR_GROUPS = -2, CORR_ERR_TRUNCATED = -3, CORR_ERR_BLOB = -4 };
 enum { FUND_ERR_SAMPLE = -2, FUND_ERR_DEGENERATE = -3 };

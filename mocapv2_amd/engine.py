@@ -379,6 +379,85 @@ class MocapContext:
             out.append(r)
         return out
 
+    def _rig_upload(self, obs_offset, obs_cam, obs_uv, poses, points):
+        """Device copies of a rig problem in the layout of mocap_rig_bundle_adjust (checked here, so that a mistake is a
+        ValueError with a reason and not only the kernel's MOCAP_RIG_E_LAYOUT)."""
+        off = np.ascontiguousarray(obs_offset, np.int32).reshape(-1)
+        cam = np.ascontiguousarray(obs_cam, np.int32).reshape(-1)
+        uv = np.ascontiguousarray(obs_uv, np.float64).reshape(-1, 2)
+        poses = np.ascontiguousarray(poses, np.float64)
+        points = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+        Cn, N, n_obs = len(poses), len(points), len(cam)
+        if poses.shape != (Cn, 12) or not 2 <= Cn <= 32:
+            raise ValueError(f"poses must be [2..32][12] (R row-major, then t), got {poses.shape}")
+        if len(off) != N + 1 or off[0] != 0 or off[-1] != n_obs or len(uv) != n_obs or N < 1:
+            raise ValueError(f"obs_offset must be [N + 1 = {N + 1}] from 0 to n_obs = {n_obs}, obs_uv [n_obs][2]")
+        cnt = np.diff(off)
+        if (cnt < 2).any() or (cnt > Cn).any():
+            raise ValueError("every point needs 2..C observations")
+        if cam.min() < 0 or cam.max() >= Cn:
+            raise ValueError(f"obs_cam outside 0..{Cn - 1}")
+        inner = np.ones(n_obs, bool)
+        inner[off[:-1]] = False
+        if (np.diff(cam, prepend=-1)[inner] <= 0).any():
+            raise ValueError("a point's observations must come in strictly ascending camera order")
+        if getattr(self, "n_cam", 0) < Cn:
+            raise ValueError(f"set_cameras: {getattr(self, 'n_cam', 0)} cameras set, {Cn} needed (their K and dist are used)")
+        if not (np.isfinite(uv).all() and np.isfinite(poses).all() and np.isfinite(points).all()):
+            raise ValueError("observations, poses and points must be finite")
+        dev = self.device
+        return (Cn, N, n_obs, torch.from_numpy(off).to(dev), torch.from_numpy(cam).to(dev), torch.from_numpy(uv).to(dev),
+                torch.from_numpy(poses).to(dev), torch.from_numpy(points).to(dev))
+
+    def rig_linearize(self, obs_offset, obs_cam, obs_uv, poses, points, lam):
+        """The pieces of one iteration of rig_bundle_adjust at a given state and damping (mocap_rig_linearize): dict with cost
+        (1/2 sum r^2), gradient [6 (C - 1) + 3 N], S [D][D] (damped reduced camera matrix), rhs [D], behind (a point is not
+        in front of a camera that sees it).  Arguments as rig_bundle_adjust; K and dist come from set_cameras."""
+        Cn, N, n_obs, d_off, d_cam, d_uv, d_poses, d_pts = self._rig_upload(obs_offset, obs_cam, obs_uv, poses, points)
+        D = 6 * (Cn - 1)
+        dev = self.device
+        cost = torch.zeros((1,), dtype=torch.float64, device=dev)
+        grad = torch.zeros((D + 3 * N,), dtype=torch.float64, device=dev)
+        S = torch.zeros((D, D), dtype=torch.float64, device=dev)
+        rhs = torch.zeros((D,), dtype=torch.float64, device=dev)
+        status = torch.zeros((2,), dtype=torch.int32, device=dev)
+        _abi.check(self.lib.mocap_rig_linearize(self._h, Cn, N, n_obs, _ptr(d_off), _ptr(d_cam), _ptr(d_uv), _ptr(d_poses),
+                                                _ptr(d_pts), float(lam), _ptr(cost), _ptr(grad), _ptr(S), _ptr(rhs), _ptr(status),
+                                                _stream()))
+        self.sync()
+        status = status.cpu().numpy()
+        if status[0]:
+            raise _abi.MocapError(-2, "mocap_rig_linearize: the observation arrays break the layout rules (MOCAP_RIG_E_LAYOUT)")
+        return {"cost": float(cost.cpu().numpy()[0]), "gradient": grad.cpu().numpy(), "S": S.cpu().numpy(), "rhs": rhs.cpu().numpy(),
+                "behind": bool(status[1])}
+
+    def rig_bundle_adjust(self, obs_offset, obs_cam, obs_uv, poses, points, max_iters=50, ftol=1e-12, lambda0=1e-3):
+        """Bundle adjustment of a whole rig on the device (mocap_rig_bundle_adjust; the N-camera, partial-visibility
+        generalisation of reference lib/Helpers.py:158-176): one upload, ONE call that enqueues every iteration, one sync.
+        obs_offset int32 [N + 1], obs_cam int32 [n_obs] (true camera numbers, ascending within a point), obs_uv [n_obs][2]:
+        the observations, point-major; poses [C][12] (R row-major, then t; camera 0 is the identity), points [N][3]: the
+        start.  K and dist come from set_cameras.  Returns dict: poses [C][12], points [N][3] (|t_1| as at the start),
+        status (MOCAP_RIG_STOP_* > 0), iterations, cost_initial, cost (1/2 sum r^2), history [iterations][4] = (cost after
+        the iteration, lambda it was solved with, accepted, |step|).  A negative status (MOCAP_RIG_E_*) raises MocapError:
+        nothing is returned silently wrong."""
+        Cn, N, n_obs, d_off, d_cam, d_uv, d_poses, d_pts = self._rig_upload(obs_offset, obs_cam, obs_uv, poses, points)
+        max_iters = int(max_iters)
+        hist = torch.empty((max_iters, 4), dtype=torch.float64, device=self.device)
+        result = torch.zeros((4,), dtype=torch.float64, device=self.device)
+        _abi.check(self.lib.mocap_rig_bundle_adjust(self._h, Cn, N, n_obs, _ptr(d_off), _ptr(d_cam), _ptr(d_uv), _ptr(d_poses),
+                                                    _ptr(d_pts), max_iters, float(ftol), float(lambda0), _ptr(hist), _ptr(result),
+                                                    _stream()))
+        self.sync()
+        result = result.cpu().numpy()
+        status, iters = int(result[0]), int(result[1])
+        if status <= 0:
+            what = {-2: "the observation arrays break the layout rules (MOCAP_RIG_E_LAYOUT)",
+                    -3: "in the start state a point is not in front of a camera that sees it, or the cost is not finite "
+                        "(MOCAP_RIG_E_BEHIND)"}.get(status, f"status {status}")
+            raise _abi.MocapError(status, "mocap_rig_bundle_adjust: " + what)
+        return {"poses": d_poses.cpu().numpy(), "points": d_pts.cpu().numpy(), "status": status, "iterations": iters,
+                "cost_initial": float(result[2]), "cost": float(result[3]), "history": hist.cpu().numpy()[:iters].copy()}
+
     def ba_problem(self, pts, valid=None):
         """Bundle-adjustment residuals with the image points resident on the GPU (see BAProblem)."""
         return BAProblem(self, pts, valid)
