@@ -302,6 +302,60 @@ MOCAP_API int mocap_rig_linearize(mocap_ctx_t ctx, int C, int N, int n_obs, cons
                                   const double* points_dev, double lambda, double* cost_dev, double* gradient_dev, double* S_dev,
                                   double* rhs_dev, int32_t* status_dev, void* stream);
 
+/* Intrinsic calibration of every camera of a rig from planar-board corner lists: per camera fx, fy, cx, cy, k1, k2, p1, p2, k3
+ * and one board -> camera pose per view, by Levenberg-Marquardt on the device (Schur complement on the views, analytic
+ * Jacobian, Marquardt scaling, Nielsen's damping rule; FP64 throughout; definition in DESIGN.md section 2, restated by
+ * tests/intrinsics_ref.py).  Replaces reference CalculateCameraIntrinsic.py:58, cv2.calibrateCamera(objpoints, imgpoints,
+ * size, None, None), for all cameras in one call; corner detection stays with the caller.  Both entries were added without a
+ * change to any existing one, so MOCAP_ABI_VERSION stays 7.
+ *   n_cams                cameras, 1..65536
+ *   view_offset_host      int32 [n_cams + 1], HOST: camera c owns views view_offset[c] .. view_offset[c + 1] - 1, from 0,
+ *                         not descending; n_views = view_offset[n_cams] (at most 2^20)
+ *   point_offset_host     int32 [n_views + 1], HOST: view v owns points point_offset[v] .. point_offset[v + 1] - 1, from 0,
+ *                         not descending; total = point_offset[n_views] (at most 2^26).  Both are copied before the call returns
+ *   obj_xy_dev            float64 [total][2] board coordinates (X, Y) of every corner, Z = 0
+ *   img_uv_dev            float64 [total][2] their pixels
+ *   image_size_host       int32 [n_cams][2], HOST: width, height (the initialisation's principal point is ((w - 1) / 2,
+ *                         (h - 1) / 2)); may be null with have_start
+ *   have_start            0: kd_dev and view_poses_dev are outputs, the start is the definition's initialisation;
+ *                         1: they hold the start
+ *   max_iters, ftol, lambda0  the stopping rules and the first damping (50, 1e-12, 1e-3 in the Python surface)
+ *   kd_dev                float64 [n_cams][9] in / out: fx, fy, cx, cy, k1, k2, p1, p2, k3
+ *   view_poses_dev        float64 [n_views][12] in / out: R row-major then t, board -> camera
+ *   view_rms_dev          float64 [n_views]: sqrt(sum r^2 of the view / its points), NaN for a failed camera
+ *   history_dev           float64 [n_cams][max_iters][4], per camera as mocap_rig_bundle_adjust's
+ *   result_dev            float64 [n_cams][4]: status, iterations done, cost at the start (handed in or initialised), final
+ *                         cost (1/2 sum r^2 over the camera's points; OpenCV's return value is sqrt(2 cost / points)).
+ *                         status > 0: MOCAP_RIG_STOP_*; status < 0: MOCAP_INTR_E_*, and that camera's kd and poses are left
+ *                         as they were.  Every camera has its own damping, stop and status: a finished or failed camera
+ *                         changes nothing in another, and a camera's results are the bits it gives when calibrated alone
+ * A camera needs at least 3 views and a view at least 4 points, else the camera reports MOCAP_INTR_E_LAYOUT.  Offsets that
+ * descend or sizes outside the ranges are bad arguments (MOCAP_E_INVALID).
+ * Asynchronous on `stream`: all max_iters iterations are enqueued (four launches each), the kernels of a camera that has
+ * stopped return at once, and no array of the iteration crosses to the host.  No floating-point atomics: the same call gives
+ * the same bits.  The scratch belongs to the context and grows on demand: calls on one context must be ordered on one stream. */
+enum {
+    MOCAP_INTR_E_LAYOUT = -2,     /* fewer than 3 views, or a view with fewer than 4 points */
+    MOCAP_INTR_E_BEHIND = -3,     /* in the start state a point is not in front of its view's camera, or the cost is not finite */
+    MOCAP_INTR_E_DEGENERATE = -4  /* the initialisation cannot tell the focal lengths apart from the views' distances (all views
+                                     fronto-parallel, for one): 2x2 determinant <= 1e-10 (trace / 2)^2, or a solution not positive */
+};
+MOCAP_API int mocap_intrinsics_calibrate(mocap_ctx_t ctx, int n_cams, const int32_t* view_offset_host,
+                                         const int32_t* point_offset_host, const double* obj_xy_dev, const double* img_uv_dev,
+                                         const int32_t* image_size_host, int have_start, int max_iters, double ftol,
+                                         double lambda0, double* kd_dev, double* view_poses_dev, double* view_rms_dev,
+                                         double* history_dev, double* result_dev, void* stream);
+/* The pieces of one iteration of mocap_intrinsics_calibrate at a given state and damping, for tests: cost_dev [n_cams] = 1/2
+ * sum r^2; gradient_dev [9 n_cams + 6 n_views] = J^T r (the cameras' 9 each, then the views' 6 each: rotation, translation);
+ * S_dev [n_cams][81] the damped reduced camera matrix U* - sum_v W_v V*_v^-1 W_v^T; rhs_dev [n_cams][9] the reduced
+ * right-hand side -g_c + sum_v W_v V*_v^-1 g_v; status_dev int32 [n_cams][2] = (layout error, a point not in front of its
+ * view's camera).  The entries of a camera with a layout error are zero.  kd_dev and view_poses_dev are only read.
+ * Asynchronous on `stream`. */
+MOCAP_API int mocap_intrinsics_linearize(mocap_ctx_t ctx, int n_cams, const int32_t* view_offset_host,
+                                         const int32_t* point_offset_host, const double* obj_xy_dev, const double* img_uv_dev,
+                                         const double* kd_dev, const double* view_poses_dev, double lambda, double* cost_dev,
+                                         double* gradient_dev, double* S_dev, double* rhs_dev, int32_t* status_dev, void* stream);
+
 /* The path's one exchange step: with the cameras sharded over GPUs (one process per GPU), every rank
  * contributes the fixed-size centroid records of its images and receives all ranks' records, in rank order, before
  * correspondence -- one ncclAllGather (RCCL over xGMI) per batch.  The reference has no counterpart: its camera

@@ -17,6 +17,8 @@ What is batched that the reference loops over:
 Beyond the reference (whose calibration is two-camera at heart): `calibrate_rig` = `rig_initial_poses` (all camera pairs'
 fundamental matrices in one RANSAC call, a spanning tree with a common scale) + `bundle_adjust_rig` (all poses and all points
 on the GPU over exactly the observations that exist, csrc/rig_ba.hip; definition in DESIGN.md section 2).
+`calibrate_intrinsics` supplies the camera_params all of these take: K and distortion of every camera from board views
+(the reference's CalculateCameraIntrinsic.py:58, cv2.calibrateCamera, batched over the rig; csrc/intrinsics.hip).
 Image capture and the plotting / JSON writing of that script are outside the path.  `calculate_extrinsics` is the
 script's function of that name (:162-255) from image points to poses; the pieces still take fundamental matrices as
 arguments.
@@ -477,6 +479,77 @@ def calibrate_rig(image_points, valid, camera_params, threshold=10.0, hypotheses
     return out
 
 
+# ---- intrinsics: every camera of a rig from board views, on the GPU ------------------------------------------------------------
+def calibrate_intrinsics(views, image_sizes, start=None, max_iters=50, ftol=1e-12, ctx=None):
+    """K and the five distortion coefficients of every camera of a rig from planar-board corner lists, in ONE call on the GPU
+    (engine.MocapContext.intrinsics_calibrate -> mocap_intrinsics_calibrate; definition in DESIGN.md section 2).  The
+    reference's counterpart is cv2.calibrateCamera(objpoints, imgpoints, size, None, None) per camera
+    (CalculateCameraIntrinsic.py:58); finding the corners in the images (:35-45) stays with the caller.
+    views[c]: the views of camera c, each (object points [n][2] or [n][3] with Z = 0 -- the board's corners in board
+    coordinates --, image points [n][2] pixels), at least 3 views of at least 4 points; image_sizes: (width, height), one pair
+    for all cameras or one per camera; start: None, or per camera (camera_params entry, list of {"R", "t"} poses).
+    Returns one dict per camera: intrinsic_matrix (3x3) and distortion_coef ([k1, k2, p1, p2, k3]) -- the entry is a
+    camera_params entry as `calibrate_rig` and `save_intrinsics` take it --, poses (list of {"R": 3x3, "t": 3x1} board ->
+    camera, one per view), rms_px (sqrt(2 cost / points): cv2.calibrateCamera's return value), view_rms [views], cost,
+    cost_initial, status (MOCAP_RIG_STOP_*: 1 max_iters, 2 ftol, 3 lambda, 4 Cholesky; or MOCAP_INTR_E_*: -3 a start with a
+    point behind its camera, -4 views that cannot tell the focal lengths: all fronto-parallel, for one), iterations, history
+    [iterations][4] (cost, lambda, accepted, |step|).  A camera that failed (status < 0) is reported, not raised, so that one bad
+    camera does not lose the others: its matrices are the start's (None without one) and its rms_px is NaN.  What the host
+    can see before the call -- too few views or points, shapes, a board that is not flat -- raises ValueError naming the camera."""
+    n_cams = len(views)
+    if n_cams < 1:
+        raise ValueError("no cameras")
+    sizes = np.asarray(image_sizes, np.int64)
+    sizes = np.broadcast_to(sizes.reshape(-1, 2), (n_cams, 2)) if sizes.size == 2 else sizes.reshape(-1, 2)
+    if len(sizes) != n_cams:
+        raise ValueError(f"{len(sizes)} image sizes for {n_cams} cameras")
+    if start is not None and len(start) != n_cams:
+        raise ValueError(f"{len(start)} starts for {n_cams} cameras")
+    voff, poff, objs, imgs = [0], [0], [], []
+    for c, cam_views in enumerate(views):
+        if len(cam_views) < 3:
+            raise ValueError(f"camera {c}: {len(cam_views)} views, at least 3 are needed")
+        for v, (obj, img) in enumerate(cam_views):
+            obj, img = np.asarray(obj, float), np.asarray(img, float)
+            if obj.ndim != 2 or obj.shape[1] not in (2, 3) or img.shape != (len(obj), 2):
+                raise ValueError(f"camera {c}, view {v}: object points must be [n][2] or [n][3] and image points [n][2], got {obj.shape} and {img.shape}")
+            if len(obj) < 4:
+                raise ValueError(f"camera {c}, view {v}: {len(obj)} points, at least 4 are needed")
+            if obj.shape[1] == 3 and (obj[:, 2] != 0).any():
+                raise ValueError(f"camera {c}, view {v}: the board must be planar, Z = 0 in board coordinates")
+            objs.append(obj[:, :2])
+            imgs.append(img)
+            poff.append(poff[-1] + len(obj))
+        voff.append(voff[-1] + len(cam_views))
+    begin = None
+    if start is not None:
+        kd0, poses0 = [], []
+        for c, (entry, poses) in enumerate(start):
+            if len(poses) != len(views[c]):
+                raise ValueError(f"camera {c}: {len(poses)} start poses for {len(views[c])} views")
+            K, d = np.asarray(entry["intrinsic_matrix"], float), np.asarray(entry["distortion_coef"], float).ravel()[:5]
+            kd0.append(np.r_[K[0, 0], K[1, 1], K[0, 2], K[1, 2], d])
+            poses0 += [np.r_[np.asarray(p["R"], float).reshape(9), np.asarray(p["t"], float).reshape(3)] for p in poses]
+        begin = (np.array(kd0), np.array(poses0))
+    ctx = ctx or default_context()
+    out = ctx.intrinsics_calibrate(voff, poff, np.concatenate(objs), np.concatenate(imgs), sizes, begin, max_iters, ftol)
+    result = []
+    for c in range(n_cams):
+        status, kd = int(out["status"][c]), out["kd"][c]
+        ok, have = status > 0, status > 0 or start is not None
+        n_pts = poff[voff[c + 1]] - poff[voff[c]]
+        P = out["poses"][voff[c]:voff[c + 1]]
+        result.append({
+            "intrinsic_matrix": np.array([[kd[0], 0.0, kd[2]], [0.0, kd[1], kd[3]], [0.0, 0.0, 1.0]]) if have else None,
+            "distortion_coef": kd[4:].copy() if have else None,
+            "poses": [{"R": p[:9].reshape(3, 3).copy(), "t": p[9:].reshape(3, 1).copy()} for p in P] if have else None,
+            "rms_px": float(np.sqrt(2.0 * out["cost"][c] / n_pts)) if ok else float("nan"),
+            "view_rms": out["view_rms"][voff[c]:voff[c + 1]].copy(), "cost": float(out["cost"][c]),
+            "cost_initial": float(out["cost_initial"][c]), "status": status, "iterations": int(out["iterations"][c]),
+            "history": out["history"][c]})
+    return result
+
+
 # ---- bundle adjustment: residual and Jacobian in batched launches ---------------------------------------------------
 def residuals_batched(image_points, param_sets, camera_params, ctx=None, problem=None):
     """Residual vectors (per-point reprojection MSE, float32 -- reference lib/Helpers.py:161-167) of S parameter
@@ -650,6 +723,17 @@ def save_extrinsics(camera_poses, prefix="", directory="./jsons", camera_count=N
     return extrinsics_filename
 
 
+def save_intrinsics(entry, path="./jsons/camera-intrinsics.json"):
+    """The file reference CalculateCameraIntrinsic.py:77-84 writes: {"intrinsic_matrix": 3x3 list, "distortion_coef": list of
+    5} (`dist[0]` of cv2.calibrateCamera's 1x5 array), the layout `lib.Helpers` reads back as a camera_params entry.  entry: a
+    dict of `calibrate_intrinsics`, or any camera_params entry.  Returns the file name."""
+    intrinsics = {"intrinsic_matrix": np.asarray(entry["intrinsic_matrix"], float).reshape(3, 3).tolist(),
+                  "distortion_coef": np.asarray(entry["distortion_coef"], float).ravel().tolist()}
+    with open(path, "w") as outfile:
+        json.dump(intrinsics, outfile)
+    return path
+
+
 def save_objects(prefix="", object_points=None, directory="./jsons"):
     """reference `save_objects` (:275-281): `{directory}/{prefix}objects.json` = [[x, y, z], ...]."""
     objects_filename = f"{directory}/{prefix}objects.json"
@@ -684,4 +768,4 @@ __all__ = ["poses_to_fundamental_matrix", "decompose_essential", "select_relativ
            "calculate_normal", "rotation_matrix_from_vectors", "set_floor", "get_points", "save_extrinsics", "save_objects",
            "save_fundamentals", "pair_fundamentals", "sample_table", "find_fundamental_matrix", "find_fundamental_matrices",
            "tracker_fundamentals", "calculate_extrinsics", "undistort_points", "rig_initial_poses", "bundle_adjust_rig",
-           "calibrate_rig"]
+           "calibrate_rig", "calibrate_intrinsics", "save_intrinsics"]

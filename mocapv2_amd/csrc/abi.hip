@@ -227,6 +227,7 @@ struct mocap_ctx {
     Buf<double> ba_obj;                    // object points of mocap_ba_residuals, [B][N][3]
     Buf<char> fund_scratch;                // mocap_fundamental_ransac: every hypothesis' matrix, the counters, the pair offsets
     Buf<char> rig_scratch;                 // mocap_rig_bundle_adjust / mocap_rig_linearize: the state record, both state buffers, the blocks and partial sums
+    Buf<char> intr_scratch;                // mocap_intrinsics_calibrate / mocap_intrinsics_linearize: the offsets, the state records, both state buffers, the views' records
     Buf<char, true> ba_pinned;             // mocap_ba_residuals' host-side hand-over: parameters in, residuals + counts out (the kernel reads / writes it directly)
     std::shared_ptr<struct SharedComm> comm; // RCCL communicator of mocap_comm_init / mocap_comm_share, else null
     bool profiling = false;
@@ -1629,6 +1630,117 @@ int mocap_rig_bundle_adjust(mocap_ctx_t c, int C, int N, int n_obs, const int32_
     // every iteration is enqueued; the kernels of an iteration after the stop return at once
     for (int it = 0; it < max_iters; it++) launch_rig_iteration(a, it, max_iters, ftol, s);
     launch_rig_finish(a, s);
+    HIP_TRY(hipGetLastError());
+    return MOCAP_OK;
+}
+
+// The scratch of an intrinsic calibration, carved out of one block the context owns (grown to twice what a call needs); the
+// partition depends on the problem's sizes alone.  Checks the host-side layout, and uploads it with what it implies: the
+// camera of every view, and per camera whether it has its 3 views of 4 points.
+static int intr_args(mocap_ctx* c, int n_cams, const int32_t* view_offset, const int32_t* point_offset, const int32_t* image_size,
+                     const double* obj, const double* img, hipStream_t s, IntrArgs& a)
+{
+    if (n_cams < 1 || n_cams > 65536) return fail(MOCAP_E_INVALID, "n_cams=%d: 1..65536 cameras", n_cams);
+    if (view_offset[0] != 0) return fail(MOCAP_E_INVALID, "view_offset[0] = %d", view_offset[0]);
+    for (int k = 0; k < n_cams; k++)
+        if (view_offset[k + 1] < view_offset[k]) return fail(MOCAP_E_INVALID, "view_offset descends at camera %d", k);
+    const int n_views = view_offset[n_cams];
+    if (n_views < 1 || n_views > (1 << 20)) return fail(MOCAP_E_INVALID, "%d views: 1..2^20", n_views);
+    if (point_offset[0] != 0) return fail(MOCAP_E_INVALID, "point_offset[0] = %d", point_offset[0]);
+    for (int v = 0; v < n_views; v++)
+        if (point_offset[v + 1] < point_offset[v]) return fail(MOCAP_E_INVALID, "point_offset descends at view %d", v);
+    const int total = point_offset[n_views];
+    if (total < 1 || total > (1 << 26)) return fail(MOCAP_E_INVALID, "%d points: 1..2^26", total);
+    if (image_size)
+        for (int k = 0; k < 2 * n_cams; k++)
+            if (image_size[k] < 1) return fail(MOCAP_E_INVALID, "camera %d: image size %d x %d", k / 2, image_size[k & ~1], image_size[k | 1]);
+    // one host block, one copy: view_offset | point_offset | view_cam | image_size | cam_bad
+    const size_t n_int = ((size_t)n_cams + 1) + ((size_t)n_views + 1) + n_views + 2 * (size_t)n_cams + n_cams;
+    std::vector<int32_t> host(n_int);
+    int32_t* h_voff = host.data(); int32_t* h_poff = h_voff + n_cams + 1; int32_t* h_vcam = h_poff + n_views + 1;
+    int32_t* h_size = h_vcam + n_views; int32_t* h_bad = h_size + 2 * (size_t)n_cams;
+    memcpy(h_voff, view_offset, sizeof(int32_t) * ((size_t)n_cams + 1));
+    memcpy(h_poff, point_offset, sizeof(int32_t) * ((size_t)n_views + 1));
+    for (int k = 0; k < n_cams; k++) {
+        bool bad = view_offset[k + 1] - view_offset[k] < 3;
+        for (int v = view_offset[k]; v < view_offset[k + 1]; v++) { h_vcam[v] = k; bad = bad || point_offset[v + 1] - point_offset[v] < 4; }
+        h_bad[k] = bad;
+        h_size[2 * k] = image_size ? image_size[2 * k] : 1; h_size[2 * k + 1] = image_size ? image_size[2 * k + 1] : 1;
+    }
+    a = IntrArgs{};
+    a.n_cams = n_cams; a.n_views = n_views; a.obj = obj; a.img = img;
+    size_t used = 0;
+    auto take = [&used](size_t bytes) { const size_t at = used; used += (bytes + 15) & ~(size_t)15; return at; };
+    const size_t nc = n_cams, nv = n_views;
+    const size_t o_int = take(4 * n_int), o_state = take(sizeof(IntrState) * nc), o_kd = take(8 * 2 * 9 * nc), o_poses = take(8 * 2 * 12 * nv);
+    const size_t o_vcost = take(8 * 2 * nv), o_H = take(8 * 9 * nv), o_rec = take(8 * (size_t)INTR_REC * nv), o_gc = take(8 * 9 * nc), o_gv = take(8 * 6 * nv);
+    const size_t o_S = take(8 * 81 * nc), o_rhs = take(8 * 9 * nc), o_udiag = take(8 * 9 * nc), o_delta = take(8 * 9 * nc);
+    const size_t o_lcost = take(8 * nc), o_cpart = take(8 * 2 * nc), o_upd = take(8 * 3 * nv);
+    if (used > c->intr_scratch.n) TRY(c->intr_scratch.reserve(used * 2));
+    char* const b = c->intr_scratch;
+    int32_t* d_int = (int32_t*)(b + o_int);
+    // pageable host memory: the copy has left `host` when this returns
+    HIP_TRY(hipMemcpyAsync(d_int, host.data(), 4 * n_int, hipMemcpyHostToDevice, s));
+    a.view_offset = d_int; a.point_offset = d_int + (h_poff - h_voff); a.view_cam = d_int + (h_vcam - h_voff);
+    a.image_size = d_int + (h_size - h_voff); a.cam_bad = d_int + (h_bad - h_voff);
+    a.state = (IntrState*)(b + o_state); a.kd = (double*)(b + o_kd); a.poses = (double*)(b + o_poses); a.view_cost = (double*)(b + o_vcost);
+    a.H = (double*)(b + o_H); a.rec = (double*)(b + o_rec); a.gc = (double*)(b + o_gc); a.gv = (double*)(b + o_gv); a.S = (double*)(b + o_S);
+    a.rhs = (double*)(b + o_rhs); a.udiag = (double*)(b + o_udiag); a.delta_c = (double*)(b + o_delta); a.lin_cost = (double*)(b + o_lcost);
+    a.cam_part = (double*)(b + o_cpart); a.upd_part = (double*)(b + o_upd);
+    HIP_TRY(hipMemsetAsync(a.state, 0, sizeof(IntrState) * nc, s));
+    return 0;
+}
+
+int mocap_intrinsics_linearize(mocap_ctx_t c, int n_cams, const int32_t* view_offset_host, const int32_t* point_offset_host,
+                               const double* obj_xy, const double* img_uv, const double* kd, const double* view_poses, double lambda,
+                               double* cost, double* gradient, double* S, double* rhs, int32_t* status, void* stream)
+{
+    if (!c || !view_offset_host || !point_offset_host || !obj_xy || !img_uv || !kd || !view_poses || !cost || !gradient || !S || !rhs || !status)
+        return fail(MOCAP_E_INVALID, "null argument");
+    if (!(lambda >= 0.0) || !(lambda <= 1e300)) return fail(MOCAP_E_INVALID, "lambda = %g", lambda);
+    if (set_device(c)) return MOCAP_E_HIP;
+    std::lock_guard<std::mutex> lk(c->mu);
+    hipStream_t s = (hipStream_t)stream;
+    IntrArgs a;
+    TRY(intr_args(c, n_cams, view_offset_host, point_offset_host, nullptr, obj_xy, img_uv, s, a));
+    // (the state handed in is only read: the begin kernel copies it, no finish kernel runs)
+    a.kd_io = const_cast<double*>(kd); a.poses_io = const_cast<double*>(view_poses); a.lin_status = status;
+    const size_t nc = n_cams, nv = a.n_views;
+    // gc | gv | S | rhs lie one after another in the scratch: a camera with a layout error leaves its entries zero
+    HIP_TRY(hipMemsetAsync(a.gc, 0, (char*)a.udiag - (char*)a.gc, s));
+    HIP_TRY(hipMemsetAsync(a.lin_cost, 0, 8 * nc, s));
+    launch_intr_begin(a, 1, lambda, s);
+    launch_intr_linearize(a, 0, false, s);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(cost, a.lin_cost, 8 * nc, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(gradient, a.gc, 8 * 9 * nc, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(gradient + 9 * nc, a.gv, 8 * 6 * nv, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(S, a.S, 8 * 81 * nc, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(rhs, a.rhs, 8 * 9 * nc, hipMemcpyDeviceToDevice, s));
+    return MOCAP_OK;
+}
+
+int mocap_intrinsics_calibrate(mocap_ctx_t c, int n_cams, const int32_t* view_offset_host, const int32_t* point_offset_host,
+                               const double* obj_xy, const double* img_uv, const int32_t* image_size_host, int have_start, int max_iters,
+                               double ftol, double lambda0, double* kd, double* view_poses, double* view_rms, double* history, double* result,
+                               void* stream)
+{
+    if (!c || !view_offset_host || !point_offset_host || !obj_xy || !img_uv || !kd || !view_poses || !view_rms || !history || !result ||
+        (!have_start && !image_size_host))
+        return fail(MOCAP_E_INVALID, "null argument");
+    if (max_iters < 1 || max_iters > 10000 || !(ftol >= 0.0) || !(lambda0 > 0.0) || !(lambda0 <= 1e16))
+        return fail(MOCAP_E_INVALID, "max_iters=%d ftol=%g lambda0=%g", max_iters, ftol, lambda0);
+    if (set_device(c)) return MOCAP_E_HIP;
+    std::lock_guard<std::mutex> lk(c->mu);
+    hipStream_t s = (hipStream_t)stream;
+    IntrArgs a;
+    TRY(intr_args(c, n_cams, view_offset_host, point_offset_host, image_size_host, obj_xy, img_uv, s, a));
+    a.kd_io = kd; a.poses_io = view_poses; a.view_rms = view_rms; a.history = history; a.result = result; a.max_iters = max_iters;
+    HIP_TRY(hipMemsetAsync(history, 0, 8 * 4 * (size_t)max_iters * n_cams, s));
+    launch_intr_begin(a, have_start != 0, lambda0, s);
+    // every iteration is enqueued; the kernels of a camera that has stopped return at once
+    for (int it = 0; it < max_iters; it++) launch_intr_iteration(a, it, ftol, s);
+    launch_intr_finish(a, s);
     HIP_TRY(hipGetLastError());
     return MOCAP_OK;
 }

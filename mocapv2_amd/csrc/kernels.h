@@ -41,6 +41,23 @@ __device__ __forceinline__ double block_sum(double v, double* s_part /*[4]*/)
     return (s_part[0] + s_part[1]) + (s_part[2] + s_part[3]);
 }
 
+// R <- Exp(w) R by Rodrigues' formula: the local rotation update of the two Levenberg-Marquardt loops (rig_ba.hip, intrinsics.hip)
+__device__ __forceinline__ void rotate_left(const double w[3], const double R[9], double out[9])
+{
+    const double th2 = (w[0] * w[0] + w[1] * w[1]) + w[2] * w[2], th = sqrt(th2);
+    const double ka = th < 1e-12 ? 1.0 : sin(th) / th, kb = th < 1e-12 ? 0.5 : (1.0 - cos(th)) / th2;
+    // E = I + ka K + kb K^2, K = [w]x, K^2 = w w^T - th2 I
+    double E[9];
+    E[0] = 1.0 + kb * (w[0] * w[0] - th2); E[4] = 1.0 + kb * (w[1] * w[1] - th2); E[8] = 1.0 + kb * (w[2] * w[2] - th2);
+    E[1] = kb * (w[0] * w[1]) - ka * w[2]; E[3] = kb * (w[0] * w[1]) + ka * w[2];
+    E[2] = kb * (w[0] * w[2]) + ka * w[1]; E[6] = kb * (w[0] * w[2]) - ka * w[1];
+    E[5] = kb * (w[1] * w[2]) - ka * w[0]; E[7] = kb * (w[1] * w[2]) + ka * w[0];
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) out[3 * i + j] = (E[3 * i] * R[j] + E[3 * i + 1] * R[3 + j]) + E[3 * i + 2] * R[6 + j];
+}
+
 void launch_mask_convert(const uint32_t* src, uint32_t* dst, int n_images, int H, int wpr, bool to_blocked, hipStream_t s);
 
 // The dense filter kernel (any geometry, any lens model): every tile of every image, the undistortion as a gather in the
@@ -399,6 +416,59 @@ void launch_rig_iteration(const RigArgs& a, int it, int max_iters, double ftol, 
 void launch_rig_finish(const RigArgs& a, hipStream_t s);
 int rig_lin_blocks(int N);
 int rig_schur_chunks(int N);
+
+// intrinsic calibration of every camera of a rig from planar-board views (intrinsics.hip).  One state record per camera,
+// written by that camera's single-workgroup kernels only (the flags `behind`, `trial_behind` and `chol_fail` also by integer
+// atomicOr from its views' waves), read by every kernel of the iterations that follow.  The stop values are RIG_STOP_*.
+struct IntrState {
+    double lambda, nu;         // Marquardt damping and Nielsen's growth factor
+    double cost, cost0;        // 1/2 sum r^2 of the current state, and of the start
+    int32_t stop, status;      // stop != 0: every later kernel returns at once for this camera; status: RIG_STOP_* / INTR_ERR_*
+    int32_t iters, cur;        // iterations done; which of the two state buffers holds the current state
+    int32_t chol_fail, chol_fail_prev, behind, trial_behind;
+};
+enum { INTR_ERR_LAYOUT = -2, INTR_ERR_BEHIND = -3, INTR_ERR_DEGENERATE = -4 };
+// A view's record, in doubles: the 136 sums of [J r]^T [J r] (16 columns: kd's 9, the pose's 6, r; upper triangle row by row),
+// then the upper triangle of W V*^-1 W^T (45), W V*^-1 g_v (9), the factor of V* (packed lower triangle, 21)
+enum { INTR_REC_SUMS = 0, INTR_REC_T = 136, INTR_REC_YG = 181, INTR_REC_L = 190, INTR_REC = 216 };
+
+struct IntrArgs {
+    int n_cams, n_views;
+    const int32_t* view_offset;  // [n_cams + 1] camera c owns views view_offset[c] .. view_offset[c + 1] - 1     (device copies
+    const int32_t* point_offset; // [n_views + 1] view v owns points point_offset[v] .. point_offset[v + 1] - 1     made by the
+    const int32_t* view_cam;     // [n_views] the view's camera                                                      entry point)
+    const int32_t* image_size;   // [n_cams][2] width, height (read by the initialisation only)
+    const int32_t* cam_bad;      // [n_cams] nonzero: fewer than 3 views, or a view with fewer than 4 points
+    const double* obj;           // [total][2] board points (X, Y), Z = 0
+    const double* img;           // [total][2] their pixels
+    double* kd_io;               // [n_cams][9] the caller's: fx, fy, cx, cy, k1, k2, p1, p2, k3
+    double* poses_io;            // [n_views][12] the caller's: R row-major, then t (board -> camera)
+    double* view_rms;            // [n_views] the caller's
+    double* history;             // [n_cams][max_iters][4] the caller's
+    double* result;              // [n_cams][4] the caller's
+    int32_t* lin_status;         // [n_cams][2] the caller's (mocap_intrinsics_linearize), else null
+    int max_iters;
+    // scratch of the context
+    IntrState* state;            // [n_cams]
+    double* kd;                  // [2][n_cams][9] current and trial state (state->cur)
+    double* poses;               // [2][n_views][12]
+    double* view_cost;           // [2][n_views] sum r^2 of the view in the current and the trial state
+    double* H;                   // [n_views][9] the initialisation's homographies
+    double* rec;                 // [n_views][INTR_REC]
+    double* gv;                  // [n_views][6] the views' gradients
+    double* S;                   // [n_cams][81] damped reduced camera matrix
+    double* rhs;                 // [n_cams][9]
+    double* gc;                  // [n_cams][9] camera gradient
+    double* udiag;               // [n_cams][9] diagonal of the undamped U
+    double* delta_c;             // [n_cams][9] camera step
+    double* lin_cost;            // [n_cams] 1/2 sum r^2 of the linearised state
+    double* cam_part;            // [n_cams][2] the camera's part of the predicted reduction and of |step|^2
+    double* upd_part;            // [n_views][3] trial sum r^2, predicted reduction, |step|^2 of the view
+};
+void launch_intr_begin(const IntrArgs& a, int have_start, double lambda0, hipStream_t s);
+void launch_intr_linearize(const IntrArgs& a, int it, bool solve, hipStream_t s);
+void launch_intr_iteration(const IntrArgs& a, int it, double ftol, hipStream_t s);
+void launch_intr_finish(const IntrArgs& a, hipStream_t s);
 
 enum { CORR_ERR_GROUPS = -2, CORR_ERR_TRUNCATED = -3, CORR_ERR_BLOB = -4 };
 enum { FUND_ERR_SAMPLE = -2, FUND_ERR_DEGENERATE = -3 };

@@ -377,23 +377,6 @@ __device__ __forceinline__ void solve_packed(const double* L, int D, double* s_x
     }
 }
 
-// R <- Exp(w) R by Rodrigues' formula
-__device__ __forceinline__ void rotate_left(const double w[3], const double R[9], double out[9])
-{
-    const double th2 = (w[0] * w[0] + w[1] * w[1]) + w[2] * w[2], th = sqrt(th2);
-    const double ka = th < 1e-12 ? 1.0 : sin(th) / th, kb = th < 1e-12 ? 0.5 : (1.0 - cos(th)) / th2;
-    // E = I + ka K + kb K^2, K = [w]x, K^2 = w w^T - th2 I
-    double E[9];
-    E[0] = 1.0 + kb * (w[0] * w[0] - th2); E[4] = 1.0 + kb * (w[1] * w[1] - th2); E[8] = 1.0 + kb * (w[2] * w[2] - th2);
-    E[1] = kb * (w[0] * w[1]) - ka * w[2]; E[3] = kb * (w[0] * w[1]) + ka * w[2];
-    E[2] = kb * (w[0] * w[2]) + ka * w[1]; E[6] = kb * (w[0] * w[2]) - ka * w[1];
-    E[5] = kb * (w[1] * w[2]) - ka * w[0]; E[7] = kb * (w[1] * w[2]) + ka * w[0];
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) out[3 * i + j] = (E[3 * i] * R[j] + E[3 * i + 1] * R[3 + j]) + E[3 * i + 2] * R[6 + j];
-}
-
 } // namespace
 
 // One workgroup.  Also the keeper of the state record's first cost, and of the two failures a linearisation can show.

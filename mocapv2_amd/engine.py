@@ -458,6 +458,94 @@ class MocapContext:
         return {"poses": d_poses.cpu().numpy(), "points": d_pts.cpu().numpy(), "status": status, "iterations": iters,
                 "cost_initial": float(result[2]), "cost": float(result[3]), "history": hist.cpu().numpy()[:iters].copy()}
 
+    def _intr_upload(self, view_offset, point_offset, obj_xy, img_uv):
+        """Host offsets and device copies of a board-view problem in the layout of mocap_intrinsics_calibrate.  Only the
+        shapes are checked here: what a camera or a view lacks is that camera's MOCAP_INTR_E_LAYOUT."""
+        voff = np.ascontiguousarray(view_offset, np.int32).reshape(-1)
+        poff = np.ascontiguousarray(point_offset, np.int32).reshape(-1)
+        obj = np.ascontiguousarray(obj_xy, np.float64).reshape(-1, 2)
+        img = np.ascontiguousarray(img_uv, np.float64).reshape(-1, 2)
+        n_cams = len(voff) - 1
+        if n_cams < 1 or voff[0] != 0 or (np.diff(voff) < 0).any():
+            raise ValueError("view_offset must be [n_cams + 1], from 0, not descending")
+        n_views = int(voff[-1])
+        if n_views < 1 or len(poff) != n_views + 1 or poff[0] != 0 or (np.diff(poff) < 0).any():
+            raise ValueError(f"point_offset must be [n_views + 1 = {n_views + 1}], from 0, not descending")
+        if len(obj) != poff[-1] or len(img) != poff[-1] or len(obj) < 1:
+            raise ValueError(f"obj_xy and img_uv must be [{poff[-1]}][2], got {obj.shape} and {img.shape}")
+        if not (np.isfinite(obj).all() and np.isfinite(img).all()):
+            raise ValueError("board points and pixels must be finite")
+        dev = self.device
+        return n_cams, n_views, voff, poff, torch.from_numpy(obj).to(dev), torch.from_numpy(img).to(dev)
+
+    def intrinsics_linearize(self, view_offset, point_offset, obj_xy, img_uv, kd, view_poses, lam):
+        """The pieces of one iteration of intrinsics_calibrate at a given state and damping (mocap_intrinsics_linearize): dict
+        with cost [n_cams] (1/2 sum r^2), gradient [9 n_cams + 6 n_views] (cameras first), S [n_cams][9][9] (damped reduced
+        camera matrix), rhs [n_cams][9], layout [n_cams] (the camera breaks the layout rules: its entries are zero), behind
+        [n_cams] (a point is not in front of its view's camera).  Arguments as intrinsics_calibrate."""
+        n_cams, n_views, voff, poff, d_obj, d_img = self._intr_upload(view_offset, point_offset, obj_xy, img_uv)
+        kd = np.ascontiguousarray(kd, np.float64).reshape(n_cams, 9)
+        poses = np.ascontiguousarray(view_poses, np.float64).reshape(n_views, 12)
+        dev = self.device
+        d_kd, d_poses = torch.from_numpy(kd).to(dev), torch.from_numpy(poses).to(dev)
+        cost = torch.zeros((n_cams,), dtype=torch.float64, device=dev)
+        grad = torch.zeros((9 * n_cams + 6 * n_views,), dtype=torch.float64, device=dev)
+        S = torch.zeros((n_cams, 9, 9), dtype=torch.float64, device=dev)
+        rhs = torch.zeros((n_cams, 9), dtype=torch.float64, device=dev)
+        status = torch.zeros((n_cams, 2), dtype=torch.int32, device=dev)
+        ip = C.POINTER(C.c_int)
+        _abi.check(self.lib.mocap_intrinsics_linearize(self._h, n_cams, voff.ctypes.data_as(ip), poff.ctypes.data_as(ip), _ptr(d_obj),
+                                                       _ptr(d_img), _ptr(d_kd), _ptr(d_poses), float(lam), _ptr(cost), _ptr(grad), _ptr(S),
+                                                       _ptr(rhs), _ptr(status), _stream()))
+        self.sync()
+        status = status.cpu().numpy()
+        return {"cost": cost.cpu().numpy(), "gradient": grad.cpu().numpy(), "S": S.cpu().numpy(), "rhs": rhs.cpu().numpy(),
+                "layout": status[:, 0].astype(bool), "behind": status[:, 1].astype(bool)}
+
+    def intrinsics_calibrate(self, view_offset, point_offset, obj_xy, img_uv, image_sizes, start=None, max_iters=50, ftol=1e-12,
+                             lambda0=1e-3):
+        """Intrinsic calibration of every camera of a rig from planar-board corner lists on the device
+        (mocap_intrinsics_calibrate; reference CalculateCameraIntrinsic.py:58, cv2.calibrateCamera, for all cameras at once):
+        one upload, ONE call that enqueues every iteration, one sync.
+        view_offset int32 [n_cams + 1], point_offset int32 [n_views + 1]: camera c owns views view_offset[c] ..
+        view_offset[c + 1] - 1, view v points point_offset[v] .. point_offset[v + 1] - 1; obj_xy [total][2] board coordinates
+        (Z = 0), img_uv [total][2] pixels; image_sizes [n_cams][2] (width, height); start: None (the definition's
+        initialisation) or (kd [n_cams][9], poses [n_views][12]).
+        Returns dict of arrays: kd [n_cams][9] (fx, fy, cx, cy, k1, k2, p1, p2, k3), poses [n_views][12] (R row-major, then
+        t), view_rms [n_views], status [n_cams] (MOCAP_RIG_STOP_* > 0, or MOCAP_INTR_E_*: -2 layout, -3 a point behind its
+        camera at the start, -4 degenerate views), iterations, cost_initial, cost [n_cams] (1/2 sum r^2), and history: per
+        camera [iterations][4] = (cost after the iteration, lambda it was solved with, accepted, |step|).  A failed camera is
+        reported by its status, never raised: its kd and poses are the start handed in (NaN when there was none)."""
+        n_cams, n_views, voff, poff, d_obj, d_img = self._intr_upload(view_offset, point_offset, obj_xy, img_uv)
+        size = np.ascontiguousarray(image_sizes, np.int32).reshape(n_cams, 2)
+        if (size < 1).any():
+            raise ValueError("image sizes must be positive")
+        max_iters = int(max_iters)
+        dev = self.device
+        if start is None:
+            d_kd = torch.full((n_cams, 9), float("nan"), dtype=torch.float64, device=dev)
+            d_poses = torch.full((n_views, 12), float("nan"), dtype=torch.float64, device=dev)
+        else:
+            kd = np.ascontiguousarray(start[0], np.float64).reshape(n_cams, 9)
+            poses = np.ascontiguousarray(start[1], np.float64).reshape(n_views, 12)
+            if not (np.isfinite(kd).all() and np.isfinite(poses).all()):
+                raise ValueError("the start must be finite")
+            d_kd, d_poses = torch.from_numpy(kd).to(dev), torch.from_numpy(poses).to(dev)
+        rms = torch.zeros((n_views,), dtype=torch.float64, device=dev)
+        hist = torch.empty((n_cams, max_iters, 4), dtype=torch.float64, device=dev)
+        result = torch.zeros((n_cams, 4), dtype=torch.float64, device=dev)
+        ip = C.POINTER(C.c_int)
+        _abi.check(self.lib.mocap_intrinsics_calibrate(self._h, n_cams, voff.ctypes.data_as(ip), poff.ctypes.data_as(ip), _ptr(d_obj),
+                                                       _ptr(d_img), size.ctypes.data_as(ip), int(start is not None), max_iters,
+                                                       float(ftol), float(lambda0), _ptr(d_kd), _ptr(d_poses), _ptr(rms), _ptr(hist),
+                                                       _ptr(result), _stream()))
+        self.sync()
+        result, hist = result.cpu().numpy(), hist.cpu().numpy()
+        iters = result[:, 1].astype(np.int64)
+        return {"kd": d_kd.cpu().numpy(), "poses": d_poses.cpu().numpy(), "view_rms": rms.cpu().numpy(),
+                "status": result[:, 0].astype(np.int64), "iterations": iters, "cost_initial": result[:, 2].copy(),
+                "cost": result[:, 3].copy(), "history": [hist[c, :iters[c]].copy() for c in range(n_cams)]}
+
     def ba_problem(self, pts, valid=None):
         """Bundle-adjustment residuals with the image points resident on the GPU (see BAProblem)."""
         return BAProblem(self, pts, valid)
