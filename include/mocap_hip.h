@@ -32,7 +32,8 @@ enum {
 
 /* per-image status written to out_count by the blob kernels when an internal capacity is exceeded */
 enum {
-    MOCAP_BLOB_E_CANDIDATES = -2, /* more than 1024 border start candidates in one image */
+    MOCAP_BLOB_E_CANDIDATES = -2, /* more than 1024 border start candidates in one image (pixels that locally look like the
+                                     first pixel of a border; how much of the frame holds set pixels is no limit) */
     MOCAP_BLOB_E_CONTOURS = -3,   /* more than 384 borders or 256 kept contours in one image */
     MOCAP_BLOB_E_STEPS = -4,      /* a border longer than the step limit */
     MOCAP_BLOB_E_DEPTH = -5,      /* a kept contour nested deeper than 8 levels */

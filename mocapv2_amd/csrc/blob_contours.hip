@@ -39,7 +39,7 @@ constexpr int MAXC = 1024;  // candidates per image (after the run-level filters
 constexpr int MAXR = 384;   // borders per image
 constexpr int MAXK = 256;   // kept contours per image
 constexpr int MAXD = 8;     // nesting depth of a kept contour
-constexpr int MAXCELL = 4096; // occupancy cells (strip x 8 rows) scanned per image
+constexpr int MAXCELL = 4096; // occupancy cells (strip x 8 rows) listed per image; with more, every cell is scanned
 constexpr int MAXA = 64;    // links per image whose owner has to be found by a walk that are handed to the packed second pass
 
 __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
@@ -373,13 +373,12 @@ __device__ __forceinline__ void contours_body(const ContourArgs& a, const int im
     // (strip, chunk): bit g = rows 8g..8g+7 of the chunk contain set pixels in that 240-column strip.  Occupied
     // cells, plus their right and lower neighbours (a hole can start in an empty cell whose W / N neighbour pixel
     // lies in the occupied one), are scanned row by row with word-parallel bit tests; without the occupancy words
-    // (mask supplied by the caller) every cell is scanned.
+    // (mask supplied by the caller), or when the occupied cells outnumber the list (MAXCELL), every cell is scanned.
     {
         const int R = a.rows_per_chunk, NS = a.n_strips, NCH = a.n_chunks;
         const int gpc = (R + 7) >> 3;                       // 8-row groups per chunk
         const uint32_t* cells = a.cells ? a.cells + (size_t)image * NCH * NS : nullptr;
         const uint32_t* boxes = (a.cells && a.boxes) ? a.boxes + (size_t)image * NCH * NS * 4 : nullptr;
-        const bool ranged = cells != nullptr; // cell_rng holds the words to examine (the whole strip without boxes)
         const int n_cells = NCH * NS * gpc;
         if (cells) {
             // one task = one (chunk, strip) occupancy word: its own groups, and the groups its right and lower
@@ -429,9 +428,11 @@ __device__ __forceinline__ void contours_body(const ContourArgs& a, const int im
                 }
             }
             __syncthreads();
-            if (ncell > MAXCELL && tid == 0) atomicMax(&err, 4);
         }
-        const int ncl = cells ? (ncell < MAXCELL ? ncell : MAXCELL) : n_cells;
+        // A frame with more cells to scan than the list holds (MAXCELL; a 3840 x 2160 frame has 16 strips x 286 groups) is no error: like a
+        // caller's mask it has every cell scanned, over the whole width of its strip.
+        const bool listed = cells != nullptr && ncell <= MAXCELL; // cell_list / cell_rng hold the cells and the words to examine
+        const int ncl = listed ? ncell : n_cells;
         // One task = one cell, taken by a group of 8 lanes: lane j of the group holds row j of the cell (the lanes of a load lie
         // in one or two lines of the blocked mask) and loads 8 consecutive words of it, kf - 1 + p0 .. kf + p0 + 6 (kf = first
         // word of the cell's column range, see above); the row above comes from lane j - 1 (DPP), lane 0 loads it.  Words
@@ -440,14 +441,14 @@ __device__ __forceinline__ void contours_body(const ContourArgs& a, const int im
         for (int ci0 = 0; ci0 < ncl; ci0 += NTHREADS / 8) {
             const int ci = ci0 + grp8;
             const bool cv = ci < ncl;
-            const int cell = cv ? (cells ? (int)cell_list[ci] : ci) : 0;
+            const int cell = cv ? (listed ? (int)cell_list[ci] : ci) : 0;
             const int g = cell % gpc, st = (cell / gpc) % NS, ch = cell / (gpc * NS);
             const int y0 = ch * R + 8 * g;
             const int yend = (ch + 1) * R < a.H ? (ch + 1) * R : a.H;
             const int xa = 240 * st, xb = xa + 240 < a.W ? xa + 240 : a.W; // the strip's columns [xa, xb)
             const int ka = xa >> 5, kb = (xb - 1) >> 5;
             int kf = ka, cnt = kb - ka + 1;
-            if (ranged && cv) { const uint32_t rg = cell_rng[ci]; kf = (int)(rg & 0xfffu); cnt = (int)(rg >> 12); }
+            if (listed && cv) { const uint32_t rg = cell_rng[ci]; kf = (int)(rg & 0xfffu); cnt = (int)(rg >> 12); }
             if (!cv) cnt = 0;
             const int y = y0 + sub;
             const bool rowv = y < yend && 8 * g + sub < R;
@@ -514,7 +515,7 @@ __device__ __forceinline__ void contours_body(const ContourArgs& a, const int im
     }
     __syncthreads();
     stamp(1);
-    if (ncand > MAXC || err) {
+    if (ncand > MAXC) {
         if (tid == 0) { *out_count = BLOB_ERR_CANDIDATES; if (a.dbg_count) a.dbg_count[image] = 0; if (MODE == 1) work.st_ncand = -1; }
         return;
     }

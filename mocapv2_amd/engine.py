@@ -183,15 +183,19 @@ class MocapContext:
         _abi.check(self.lib.mocap_filter_mask(self._h, _ptr(flat), n, cam_mod, slot_base, stride, pitch, _ptr(mask), _stream()))
         return mask
 
-    def contours_from_mask(self, mask, max_blobs=MAX_BLOBS, debug_cap=0):
+    def contours_from_mask(self, mask, max_blobs=MAX_BLOBS, debug_cap=0, xy=None):
+        """xy: optional int32 [n, rows >= max_blobs, 2] device tensor to write into (at most max_blobs rows per image are written)."""
         n = mask.shape[0]
-        xy = torch.empty((n, max_blobs, 2), dtype=torch.int32, device=self.device)
+        if xy is None:
+            xy = torch.empty((n, max_blobs, 2), dtype=torch.int32, device=self.device)
+        assert xy.is_cuda and xy.is_contiguous() and xy.dtype == torch.int32 and xy.dim() == 3
+        assert xy.shape[0] == n and xy.shape[1] >= max_blobs and xy.shape[2] == 2, (xy.shape, n, max_blobs)
         cnt = torch.empty((n,), dtype=torch.int32, device=self.device)
         dbg = dbg_n = None
         if debug_cap:
             dbg = torch.zeros((n, debug_cap, C.sizeof(_abi.Contour)), dtype=torch.uint8, device=self.device)
             dbg_n = torch.zeros((n,), dtype=torch.int32, device=self.device)
-        _abi.check(self.lib.mocap_contours_from_mask(self._h, _ptr(mask), n, _ptr(xy), 2 * max_blobs, _ptr(cnt), 1, max_blobs,
+        _abi.check(self.lib.mocap_contours_from_mask(self._h, _ptr(mask), n, _ptr(xy), 2 * xy.shape[1], _ptr(cnt), 1, max_blobs,
                                                      _ptr(dbg), _ptr(dbg_n), debug_cap, _stream()))
         if not debug_cap:
             return xy, cnt

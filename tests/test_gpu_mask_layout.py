@@ -6,7 +6,7 @@ import pytest
 
 import oracle
 from mocapv2_amd.synth import MILD_DIST, Scene
-from test_gpu_blob import check_against_oracle, dark_frames, make_ctx, rand_frames
+from test_gpu_blob import dark_frames, make_ctx, rand_frames
 
 pytestmark = pytest.mark.gpu
 
@@ -41,7 +41,7 @@ def test_filter_mask_writes_row_major_mask_twice(torch_cuda, W, H):
 
 @pytest.mark.parametrize("W,H", [(301, 33), (1921, 1081)])
 def test_contours_from_caller_mask_match_oracle(torch_cuda, W, H):
-    from gpu_util import pack_mask
+    from gpu_util import check_against_oracle, pack_mask
     rng = np.random.default_rng(H)
     frames = dark_frames(rng, 2, H, W, n_discs=3 if H < 64 else 30, salt=0.001)
     masks = np.stack([oracle.image_filter(f, 0) for f in frames])
