@@ -304,6 +304,14 @@ static int load_rccl()
         if (r_ != 0) return fail(MOCAP_E_HIP, "%s failed: %s", #expr, g_rccl.GetErrorString(r_));             \
     } while (0)
 
+// Cuts a scratch block (rig_args, intr_args) into buffers, each rounded up to 16 bytes, in the order of the take() calls.  Over
+// a null base it only counts (`used` is the block's size); over the block it sets the pointers.
+struct Carver {
+    char* base;
+    size_t used = 0;
+    template <class T> void take(T*& p, size_t count) { p = base ? (T*)(base + used) : nullptr; used += (sizeof(T) * count + 15) & ~(size_t)15; }
+};
+
 extern "C" {
 
 int mocap_abi_version(void) { return MOCAP_ABI_VERSION; }
@@ -1562,23 +1570,19 @@ static int rig_args(mocap_ctx* c, int C, int N, int n_obs, const int32_t* obs_of
     a.n_pairs = (C - 1) * C / 2; a.n_lin_blocks = rig_lin_blocks(N); a.n_chunks = rig_schur_chunks(N);
     a.poses_io = poses; a.points_io = points;
     const size_t D = 6 * (size_t)(C - 1);
-    size_t used = 0;
-    auto take = [&used](size_t bytes) { const size_t at = used; used += (bytes + 15) & ~(size_t)15; return at; };
-    const size_t o_state = take(sizeof(RigState)), o_poses = take(8 * 2 * 12 * (size_t)C), o_points = take(8 * 2 * 3 * (size_t)N);
-    const size_t o_mask = take(4 * (size_t)N), o_W = take(8 * 18 * (size_t)n_obs), o_Vinv = take(8 * 6 * (size_t)N);
-    const size_t o_vdiag = take(8 * 3 * (size_t)N), o_gp = take(8 * 3 * (size_t)N);
-    const size_t o_lin = take(8 * 27 * (size_t)a.n_lin_blocks * (C - 1)), o_cost = take(8 * (size_t)a.n_lin_blocks);
-    const size_t o_schur = take(8 * 42 * (size_t)a.n_chunks * a.n_pairs), o_S = take(8 * D * D), o_rhs = take(8 * D), o_gc = take(8 * D);
-    const size_t o_udiag = take(8 * D), o_chol = take(8 * D * (D + 1) / 2), o_delta = take(8 * D);
-    const size_t o_upd = take(8 * 3 * (size_t)a.n_lin_blocks), o_scal = take(8 * RIG_N_SCALARS);
-    if (used > c->rig_scratch.n) TRY(c->rig_scratch.reserve(used * 2));
-    char* const b = c->rig_scratch;
-    a.state = (RigState*)(b + o_state); a.poses = (double*)(b + o_poses); a.points = (double*)(b + o_points);
-    a.mask = (uint32_t*)(b + o_mask); a.W = (double*)(b + o_W); a.Vinv = (double*)(b + o_Vinv); a.vdiag = (double*)(b + o_vdiag);
-    a.gp = (double*)(b + o_gp); a.lin_part = (double*)(b + o_lin); a.cost_part = (double*)(b + o_cost);
-    a.schur_part = (double*)(b + o_schur); a.S = (double*)(b + o_S); a.rhs = (double*)(b + o_rhs); a.gc = (double*)(b + o_gc);
-    a.udiag = (double*)(b + o_udiag); a.chol = (double*)(b + o_chol); a.delta_c = (double*)(b + o_delta);
-    a.upd_part = (double*)(b + o_upd); a.scalars = (double*)(b + o_scal);
+    auto carve = [&](char* base) {
+        Carver k{base};
+        k.take(a.state, 1); k.take(a.poses, 2 * 12 * (size_t)C); k.take(a.points, 2 * 3 * (size_t)N); k.take(a.mask, N);
+        k.take(a.W, 18 * (size_t)n_obs); k.take(a.Vinv, 6 * (size_t)N); k.take(a.vdiag, 3 * (size_t)N); k.take(a.gp, 3 * (size_t)N);
+        k.take(a.lin_part, 27 * (size_t)a.n_lin_blocks * (C - 1)); k.take(a.cost_part, a.n_lin_blocks);
+        k.take(a.schur_part, 42 * (size_t)a.n_chunks * a.n_pairs);
+        k.take(a.S, D * D); k.take(a.rhs, D); k.take(a.gc, D); k.take(a.udiag, D); k.take(a.chol, D * (D + 1) / 2); k.take(a.delta_c, D);
+        k.take(a.upd_part, 3 * (size_t)a.n_lin_blocks); k.take(a.scalars, RIG_N_SCALARS);
+        return k.used;
+    };
+    const size_t need = carve(nullptr);
+    if (need > c->rig_scratch.n) TRY(c->rig_scratch.reserve(need * 2));
+    carve(c->rig_scratch);
     return 0;
 }
 
@@ -1669,24 +1673,24 @@ static int intr_args(mocap_ctx* c, int n_cams, const int32_t* view_offset, const
     }
     a = IntrArgs{};
     a.n_cams = n_cams; a.n_views = n_views; a.obj = obj; a.img = img;
-    size_t used = 0;
-    auto take = [&used](size_t bytes) { const size_t at = used; used += (bytes + 15) & ~(size_t)15; return at; };
     const size_t nc = n_cams, nv = n_views;
-    const size_t o_int = take(4 * n_int), o_state = take(sizeof(IntrState) * nc), o_kd = take(8 * 2 * 9 * nc), o_poses = take(8 * 2 * 12 * nv);
-    const size_t o_vcost = take(8 * 2 * nv), o_H = take(8 * 9 * nv), o_rec = take(8 * (size_t)INTR_REC * nv), o_gc = take(8 * 9 * nc), o_gv = take(8 * 6 * nv);
-    const size_t o_S = take(8 * 81 * nc), o_rhs = take(8 * 9 * nc), o_udiag = take(8 * 9 * nc), o_delta = take(8 * 9 * nc);
-    const size_t o_lcost = take(8 * nc), o_cpart = take(8 * 2 * nc), o_upd = take(8 * 3 * nv);
-    if (used > c->intr_scratch.n) TRY(c->intr_scratch.reserve(used * 2));
-    char* const b = c->intr_scratch;
-    int32_t* d_int = (int32_t*)(b + o_int);
+    int32_t* d_int;
+    auto carve = [&](char* base) {
+        Carver k{base};
+        k.take(d_int, n_int); k.take(a.state, nc); k.take(a.kd, 2 * 9 * nc); k.take(a.poses, 2 * 12 * nv); k.take(a.view_cost, 2 * nv);
+        k.take(a.H, 9 * nv); k.take(a.rec, (size_t)INTR_REC * nv);
+        k.take(a.gc, 9 * nc); k.take(a.gv, 6 * nv); k.take(a.S, 81 * nc); k.take(a.rhs, 9 * nc); // mocap_intrinsics_linearize clears
+        k.take(a.udiag, 9 * nc);                                                                 // these four as one span up to udiag
+        k.take(a.delta_c, 9 * nc); k.take(a.lin_cost, nc); k.take(a.cam_part, 2 * nc); k.take(a.upd_part, 3 * nv);
+        return k.used;
+    };
+    const size_t need = carve(nullptr);
+    if (need > c->intr_scratch.n) TRY(c->intr_scratch.reserve(need * 2));
+    carve(c->intr_scratch);
     // pageable host memory: the copy has left `host` when this returns
     HIP_TRY(hipMemcpyAsync(d_int, host.data(), 4 * n_int, hipMemcpyHostToDevice, s));
     a.view_offset = d_int; a.point_offset = d_int + (h_poff - h_voff); a.view_cam = d_int + (h_vcam - h_voff);
     a.image_size = d_int + (h_size - h_voff); a.cam_bad = d_int + (h_bad - h_voff);
-    a.state = (IntrState*)(b + o_state); a.kd = (double*)(b + o_kd); a.poses = (double*)(b + o_poses); a.view_cost = (double*)(b + o_vcost);
-    a.H = (double*)(b + o_H); a.rec = (double*)(b + o_rec); a.gc = (double*)(b + o_gc); a.gv = (double*)(b + o_gv); a.S = (double*)(b + o_S);
-    a.rhs = (double*)(b + o_rhs); a.udiag = (double*)(b + o_udiag); a.delta_c = (double*)(b + o_delta); a.lin_cost = (double*)(b + o_lcost);
-    a.cam_part = (double*)(b + o_cpart); a.upd_part = (double*)(b + o_upd);
     HIP_TRY(hipMemsetAsync(a.state, 0, sizeof(IntrState) * nc, s));
     return 0;
 }

@@ -3,8 +3,8 @@
 //
 // Replaces reference CalculateCameraIntrinsic.py:58, cv2.calibrateCamera(objpoints, imgpoints, size, None, None), for all
 // cameras in one call.  OpenCV's iteration is not reproduced: the contract is the definition of DESIGN.md section 2, restated in
-// NumPy by tests/intrinsics_ref.py.  The projection is that of `observe` in rig_ba.hip with a board point (X, Y, 0): the same
-// operations in the same order (the third product of its sums is an exact zero and is left out).
+// NumPy by tests/intrinsics_ref.py.  The camera model with its derivatives and the step-control rule are lm.h's, shared with
+// rig_ba.hip; a board point is (X, Y, 0), and the third product of R X, an exact zero, is left out.
 // The library is built with -ffp-contract=off: every product and sum below is rounded on its own.  No floating-point atomics
 // anywhere: a view's sums run over its points in ascending order, a camera's over its views in ascending order, lanes join by
 // the fixed shuffle tree of wave_sum.  Two runs give the same bits, and a camera's result does not depend on the cameras it is
@@ -25,22 +25,18 @@
 //   intr_solve_kernel       a workgroup per camera: the views' records in ascending order into S and the reduced right-hand
 //                           side; Cholesky of S, the camera step, the trial intrinsics
 //   intr_update_kernel      a wave per view: back-substitution, the trial pose, the trial cost
-//   intr_decide_kernel      a workgroup per camera: rig_decide_kernel's rules (gain ratio, Nielsen's update, stops, history)
+//   intr_decide_kernel      a workgroup per camera: lm_decide (gain ratio, accept / reject, Nielsen's update, stops, history)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "kernels.h"
+#include "lm.h"
 #include "jacobi9.h"
 
 namespace mocap {
 
 namespace {
 
-constexpr double HUGE_D = 1.7976931348623157e308;
-__device__ __forceinline__ bool finite(double x) { return fabs(x) <= HUGE_D; } // false for NaN
-
-__device__ __forceinline__ constexpr int low(int i, int j) { return i * (i + 1) / 2 + j; }                 // packed lower triangle, j <= i
-__device__ __forceinline__ constexpr int up16(int i, int j) { return i * 16 - i * (i - 1) / 2 + (j - i); } // the view's sums, i <= j
-__device__ __forceinline__ constexpr int up9(int i, int j) { return i * 9 - i * (i - 1) / 2 + (j - i); }
+__device__ __forceinline__ constexpr int up16(int i, int j) { return tri(i, j, 16); } // the view's 136 sums, i <= j
 
 // In-place Cholesky A = L L^T on the packed lower triangle, column by column; every index a constant, the matrix in registers.
 // False when a pivot is not positive and finite (the factor then holds NaN).
@@ -53,7 +49,7 @@ __device__ __forceinline__ bool cholesky(double* L)
         double s = L[low(j, j)];
 #pragma unroll
         for (int k = 0; k < j; k++) s = s - L[low(j, k)] * L[low(j, k)];
-        ok = ok && s > 0.0 && s <= HUGE_D;
+        ok = ok && s > 0.0 && finite(s);
         const double d = sqrt(s);
         L[low(j, j)] = d;
 #pragma unroll
@@ -93,36 +89,17 @@ __device__ __forceinline__ void cholesky_solve(const double* L, double* x)
 template <bool JAC>
 __device__ __forceinline__ bool observe_board(const double* kd, const double* P, double X, double Y, double ou, double ov, double r[2], double* j0, double* j1)
 {
-    const double fx = kd[0], fy = kd[1], cx = kd[2], cy = kd[3], k1 = kd[4], k2 = kd[5], p1 = kd[6], p2 = kd[7], k3 = kd[8];
-    const double q0 = P[0] * X + P[1] * Y, q1 = P[3] * X + P[4] * Y, q2 = P[6] * X + P[7] * Y;
-    const double px = q0 + P[9], py = q1 + P[10], pz = q2 + P[11];
-    const bool front = pz > 0.0;
-    const double x = px / pz, y = py / pz;
-    const double xx = x * x, yy = y * y, xy = x * y;
-    const double r2 = xx + yy, r4 = r2 * r2, r6 = r4 * r2;
-    const double cd = ((1.0 + k1 * r2) + k2 * r4) + k3 * r6;
-    const double tx = r2 + 2.0 * xx, ty = r2 + 2.0 * yy;
-    const double xd = (x * cd + (2.0 * p1) * xy) + p2 * tx;
-    const double yd = (y * cd + p1 * ty) + (2.0 * p2) * xy;
-    r[0] = (fx * xd + cx) - ou;
-    r[1] = (fy * yd + cy) - ov;
+    const Lens m{kd[0], kd[1], kd[2], kd[3], kd[4], kd[5], kd[6], kd[7], kd[8]};
+    const double q[3] = {P[0] * X + P[1] * Y, P[3] * X + P[4] * Y, P[6] * X + P[7] * Y};
+    Projected o;
+    const bool front = project<JAC>(m, q, P + 9, ou, ov, r, o);
     if (JAC) {
-        j0[0] = xd; j0[1] = 0.0; j0[2] = 1.0; j0[3] = 0.0;
-        j1[0] = 0.0; j1[1] = yd; j1[2] = 0.0; j1[3] = 1.0;
-        j0[4] = fx * (x * r2); j0[5] = fx * (x * r4); j0[6] = fx * (2.0 * xy); j0[7] = fx * tx; j0[8] = fx * (x * r6);
-        j1[4] = fy * (y * r2); j1[5] = fy * (y * r4); j1[6] = fy * ty; j1[7] = fy * (2.0 * xy); j1[8] = fy * (y * r6);
-        const double e = (k1 + (2.0 * k2) * r2) + (3.0 * k3) * r4;
-        const double a00 = ((cd + (2.0 * xx) * e) + (2.0 * p1) * y) + (6.0 * p2) * x;
-        const double a01 = ((2.0 * xy) * e + (2.0 * p1) * x) + (2.0 * p2) * y;
-        const double a11 = ((cd + (2.0 * yy) * e) + (6.0 * p1) * y) + (2.0 * p2) * x;
-        const double b00 = fx * a00, b01 = fx * a01, b10 = fy * a01, b11 = fy * a11;
-        const double iz = 1.0 / pz;
-        const double A00 = b00 * iz, A01 = b01 * iz, A02 = -((b00 * x + b01 * y) * iz);
-        const double A10 = b10 * iz, A11 = b11 * iz, A12 = -((b10 * x + b11 * y) * iz);
-        j0[9] = A02 * q1 - A01 * q2; j0[10] = A00 * q2 - A02 * q0; j0[11] = A01 * q0 - A00 * q1; // A (-[R X]x)
-        j1[9] = A12 * q1 - A11 * q2; j1[10] = A10 * q2 - A12 * q0; j1[11] = A11 * q0 - A10 * q1;
-        j0[12] = A00; j0[13] = A01; j0[14] = A02;
-        j1[12] = A10; j1[13] = A11; j1[14] = A12;
+        j0[0] = o.xd; j0[1] = 0.0; j0[2] = 1.0; j0[3] = 0.0;
+        j1[0] = 0.0; j1[1] = o.yd; j1[2] = 0.0; j1[3] = 1.0;
+        j0[4] = m.fx * (o.x * o.r2); j0[5] = m.fx * (o.x * o.r4); j0[6] = m.fx * (2.0 * o.xy); j0[7] = m.fx * o.tx; j0[8] = m.fx * (o.x * o.r6);
+        j1[4] = m.fy * (o.y * o.r2); j1[5] = m.fy * (o.y * o.r4); j1[6] = m.fy * o.ty; j1[7] = m.fy * (2.0 * o.xy); j1[8] = m.fy * (o.y * o.r6);
+        pose_columns(o.A[0], q, j0 + 9);
+        pose_columns(o.A[1], q, j1 + 9);
     }
     return front;
 }
@@ -285,12 +262,7 @@ __global__ __launch_bounds__(64) void intr_linearize_kernel(IntrArgs a, int it)
     // the (up to) three of the 136 sums this lane owns: entry e = (i, j), i <= j, of the upper triangle row by row
     int ei[3], ej[3];
 #pragma unroll
-    for (int k = 0; k < 3; k++) {
-        int e = lane + 64 * k, i = 0;
-        if (e > 135) e = 135;
-        while (e >= 16 - i) { e -= 16 - i; i++; }
-        ei[k] = i; ej[k] = i + e;
-    }
+    for (int k = 0; k < 3; k++) tri_unrank(min(lane + 64 * k, 135), 16, ei[k], ej[k]);
     double acc[3] = {0, 0, 0};
     bool behind = false;
     for (int base = 0; base < n; base += 64) {
@@ -353,9 +325,9 @@ __global__ __launch_bounds__(64) void intr_linearize_kernel(IntrArgs a, int it)
     }
     __syncthreads();
     if (lane < 45) { // entry (i, j), i <= j, of Y W^T
-        int e = lane, i = 0;
-        while (e >= 9 - i) { e -= 9 - i; i++; }
-        const int j = i + e, row = j * 16 - j * (j - 1) / 2 - j;
+        int i, j;
+        tri_unrank(lane, 9, i, j);
+        const int row = j * 16 - j * (j - 1) / 2 - j;
         double t = 0;
 #pragma unroll
         for (int k = 0; k < 6; k++) t += s_Y[6 * i + k] * s_sum[row + 9 + k];
@@ -381,9 +353,8 @@ __global__ __launch_bounds__(64) void intr_solve_kernel(IntrArgs a, int it, int 
     const double lambda = st->lambda;
     const bool view_fail = st->chol_fail != 0;
     if (tid < 45) { // entry (i, j), i <= j, of S = U* - sum_v W V*^-1 W^T: the views in ascending order
-        int e = tid, i = 0;
-        while (e >= 9 - i) { e -= 9 - i; i++; }
-        const int j = i + e;
+        int i, j;
+        tri_unrank(tid, 9, i, j);
         double u = 0, t = 0;
         for (int v = v0; v < v1; v++) {
             const double* rec = a.rec + (size_t)INTR_REC * v;
@@ -423,7 +394,7 @@ __global__ __launch_bounds__(64) void intr_solve_kernel(IntrArgs a, int it, int 
 #pragma unroll
     for (int i = 0; i < 9; i++)
 #pragma unroll
-        for (int j = 0; j <= i; j++) L[low(i, j)] = s_S[up9(j, i)];
+        for (int j = 0; j <= i; j++) L[low(i, j)] = s_S[tri(j, i, 9)];
     if (!cholesky<9>(L)) { st->chol_fail = 1; return; }
 #pragma unroll
     for (int i = 0; i < 9; i++) d[i] = s_rhs[i];
@@ -502,44 +473,14 @@ __global__ __launch_bounds__(64) void intr_update_kernel(IntrArgs a)
     }
 }
 
-// A workgroup per camera, one thread decides: rig_decide_kernel's rules.  history[c][it] = (cost after the decision, the lambda
-// the step was solved with, accepted, |step|).
+// A workgroup per camera: one thread decides by lm_decide over the partials of the camera's views.  history[c][it] is its row.
 __global__ __launch_bounds__(64) void intr_decide_kernel(IntrArgs a, int it, double ftol)
 {
     const int c = blockIdx.x;
     IntrState* st = a.state + c;
     if (st->stop || threadIdx.x != 0) return;
-    const double lambda = st->lambda;
-    double* h = a.history + 4 * ((size_t)c * a.max_iters + it);
-    bool accepted = false;
-    double step = 0;
-    int stop = 0;
-    if (st->chol_fail) {
-        if (st->chol_fail_prev) stop = RIG_STOP_CHOLESKY;
-        st->chol_fail_prev = 1;
-    } else {
-        st->chol_fail_prev = 0;
-        double cs = 0, p = 0, n2 = 0;
-        for (int v = a.view_offset[c]; v < a.view_offset[c + 1]; v++) { cs += a.upd_part[3 * (size_t)v]; p += a.upd_part[3 * (size_t)v + 1]; n2 += a.upd_part[3 * (size_t)v + 2]; }
-        const double trial = 0.5 * cs, pred = 0.5 * (p + a.cam_part[2 * (size_t)c]);
-        step = sqrt(n2 + a.cam_part[2 * (size_t)c + 1]);
-        const double rho = (st->cost - trial) / pred;
-        accepted = !st->trial_behind && rho > 0.0; // NaN: rejected
-        if (accepted) {
-            const double rel = (st->cost - trial) / st->cost, f = 2.0 * rho - 1.0, g = 1.0 - (f * f) * f;
-            st->cost = trial; st->cur = 1 - st->cur;
-            st->lambda = lambda * (g > 1.0 / 3.0 ? g : 1.0 / 3.0); st->nu = 2.0;
-            if (rel < ftol) stop = RIG_STOP_FTOL;
-        }
-    }
-    if (!accepted) {
-        st->lambda = lambda * st->nu; st->nu = 2.0 * st->nu;
-        if (!stop && st->lambda > 1e16) stop = RIG_STOP_LAMBDA;
-    }
-    if (!stop && it + 1 == a.max_iters) stop = RIG_STOP_MAX_ITERS;
-    h[0] = st->cost; h[1] = lambda; h[2] = accepted ? 1.0 : 0.0; h[3] = step;
-    st->iters = it + 1; st->chol_fail = 0; st->trial_behind = 0;
-    if (stop) { st->stop = 1; st->status = stop; }
+    const int v0 = a.view_offset[c], v1 = a.view_offset[c + 1];
+    lm_decide(st, a.upd_part + 3 * (size_t)v0, v1 - v0, a.cam_part + 2 * (size_t)c, it, a.max_iters, ftol, a.history + 4 * ((size_t)c * a.max_iters + it));
 }
 
 // The record, and for a camera with a positive status the caller's arrays; a failed camera's stay as they were.

@@ -41,23 +41,6 @@ __device__ __forceinline__ double block_sum(double v, double* s_part /*[4]*/)
     return (s_part[0] + s_part[1]) + (s_part[2] + s_part[3]);
 }
 
-// R <- Exp(w) R by Rodrigues' formula: the local rotation update of the two Levenberg-Marquardt loops (rig_ba.hip, intrinsics.hip)
-__device__ __forceinline__ void rotate_left(const double w[3], const double R[9], double out[9])
-{
-    const double th2 = (w[0] * w[0] + w[1] * w[1]) + w[2] * w[2], th = sqrt(th2);
-    const double ka = th < 1e-12 ? 1.0 : sin(th) / th, kb = th < 1e-12 ? 0.5 : (1.0 - cos(th)) / th2;
-    // E = I + ka K + kb K^2, K = [w]x, K^2 = w w^T - th2 I
-    double E[9];
-    E[0] = 1.0 + kb * (w[0] * w[0] - th2); E[4] = 1.0 + kb * (w[1] * w[1] - th2); E[8] = 1.0 + kb * (w[2] * w[2] - th2);
-    E[1] = kb * (w[0] * w[1]) - ka * w[2]; E[3] = kb * (w[0] * w[1]) + ka * w[2];
-    E[2] = kb * (w[0] * w[2]) + ka * w[1]; E[6] = kb * (w[0] * w[2]) - ka * w[1];
-    E[5] = kb * (w[1] * w[2]) - ka * w[0]; E[7] = kb * (w[1] * w[2]) + ka * w[0];
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) out[3 * i + j] = (E[3 * i] * R[j] + E[3 * i + 1] * R[3 + j]) + E[3 * i + 2] * R[6 + j];
-}
-
 void launch_mask_convert(const uint32_t* src, uint32_t* dst, int n_images, int H, int wpr, bool to_blocked, hipStream_t s);
 
 // The dense filter kernel (any geometry, any lens model): every tile of every image, the undistortion as a gather in the
@@ -364,17 +347,23 @@ struct FundArgs {
     int32_t* status;           // [n_pairs][2] (winner, inliers) or (FUND_ERR_*, 0)
 };
 
-// bundle adjustment of a rig (rig_ba.hip).  The state record of one call: written by single-workgroup kernels only (the two
-// flags `behind` and `trial_behind` by integer atomicOr), read by every kernel of the iterations that follow.
-struct RigState {
+// The state record of one Levenberg-Marquardt loop (lm.h holds its rule): written by single-workgroup kernels only (the flags
+// `behind`, `trial_behind` and, where several workgroups factorise, `chol_fail` also by integer atomicOr), read by every kernel
+// of the iterations that follow.
+struct LmState {
     double lambda, nu;         // Marquardt damping and Nielsen's growth factor
     double cost, cost0;        // 1/2 sum r^2 of the current state, and of the state handed in
-    double t1_norm;            // |t_1| handed in: the gauge restored on return
-    int32_t stop, status;      // stop != 0: every later kernel returns at once; status: RIG_STOP_* / RIG_ERR_*
-    int32_t iters, cur;        // iterations done; which of the two pose / point buffers holds the current state
-    int32_t chol_fail, chol_fail_prev, behind, trial_behind, layout_err, pad;
+    int32_t stop, status;      // stop != 0: every later kernel of this loop returns at once; status: RIG_STOP_* or the solver's error
+    int32_t iters, cur;        // iterations done; which of the two state buffers holds the current state
+    int32_t chol_fail, chol_fail_prev, behind, trial_behind;
 };
-enum { RIG_LIN_COST = 0, RIG_PRED_CAM = 1, RIG_NORM2_CAM = 2, RIG_N_SCALARS = 4 };
+
+// bundle adjustment of a rig (rig_ba.hip): one loop per call
+struct RigState : LmState {
+    double t1_norm;            // |t_1| handed in: the gauge restored on return
+    int32_t layout_err, pad;
+};
+enum { RIG_LIN_COST = 0, RIG_PRED_CAM = 1, RIG_NORM2_CAM = 2, RIG_N_SCALARS = 4 }; // (PRED_CAM, NORM2_CAM: lm_decide's `cam` pair)
 enum { RIG_STOP_MAX_ITERS = 1, RIG_STOP_FTOL = 2, RIG_STOP_LAMBDA = 3, RIG_STOP_CHOLESKY = 4, RIG_ERR_LAYOUT = -2, RIG_ERR_BEHIND = -3 };
 
 struct RigArgs {
@@ -417,16 +406,9 @@ void launch_rig_finish(const RigArgs& a, hipStream_t s);
 int rig_lin_blocks(int N);
 int rig_schur_chunks(int N);
 
-// intrinsic calibration of every camera of a rig from planar-board views (intrinsics.hip).  One state record per camera,
-// written by that camera's single-workgroup kernels only (the flags `behind`, `trial_behind` and `chol_fail` also by integer
-// atomicOr from its views' waves), read by every kernel of the iterations that follow.  The stop values are RIG_STOP_*.
-struct IntrState {
-    double lambda, nu;         // Marquardt damping and Nielsen's growth factor
-    double cost, cost0;        // 1/2 sum r^2 of the current state, and of the start
-    int32_t stop, status;      // stop != 0: every later kernel returns at once for this camera; status: RIG_STOP_* / INTR_ERR_*
-    int32_t iters, cur;        // iterations done; which of the two state buffers holds the current state
-    int32_t chol_fail, chol_fail_prev, behind, trial_behind;
-};
+// intrinsic calibration of every camera of a rig from planar-board views (intrinsics.hip): one loop, and one state record, per
+// camera; no kernel reads another camera's.  status: RIG_STOP_* / INTR_ERR_*
+using IntrState = LmState;
 enum { INTR_ERR_LAYOUT = -2, INTR_ERR_BEHIND = -3, INTR_ERR_DEGENERATE = -4 };
 // A view's record, in doubles: the 136 sums of [J r]^T [J r] (16 columns: kd's 9, the pose's 6, r; upper triangle row by row),
 // then the upper triangle of W V*^-1 W^T (45), W V*^-1 g_v (9), the factor of V* (packed lower triangle, 21)

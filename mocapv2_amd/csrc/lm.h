@@ -1,0 +1,124 @@
+// lm.h -- what the two Levenberg-Marquardt solvers (rig_ba.hip, intrinsics.hip) share, each defined once: the camera model
+// with its derivatives, the step-control rule over the state record LmState of kernels.h (both: DESIGN.md section 2, restated
+// by tests/lm_ref.py), and the small index helpers of their packed triangles.
+// The library is built with -ffp-contract=off: every product and sum below is rounded on its own, and the restatement forms
+// each value by the same operations in the same order.
+#pragma once
+#include "kernels.h"
+
+namespace mocap {
+
+__device__ __forceinline__ bool finite(double x) { return fabs(x) <= 1.7976931348623157e308; } // false for NaN
+
+__device__ __forceinline__ constexpr int low(int i, int j) { return i * (i + 1) / 2 + j; } // packed lower triangle, j <= i
+// position of element (i, j), i <= j, of a symmetric n x n stored as its upper triangle row by row, and the inverse: rank e -> (i, j)
+__device__ __forceinline__ constexpr int tri(int i, int j, int n) { return i * n - i * (i - 1) / 2 + (j - i); }
+__device__ __forceinline__ void tri_unrank(int e, int n, int& i, int& j)
+{
+    for (i = 0; e >= n - i; i++) e -= n - i;
+    j = i + e;
+}
+
+// R <- Exp(w) R by Rodrigues' formula: the local rotation update of both loops
+__device__ __forceinline__ void rotate_left(const double w[3], const double R[9], double out[9])
+{
+    const double th2 = (w[0] * w[0] + w[1] * w[1]) + w[2] * w[2], th = sqrt(th2);
+    const double ka = th < 1e-12 ? 1.0 : sin(th) / th, kb = th < 1e-12 ? 0.5 : (1.0 - cos(th)) / th2;
+    // E = I + ka K + kb K^2, K = [w]x, K^2 = w w^T - th2 I
+    double E[9];
+    E[0] = 1.0 + kb * (w[0] * w[0] - th2); E[4] = 1.0 + kb * (w[1] * w[1] - th2); E[8] = 1.0 + kb * (w[2] * w[2] - th2);
+    E[1] = kb * (w[0] * w[1]) - ka * w[2]; E[3] = kb * (w[0] * w[1]) + ka * w[2];
+    E[2] = kb * (w[0] * w[2]) + ka * w[1]; E[6] = kb * (w[0] * w[2]) - ka * w[1];
+    E[5] = kb * (w[1] * w[2]) - ka * w[0]; E[7] = kb * (w[1] * w[2]) + ka * w[0];
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) out[3 * i + j] = (E[3 * i] * R[j] + E[3 * i + 1] * R[3 + j]) + E[3 * i + 2] * R[6 + j];
+}
+
+// The lens: pinhole + Brown distortion.
+struct Lens { double fx, fy, cx, cy, k1, k2, p1, p2, k3; };
+
+// What project() leaves behind for the Jacobians its callers build: the normalised point and its powers, the tangential
+// terms tx = r2 + 2 x^2, ty = r2 + 2 y^2, the distorted point, and with JAC the 2x3 A = d pixel / d (q + t).
+struct Projected { double x, y, xy, r2, r4, r6, tx, ty, xd, yd, A[2][3]; };
+
+// One point q + t in the camera frame (q = R X, formed by the caller) against its pixel (ou, ov): the residual r.  Returns
+// false when the point is not in front of the camera (z <= 0 or NaN).
+template <bool JAC>
+__device__ __forceinline__ bool project(const Lens& m, const double q[3], const double t[3], double ou, double ov, double r[2], Projected& o)
+{
+    const double px = q[0] + t[0], py = q[1] + t[1], pz = q[2] + t[2];
+    const bool front = pz > 0.0;
+    const double x = px / pz, y = py / pz;
+    const double xx = x * x, yy = y * y, xy = x * y;
+    const double r2 = xx + yy, r4 = r2 * r2, r6 = r4 * r2;
+    const double cd = ((1.0 + m.k1 * r2) + m.k2 * r4) + m.k3 * r6;
+    const double tx = r2 + 2.0 * xx, ty = r2 + 2.0 * yy;
+    const double xd = (x * cd + (2.0 * m.p1) * xy) + m.p2 * tx;
+    const double yd = (y * cd + m.p1 * ty) + (2.0 * m.p2) * xy;
+    r[0] = (m.fx * xd + m.cx) - ou;
+    r[1] = (m.fy * yd + m.cy) - ov;
+    if (JAC) {
+        o.x = x; o.y = y; o.xy = xy; o.r2 = r2; o.r4 = r4; o.r6 = r6; o.tx = tx; o.ty = ty; o.xd = xd; o.yd = yd;
+        const double e = (m.k1 + (2.0 * m.k2) * r2) + (3.0 * m.k3) * r4;
+        const double a00 = ((cd + (2.0 * xx) * e) + (2.0 * m.p1) * y) + (6.0 * m.p2) * x;
+        const double a01 = ((2.0 * xy) * e + (2.0 * m.p1) * x) + (2.0 * m.p2) * y;
+        const double a11 = ((cd + (2.0 * yy) * e) + (6.0 * m.p1) * y) + (2.0 * m.p2) * x;
+        const double b00 = m.fx * a00, b01 = m.fx * a01, b10 = m.fy * a01, b11 = m.fy * a11;
+        const double iz = 1.0 / pz;
+        o.A[0][0] = b00 * iz; o.A[0][1] = b01 * iz; o.A[0][2] = -((b00 * x + b01 * y) * iz);
+        o.A[1][0] = b10 * iz; o.A[1][1] = b11 * iz; o.A[1][2] = -((b10 * x + b11 * y) * iz);
+    }
+    return front;
+}
+
+// One row of the pose Jacobian under the local perturbation R <- Exp(w) R, t <- t + dt, from the same row of A: the columns
+// w = A (-[q]x), then dt = A
+__device__ __forceinline__ void pose_columns(const double A[3], const double q[3], double j[6])
+{
+    j[0] = A[2] * q[1] - A[1] * q[2];
+    j[1] = A[0] * q[2] - A[2] * q[0];
+    j[2] = A[1] * q[0] - A[0] * q[1];
+    j[3] = A[0]; j[4] = A[1]; j[5] = A[2];
+}
+
+// The decision of iteration `it`, by one thread.  part [n][3]: the partials of the trial step (sum r^2 of the trial state, twice
+// the predicted reduction, |step|^2), summed here in ascending order, and only for a step that was solved; cam [2]: the
+// camera step's share of the last two.  Gain ratio, accept (flip the buffer index) / reject, Nielsen's damping update, the
+// four stops.  h = the history row (cost after the decision, the lambda the step was solved with, accepted, |step|).
+__device__ __forceinline__ void lm_decide(LmState* st, const double* part, int n, const double* cam, int it, int max_iters, double ftol, double* h)
+{
+    const double lambda = st->lambda;
+    bool accepted = false;
+    double step = 0;
+    int stop = 0;
+    if (st->chol_fail) {
+        if (st->chol_fail_prev) stop = RIG_STOP_CHOLESKY;
+        st->chol_fail_prev = 1;
+    } else {
+        st->chol_fail_prev = 0;
+        double c = 0, p = 0, n2 = 0;
+        for (int b = 0; b < n; b++) { c += part[3 * (size_t)b]; p += part[3 * (size_t)b + 1]; n2 += part[3 * (size_t)b + 2]; }
+        const double trial = 0.5 * c, pred = 0.5 * (p + cam[0]);
+        step = sqrt(n2 + cam[1]);
+        const double rho = (st->cost - trial) / pred;
+        accepted = !st->trial_behind && rho > 0.0; // NaN: rejected
+        if (accepted) {
+            const double rel = (st->cost - trial) / st->cost, f = 2.0 * rho - 1.0, g = 1.0 - (f * f) * f;
+            st->cost = trial; st->cur = 1 - st->cur;
+            st->lambda = lambda * (g > 1.0 / 3.0 ? g : 1.0 / 3.0); st->nu = 2.0;
+            if (rel < ftol) stop = RIG_STOP_FTOL;
+        }
+    }
+    if (!accepted) {
+        st->lambda = lambda * st->nu; st->nu = 2.0 * st->nu;
+        if (!stop && st->lambda > 1e16) stop = RIG_STOP_LAMBDA;
+    }
+    if (!stop && it + 1 == max_iters) stop = RIG_STOP_MAX_ITERS;
+    h[0] = st->cost; h[1] = lambda; h[2] = accepted ? 1.0 : 0.0; h[3] = step;
+    st->iters = it + 1; st->chol_fail = 0; st->trial_behind = 0;
+    if (stop) { st->stop = 1; st->status = stop; }
+}
+
+} // namespace mocap

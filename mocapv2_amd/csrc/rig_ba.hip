@@ -6,6 +6,7 @@
 // is the definition of DESIGN.md section 2, restated in NumPy by tests/rig_ba_ref.py.  Observations are point-major
 // (obs_offset [N + 1], obs_cam, obs_uv), a point's cameras in ascending order; rig_init_kernel checks that and turns each
 // point's camera list into a 32-bit visibility mask, which is all the later kernels index with.
+// The camera model with its derivatives and the step-control rule are lm.h's, shared with intrinsics.hip.
 // The library is built with -ffp-contract=off: every product and sum below is rounded on its own, and the restatement forms
 // every per-observation quantity by the same operations in the same order.  What differs is the order of the sums over
 // observations and points, which is fixed here: no floating-point atomics anywhere, a lane sums its own points in order,
@@ -22,10 +23,11 @@
 //   rig_solve_kernel      one workgroup: Cholesky of S (packed lower triangle: in LDS up to 90 rows, else in global memory),
 //                         the camera step, the trial poses
 //   rig_update_kernel     a lane owns a point: back-substitution, trial point, trial cost, predicted reduction
-//   rig_decide_kernel     one workgroup: gain ratio, accept / reject, Nielsen's damping update, the stopping rules, history
+//   rig_decide_kernel     one workgroup: lm_decide (gain ratio, accept / reject, Nielsen's damping update, the stops, history)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "kernels.h"
+#include "lm.h"
 
 namespace mocap {
 
@@ -35,7 +37,7 @@ constexpr int PT_THREADS = 256;     // points per workgroup of the point-owning 
 constexpr int SCHUR_CHUNK = 1024;   // points per workgroup of rig_schur_kernel
 constexpr int CHOL_LDS_ROWS = 90;   // 90 * 91 / 2 doubles = 32 760 bytes: C <= 16 factorises in LDS
 
-struct Cam { double R[9], t[3], fx, fy, cx, cy, k1, k2, p1, p2, k3; };
+struct Cam { double R[9], t[3]; Lens lens; };
 
 __device__ __forceinline__ Cam load_cam(const CameraTable* tab, const double* pose, int c)
 {
@@ -44,54 +46,33 @@ __device__ __forceinline__ Cam load_cam(const CameraTable* tab, const double* po
     for (int k = 0; k < 9; k++) m.R[k] = pose[12 * c + k];
 #pragma unroll
     for (int k = 0; k < 3; k++) m.t[k] = pose[12 * c + 9 + k];
-    m.fx = tab->K[c][0]; m.fy = tab->K[c][4]; m.cx = tab->K[c][2]; m.cy = tab->K[c][5];
-    m.k1 = tab->dist[c][0]; m.k2 = tab->dist[c][1]; m.p1 = tab->dist[c][2]; m.p2 = tab->dist[c][3]; m.k3 = tab->dist[c][4];
+    m.lens = Lens{tab->K[c][0], tab->K[c][4], tab->K[c][2], tab->K[c][5],
+                  tab->dist[c][0], tab->dist[c][1], tab->dist[c][2], tab->dist[c][3], tab->dist[c][4]};
     return m;
 }
 
 // One observation: residual r, and with JAC the 2x6 camera Jacobian jc (local pose perturbation R <- Exp(w) R, t <- t + dt:
-// columns w, dt) and the 2x3 point Jacobian jp.  Returns false when the point is not in front of the camera (z <= 0 or NaN).
+// columns w, dt) and the 2x3 point Jacobian jp = A R.  Returns false when the point is not in front of the camera (z <= 0 or NaN).
 template <bool JAC>
 __device__ __forceinline__ bool observe(const Cam& m, const double X[3], double ou, double ov, double r[2], double jc[2][6], double jp[2][3])
 {
-    const double q0 = (m.R[0] * X[0] + m.R[1] * X[1]) + m.R[2] * X[2];
-    const double q1 = (m.R[3] * X[0] + m.R[4] * X[1]) + m.R[5] * X[2];
-    const double q2 = (m.R[6] * X[0] + m.R[7] * X[1]) + m.R[8] * X[2];
-    const double px = q0 + m.t[0], py = q1 + m.t[1], pz = q2 + m.t[2];
-    const bool front = pz > 0.0;
-    const double x = px / pz, y = py / pz;
-    const double xx = x * x, yy = y * y, xy = x * y;
-    const double r2 = xx + yy, r4 = r2 * r2, r6 = r4 * r2;
-    const double cd = ((1.0 + m.k1 * r2) + m.k2 * r4) + m.k3 * r6;
-    const double xd = (x * cd + (2.0 * m.p1) * xy) + m.p2 * (r2 + 2.0 * xx);
-    const double yd = (y * cd + m.p1 * (r2 + 2.0 * yy)) + (2.0 * m.p2) * xy;
-    r[0] = (m.fx * xd + m.cx) - ou;
-    r[1] = (m.fy * yd + m.cy) - ov;
+    const double q[3] = {(m.R[0] * X[0] + m.R[1] * X[1]) + m.R[2] * X[2], (m.R[3] * X[0] + m.R[4] * X[1]) + m.R[5] * X[2],
+                         (m.R[6] * X[0] + m.R[7] * X[1]) + m.R[8] * X[2]};
+    Projected o;
+    const bool front = project<JAC>(m.lens, q, m.t, ou, ov, r, o);
     if (JAC) {
-        const double e = (m.k1 + (2.0 * m.k2) * r2) + (3.0 * m.k3) * r4;
-        const double a00 = ((cd + (2.0 * xx) * e) + (2.0 * m.p1) * y) + (6.0 * m.p2) * x;
-        const double a01 = ((2.0 * xy) * e + (2.0 * m.p1) * x) + (2.0 * m.p2) * y;
-        const double a11 = ((cd + (2.0 * yy) * e) + (6.0 * m.p1) * y) + (2.0 * m.p2) * x;
-        const double b00 = m.fx * a00, b01 = m.fx * a01, b10 = m.fy * a01, b11 = m.fy * a11;
-        const double iz = 1.0 / pz;
-        double A[2][3];
-        A[0][0] = b00 * iz; A[0][1] = b01 * iz; A[0][2] = -((b00 * x + b01 * y) * iz);
-        A[1][0] = b10 * iz; A[1][1] = b11 * iz; A[1][2] = -((b10 * x + b11 * y) * iz);
 #pragma unroll
         for (int i = 0; i < 2; i++) {
 #pragma unroll
-            for (int j = 0; j < 3; j++) jp[i][j] = (A[i][0] * m.R[j] + A[i][1] * m.R[3 + j]) + A[i][2] * m.R[6 + j];
-            jc[i][0] = A[i][2] * q1 - A[i][1] * q2; // A (-[R X]x)
-            jc[i][1] = A[i][0] * q2 - A[i][2] * q0;
-            jc[i][2] = A[i][1] * q0 - A[i][0] * q1;
-            jc[i][3] = A[i][0]; jc[i][4] = A[i][1]; jc[i][5] = A[i][2];
+            for (int j = 0; j < 3; j++) jp[i][j] = (o.A[i][0] * m.R[j] + o.A[i][1] * m.R[3 + j]) + o.A[i][2] * m.R[6 + j];
+            pose_columns(o.A[i], q, jc[i]);
         }
     }
     return front;
 }
 
-// position of element (i, j), i <= j, of a symmetric n x n stored as its upper triangle row by row
-__device__ __forceinline__ constexpr int tri(int i, int j, int n) { return i * n - i * (i - 1) / 2 + (j - i); }
+// the pair of free cameras of a workgroup of the Schur and the reduce kernel: pair index -> (ca, cb), 1 <= ca <= cb < C, row by row
+__device__ __forceinline__ void pair_cameras(int pair, int C, int& ca, int& cb) { tri_unrank(pair, C - 1, ca, cb); ca++; cb++; }
 
 // inverse of the symmetric 3x3 with upper triangle v[6] = (00, 01, 02, 11, 12, 22) by the adjugate; same layout out
 __device__ __forceinline__ void inv_sym3(const double v[6], double o[6])
@@ -241,9 +222,8 @@ __global__ __launch_bounds__(256) void rig_schur_kernel(RigArgs a)
     __shared__ double s_red[4][42];
     if (gated(a.state)) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, pair = blockIdx.x, chunk = blockIdx.y;
-    int ca = 1, rest = pair; // pair index -> (ca, cb), 1 <= ca <= cb < C, row by row
-    while (rest >= a.C - ca) { rest -= a.C - ca; ca++; }
-    const int cb = ca + rest;
+    int ca, cb;
+    pair_cameras(pair, a.C, ca, cb);
     const bool diag = ca == cb;
     const uint32_t both = (1u << ca) | (1u << cb);
     double acc[42];
@@ -291,9 +271,8 @@ __global__ __launch_bounds__(64) void rig_reduce_kernel(RigArgs a)
     __shared__ double s_blk[36];
     if (gated(a.state)) return;
     const int tid = threadIdx.x, pair = blockIdx.x, D = 6 * (a.C - 1);
-    int ca = 1, rest = pair;
-    while (rest >= a.C - ca) { rest -= a.C - ca; ca++; }
-    const int cb = ca + rest;
+    int ca, cb;
+    pair_cameras(pair, a.C, ca, cb);
     const bool diag = ca == cb;
     const double lambda = a.state->lambda;
     if (diag && tid < 27) {
@@ -334,8 +313,6 @@ __global__ __launch_bounds__(64) void rig_reduce_kernel(RigArgs a)
 
 namespace {
 
-__device__ __forceinline__ int low(int i, int j) { return i * (i + 1) / 2 + j; } // packed lower triangle, j <= i
-
 // In-place Cholesky S = L L^T on the packed lower triangle (right-looking), 256 threads; false when a pivot is not positive
 __device__ __forceinline__ bool cholesky_packed(double* L, int D)
 {
@@ -343,7 +320,7 @@ __device__ __forceinline__ bool cholesky_packed(double* L, int D)
     for (int k = 0; k < D; k++) {
         __syncthreads();
         const double d = L[low(k, k)];
-        if (!(d > 0.0) || !(d <= 1.7976931348623157e308)) return false; // uniform: every thread reads the same value
+        if (!(d > 0.0) || !finite(d)) return false; // uniform: every thread reads the same value
         const double sd = sqrt(d);
         __syncthreads();
         for (int i = k + tid; i < D; i += 256) L[low(i, k)] = i == k ? sd : L[low(i, k)] / sd;
@@ -388,7 +365,7 @@ __global__ __launch_bounds__(256) void rig_solve_kernel(RigArgs a, int it)
     if (gated(st)) return;
     const int tid = threadIdx.x, D = 6 * (a.C - 1);
     const double cost = a.scalars[RIG_LIN_COST];
-    if (st->behind || !(cost <= 1.7976931348623157e308)) { // the state handed in (a trial state with this flaw is never accepted)
+    if (st->behind || !finite(cost)) { // the state handed in (a trial state with this flaw is never accepted)
         __syncthreads();
         if (tid == 0) { st->stop = 1; st->status = RIG_ERR_BEHIND; st->cost = st->cost0 = cost; }
         return;
@@ -494,43 +471,12 @@ __global__ __launch_bounds__(PT_THREADS) void rig_update_kernel(RigArgs a)
     }
 }
 
-// One thread decides (definition: DESIGN.md section 2, Nielsen's rule).  history[it] = (cost after the decision, the lambda
-// the step was solved with, accepted, |step|).
+// One thread decides by lm_decide over the partials of the point kernel's workgroups.  history[it] is its row.
 __global__ __launch_bounds__(64) void rig_decide_kernel(RigArgs a, int it, int max_iters, double ftol)
 {
     RigState* st = a.state;
     if (gated(st) || threadIdx.x != 0) return;
-    const double lambda = st->lambda;
-    double* h = a.history + 4 * (size_t)it;
-    bool accepted = false;
-    double step = 0;
-    int stop = 0;
-    if (st->chol_fail) {
-        if (st->chol_fail_prev) stop = RIG_STOP_CHOLESKY;
-        st->chol_fail_prev = 1;
-    } else {
-        st->chol_fail_prev = 0;
-        double c = 0, p = 0, n2 = 0;
-        for (int b = 0; b < a.n_lin_blocks; b++) { c += a.upd_part[3 * (size_t)b]; p += a.upd_part[3 * (size_t)b + 1]; n2 += a.upd_part[3 * (size_t)b + 2]; }
-        const double trial = 0.5 * c, pred = 0.5 * (p + a.scalars[RIG_PRED_CAM]);
-        step = sqrt(n2 + a.scalars[RIG_NORM2_CAM]);
-        const double rho = (st->cost - trial) / pred;
-        accepted = !st->trial_behind && rho > 0.0; // NaN: rejected
-        if (accepted) {
-            const double rel = (st->cost - trial) / st->cost, f = 2.0 * rho - 1.0, g = 1.0 - (f * f) * f;
-            st->cost = trial; st->cur = 1 - st->cur;
-            st->lambda = lambda * (g > 1.0 / 3.0 ? g : 1.0 / 3.0); st->nu = 2.0;
-            if (rel < ftol) stop = RIG_STOP_FTOL;
-        }
-    }
-    if (!accepted) {
-        st->lambda = lambda * st->nu; st->nu = 2.0 * st->nu;
-        if (!stop && st->lambda > 1e16) stop = RIG_STOP_LAMBDA;
-    }
-    if (!stop && it + 1 == max_iters) stop = RIG_STOP_MAX_ITERS;
-    h[0] = st->cost; h[1] = lambda; h[2] = accepted ? 1.0 : 0.0; h[3] = step;
-    st->iters = it + 1; st->chol_fail = 0; st->trial_behind = 0;
-    if (stop) { st->stop = 1; st->status = stop; }
+    lm_decide(st, a.upd_part, a.n_lin_blocks, a.scalars + RIG_PRED_CAM, it, max_iters, ftol, a.history + 4 * (size_t)it);
 }
 
 // The gauge on return (every t and every X scaled so that |t_1| is what it was at the start), the caller's arrays, the record.
@@ -548,7 +494,7 @@ __global__ __launch_bounds__(256) void rig_finish_kernel(RigArgs a)
     const double* t1 = pose + 12 + 9;
     const double now = sqrt((t1[0] * t1[0] + t1[1] * t1[1]) + t1[2] * t1[2]);
     double s = st->t1_norm / now;
-    if (!(s > 0.0) || !(s <= 1.7976931348623157e308)) s = 1.0; // |t_1| = 0 at either end: no scale to restore
+    if (!(s > 0.0) || !finite(s)) s = 1.0; // |t_1| = 0 at either end: no scale to restore
     for (int i = gid; i < 12 * a.C; i += stride) a.poses_io[i] = i % 12 < 9 ? pose[i] : pose[i] * s;
     for (int i = gid; i < 3 * a.N; i += stride) a.points_io[i] = pts[i] * s;
 }

@@ -12,18 +12,20 @@ accept, lambda *= max(1/3, 1 - (2 rho - 1)^3), nu = 2; else lambda *= nu, nu *= 
 step; two in a row stop the loop.  Stops: max_iters, an accepted step with relative decrease < ftol, lambda > 1e16.  On
 return every t and X is scaled so that |t_1| is what it was at the start.
 
-Every per-observation quantity below is formed by the same operations in the same order as csrc/rig_ba.hip (the library
-is built without fused multiply-add), so the kernels differ from this file in the ORDER of the sums over observations and
-points only; `permuted` measures what that order is worth."""
+The camera model with its derivatives and the loop's control are tests/lm_ref.py's, shared with tests/intrinsics_ref.py as
+csrc/lm.h is shared by the two kernel files.  Every per-observation quantity is formed by the same operations in the same
+order as csrc/rig_ba.hip and csrc/lm.h (the library is built without fused multiply-add), so the kernels differ from this
+file in the ORDER of the sums over observations and points only; `permuted` measures what that order is worth."""
 import json
 import os
 
 import numpy as np
 
+import lm_ref
+from lm_ref import STOP_MAX_ITERS, STOP_FTOL, STOP_LAMBDA, STOP_CHOLESKY  # noqa: F401 (the tests read them from here)
 from mocapv2_amd import synth
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-STOP_MAX_ITERS, STOP_FTOL, STOP_LAMBDA, STOP_CHOLESKY = 1, 2, 3, 4
 
 
 class Problem:
@@ -54,36 +56,15 @@ def observe(prob, R, t, X):
     c, n = prob.cam, prob.pt
     Rm, tm, Xm = R[c], t[c], X[n]
     q = [(Rm[:, i, 0] * Xm[:, 0] + Rm[:, i, 1] * Xm[:, 1]) + Rm[:, i, 2] * Xm[:, 2] for i in range(3)]
-    px, py, pz = q[0] + tm[:, 0], q[1] + tm[:, 1], q[2] + tm[:, 2]
-    fx, fy, cx, cy = prob.K[c, 0, 0], prob.K[c, 1, 1], prob.K[c, 0, 2], prob.K[c, 1, 2]
-    k1, k2, p1, p2, k3 = (prob.dist[c, i] for i in range(5))
+    lens = [prob.K[c, 0, 0], prob.K[c, 1, 1], prob.K[c, 0, 2], prob.K[c, 1, 2]] + [prob.dist[c, i] for i in range(5)]
     with np.errstate(all="ignore"):
-        x, y = px / pz, py / pz
-        xx, yy, xy = x * x, y * y, x * y
-        r2 = xx + yy
-        r4 = r2 * r2
-        r6 = r4 * r2
-        cd = ((1.0 + k1 * r2) + k2 * r4) + k3 * r6
-        xd = (x * cd + (2.0 * p1) * xy) + p2 * (r2 + 2.0 * xx)
-        yd = (y * cd + p1 * (r2 + 2.0 * yy)) + (2.0 * p2) * xy
-        r = np.stack([(fx * xd + cx) - prob.uv[:, 0], (fy * yd + cy) - prob.uv[:, 1]], 1)
-        e = (k1 + (2.0 * k2) * r2) + (3.0 * k3) * r4
-        a00 = ((cd + (2.0 * xx) * e) + (2.0 * p1) * y) + (6.0 * p2) * x
-        a01 = ((2.0 * xy) * e + (2.0 * p1) * x) + (2.0 * p2) * y
-        a11 = ((cd + (2.0 * yy) * e) + (6.0 * p1) * y) + (2.0 * p2) * x
-        b = [[fx * a00, fx * a01], [fy * a01, fy * a11]]
-        iz = 1.0 / pz
-        A = [[b[i][0] * iz, b[i][1] * iz, -((b[i][0] * x + b[i][1] * y) * iz)] for i in range(2)]
+        r, front, A, _ = lm_ref.project(lens, q, [tm[:, 0], tm[:, 1], tm[:, 2]], prob.uv)
         jp = np.empty((len(c), 2, 3))
         jc = np.empty((len(c), 2, 6))
         for i in range(2):
             for j in range(3):
                 jp[:, i, j] = (A[i][0] * Rm[:, 0, j] + A[i][1] * Rm[:, 1, j]) + A[i][2] * Rm[:, 2, j]
-            jc[:, i, 0] = A[i][2] * q[1] - A[i][1] * q[2]
-            jc[:, i, 1] = A[i][0] * q[2] - A[i][2] * q[0]
-            jc[:, i, 2] = A[i][1] * q[0] - A[i][0] * q[1]
-            jc[:, i, 3], jc[:, i, 4], jc[:, i, 5] = A[i][0], A[i][1], A[i][2]
-        front = pz > 0.0
+            jc[:, i, :] = np.stack(lm_ref.pose_columns(A[i], q), 1)
     return r, jc, jp, front
 
 
@@ -251,49 +232,22 @@ def lm(prob, R, t, X, max_iters=50, ftol=1e-12, lambda0=1e-3):
     R, t, X = np.array(R, float), np.array(t, float).reshape(-1, 3), np.array(X, float)
     R[0], t[0] = np.eye(3), 0.0
     t1_norm = float(np.sqrt((t[1, 0] * t[1, 0] + t[1, 1] * t[1, 1]) + t[1, 2] * t[1, 2]))
-    lam, nu = float(lambda0), 2.0
-    cost, front = cost_of(prob, R, t, X)
-    if not front or not np.isfinite(cost):
+    cost0, front = cost_of(prob, R, t, X)
+    if not front or not np.isfinite(cost0):
         raise ValueError("the state handed in has a point behind a camera that sees it")
-    cost0, history, rhos, status, chol_prev = cost, [], [], STOP_MAX_ITERS, False
-    for it in range(max_iters):
-        lin = linearize(prob, R, t, X, lam)
-        step = schur_step(prob, lin, lam)
-        used, accepted, norm, stop = lam, False, 0.0, 0
+
+    def try_step(state, lam):
+        step = schur_step(prob, linearize(prob, *state, lam), lam)
         if step is None:
-            rhos.append(np.nan)
-            if chol_prev:
-                stop = STOP_CHOLESKY
-            chol_prev = True
-        else:
-            chol_prev = False
-            dc, dp, pred = step
-            norm = float(np.sqrt(np.sum(dp * dp) + np.sum(dc * dc)))
-            R2, t2, X2 = apply_step(prob, R, t, X, dc, dp)
-            trial, ok = cost_of(prob, R2, t2, X2)
-            with np.errstate(all="ignore"):
-                rho = (cost - trial) / pred
-            rhos.append(rho)
-            accepted = bool(ok and rho > 0.0)
-            if accepted:
-                with np.errstate(all="ignore"):
-                    rel = (cost - trial) / cost
-                R, t, X, cost = R2, t2, X2, trial
-                f = 2.0 * rho - 1.0
-                lam, nu = lam * max(1.0 / 3.0, 1.0 - (f * f) * f), 2.0
-                if rel < ftol:
-                    stop = STOP_FTOL
-        if not accepted:
-            lam, nu = lam * nu, 2.0 * nu
-            if not stop and lam > 1e16:
-                stop = STOP_LAMBDA
-        history.append((cost, used, 1.0 if accepted else 0.0, norm))
-        if stop:
-            status = stop
-            break
+            return None
+        dc, dp, pred = step
+        trial_state = apply_step(prob, *state, dc, dp)
+        return (trial_state, *cost_of(prob, *trial_state), pred, float(np.sqrt(np.sum(dp * dp) + np.sum(dc * dc))))
+
+    (R, t, X), cost, status, history, rho = lm_ref.control((R, t, X), cost0, try_step, max_iters, ftol, lambda0)
     R, t, X = rescale(R, t, X, t1_norm)
     return {"R": R, "t": t, "X": X, "status": status, "iterations": len(history), "cost_initial": cost0, "cost": cost,
-            "history": np.array(history).reshape(-1, 4), "rho": np.array(rhos)}
+            "history": history, "rho": rho}
 
 
 # ---- SciPy as the independent minimiser ---------------------------------------------------------------------------------

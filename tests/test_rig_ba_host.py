@@ -225,17 +225,20 @@ def test_without_a_gpu_the_python_surface_fails_loudly():
         cal.calibrate_rig(c["image_points"], c["valid"], c["scene"].camera_params)
 
 
-def test_new_kernels_use_no_scratch_memory_and_spill_nothing():
-    """The compiler's own metadata for rig_ba.hip (scratch/kernel_meta.py, no GPU needed): 0 bytes of scratch and 0 spilled
-    VGPRs for every kernel; the Cholesky's LDS stays under 64 KB."""
+@pytest.mark.parametrize("src, stems", [
+    ("rig_ba.hip", ("rig_init", "rig_linearize", "rig_schur", "rig_reduce", "rig_solve", "rig_update", "rig_decide", "rig_finish")),
+    ("intrinsics.hip", ("intr_begin", "intr_homography", "intr_start", "intr_linearize", "intr_solve", "intr_update", "intr_decide",
+                        "intr_finish"))], ids=["rig_ba", "intrinsics"])
+def test_new_kernels_use_no_scratch_memory_and_spill_nothing(src, stems):
+    """The compiler's own metadata for the two solver files (scratch/kernel_meta.py, no GPU needed): 0 bytes of scratch and 0
+    spilled VGPRs for every kernel; the LDS (the rig's Cholesky is the largest) stays under 64 KB."""
     spec = importlib.util.spec_from_file_location("kernel_meta", os.path.join(ROOT, "scratch", "kernel_meta.py"))
     km = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(km)
-    ks = km.kernels_of(os.path.join(km.CSRC, "rig_ba.hip"))
+    ks = km.kernels_of(os.path.join(km.CSRC, src))
     names = " ".join(k["name"] for k in ks)
-    for want in ("rig_init_kernel", "rig_linearize_kernel", "rig_schur_kernel", "rig_reduce_kernel", "rig_solve_kernel",
-                 "rig_update_kernel", "rig_decide_kernel", "rig_finish_kernel"):
-        assert want in names
+    for want in stems:
+        assert want + "_kernel" in names
     for k in ks:
         print(k)
         assert k["scratch"] == 0 and k["spill"] == 0 and k["lds"] <= 65536, k
