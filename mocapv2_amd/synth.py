@@ -9,6 +9,9 @@ import numpy as np
 
 MILD_DIST = (-0.10, 0.02, 1e-3, 1e-3, 0.0)
 ZERO_DIST = (0.0, 0.0, 0.0, 0.0, 0.0)
+# the lenses of MixedScene, camera c gets MIXED_DISTS[c % 4]: a barrel, the identity, a pincushion (-3 x MILD_DIST), and a
+# barrel with tangential terms of opposite signs and k3 != 0
+MIXED_DISTS = (MILD_DIST, ZERO_DIST, (0.30, -0.06, -3e-3, -3e-3, 0.0), (-0.25, 0.09, -2e-3, 1.5e-3, -0.01))
 
 
 def intrinsics(width, height):
@@ -67,14 +70,18 @@ class Scene:
         self.camera_params = [{"intrinsic_matrix": self.K.tolist(), "distortion_coef": self.dist.tolist()}
                               for _ in range(n_cam)]
 
+    def pixels(self, markers, cam, distorted=True):
+        """float64 [M,2] pixels of the markers in camera `cam`, through its lens or (distorted=False) as a pinhole"""
+        return project(markers, self.poses[cam], self.K, self.dist if distorted else ZERO_DIST)
+
     def markers(self, rng, n_markers, extent=0.5):
         return rng.uniform(-extent, extent, size=(n_markers, 3))
 
     def centroids(self, markers, rng=None, jitter=0.0):
         """Integer pixel centroids per camera (ideal detections), list of [M,2] int arrays."""
         out = []
-        for pose in self.poses:
-            px = project(markers, pose, self.K, ZERO_DIST)
+        for cam in range(self.n_cam):
+            px = self.pixels(markers, cam, distorted=False)
             if rng is not None and jitter:
                 px = px + rng.normal(0, jitter, px.shape)
             out.append(np.floor(px).astype(np.int64))
@@ -88,7 +95,7 @@ class Scene:
         if salt > 0:
             n = int(salt * H * W)
             img[rng.integers(0, H, n), rng.integers(0, W, n)] = 255
-        px = project(markers, self.poses[cam], self.K, self.dist if distorted else ZERO_DIST)
+        px = self.pixels(markers, cam, distorted)
         radii = rng.uniform(radius_range[0], radius_range[1], size=len(markers))
         for (u, v), r in zip(px, radii):
             x0, x1 = int(np.floor(u - r - 2)), int(np.ceil(u + r + 2)) + 1
@@ -113,3 +120,40 @@ class Scene:
             for j, c in enumerate(cams):
                 out[t, j] = self.render(rng, mk, c, **kw)
         return out
+
+
+def mixed_intrinsics(n_cam, width, height):
+    """[n_cam] intrinsic matrices for one image size, no two alike: fx from 0.8 to 1.25 times intrinsics()'s focal length
+    (a spread of 1.56) in the zigzag order 0, n-1, 1, n-2, ... so that neighbours differ most, fy 2 % to 2 n % above fx,
+    principal points 1.5 % to 7.5 % of the width and up to 5 % of the height off the centre, to either side."""
+    f = 1400.0 * width / 1920.0
+    Ks = []
+    for c in range(n_cam):
+        rank = c // 2 if c % 2 == 0 else n_cam - 1 - c // 2
+        fx = f * (0.8 + 0.45 * rank / max(1, n_cam - 1))
+        fy = fx * (1.0 + 0.02 * (c + 1))
+        cx = width / 2.0 + 0.015 * width * (c % 5 + 1) * (1 if c % 2 == 0 else -1)
+        cy = height / 2.0 + 0.02 * height * ((c + 2) % 5 - 2.5)
+        Ks.append(np.array([[fx, 0.0, cx], [0.0, fy, cy], [0.0, 0.0, 1.0]]))
+    return Ks
+
+
+class MixedScene(Scene):
+    """n_cam ring cameras of one image size, every camera with its own K (`Ks[c]`, mixed_intrinsics) and its own lens
+    (`dists[c]`, MIXED_DISTS in turn), with F(0->i) from Ks[0] and Ks[i].  Scene's counterpart for everything that must
+    tell the cameras apart: `camera_params`, `pixels`, `centroids`, `render` and `render_batch` use camera c's own K and
+    lens.  There is no `K` or `dist` attribute: code written for one shared camera fails on this scene, it does not quietly
+    take camera 0's."""
+
+    def __init__(self, n_cam, width=1920, height=1080, radius=3.0, Ks=None, dists=None):
+        self.n_cam, self.width, self.height = n_cam, width, height
+        self.Ks = [np.array(k, float) for k in (mixed_intrinsics(n_cam, width, height) if Ks is None else Ks)]
+        self.dists = [np.array(MIXED_DISTS[c % len(MIXED_DISTS)] if dists is None else dists[c], float) for c in range(n_cam)]
+        assert len(self.Ks) == n_cam
+        self.poses = ring_cameras(n_cam, radius=radius)
+        self.Fs = [fundamental_from_poses(self.poses[0], self.poses[i], self.Ks[0], self.Ks[i]) for i in range(1, n_cam)]
+        self.camera_params = [{"intrinsic_matrix": self.Ks[c].tolist(), "distortion_coef": self.dists[c].tolist()}
+                              for c in range(n_cam)]
+
+    def pixels(self, markers, cam, distorted=True):
+        return project(markers, self.poses[cam], self.Ks[cam], self.dists[cam] if distorted else ZERO_DIST)

@@ -15,6 +15,8 @@ Provenance of every fixture (recorded in each file's `provenance` field):
 
 Usage:  python oracle/gen_golden.py            (writes tests/golden/)
         python oracle/gen_golden.py calib      (only tests/golden/calib_cheirality.npz)
+        python oracle/gen_golden.py mixed      (only the rigs of unequal cameras: corr_*_mixed*.npz, reproj_none_mixed.npz,
+                                                ba_residuals_mixed.npz)
 """
 import copy
 import json
@@ -197,11 +199,124 @@ def gen_calibration(H):
     print("calib_cheirality: counts", counts, "best", best)
 
 
+TRI_NONE_MASKS = [(1, 1, 1, 1), (0, 1, 1, 1), (1, 0, 1, 1), (1, 1, 0, 0), (0, 0, 1, 1), (1, 0, 0, 0), (0, 0, 0, 0)]
+
+
+def capture_residual_function(H, image_points, poses):
+    """residual_function of lib/Helpers.py:161-167, taken out of bundle_adjustment through a patched least_squares"""
+    captured = {}
+
+    def capture(fun, x0, **kw):
+        captured["fun"], captured["x0"] = fun, np.array(x0)
+
+        class R_:
+            x = np.array(x0)
+
+        return R_()
+
+    orig = H.optimize.least_squares
+    H.optimize.least_squares = capture
+    try:
+        H.bundle_adjustment(image_points, poses)
+    finally:
+        H.optimize.least_squares = orig
+    return captured["fun"], captured["x0"]
+
+
+def gen_mixed(H):
+    """Rigs whose cameras all differ in K and lens (mocapv2_amd.synth.MixedScene): a read of the wrong camera's intrinsics
+    changes every one of these outputs."""
+    from mocapv2_amd.synth import MixedScene, MIXED_DISTS  # noqa: E402
+
+    def mixed_case(name, C, M, seed, obj_count, jitter, drop=None, extra=0):
+        sc = MixedScene(C)
+        rng = np.random.default_rng(seed)
+        cents = sc.centroids(sc.markers(rng, M), rng, jitter)
+        lists = []
+        for c in range(C):
+            l = [[int(x), int(y)] for x, y in cents[c]]
+            if drop and c in drop:
+                l = l[: len(l) - drop[c]]
+            for _ in range(extra):
+                l.append([int(rng.integers(0, sc.width)), int(rng.integers(0, sc.height))])
+            lists.append([l[i] for i in rng.permutation(len(l))])
+        save_corr(name, H, lists, sc.poses, sc.camera_params, sc.Fs, obj_count,
+                  f"synthetic ring of unequal cameras (MixedScene) C={C} M={M} seed={seed}")
+
+    mixed_case("corr_c4_m6_mixed", 4, 6, 108, 6, jitter=0.5)
+    mixed_case("corr_c6_m8_mixed_clutter", 6, 8, 109, 8, jitter=0.7, drop={3: 2}, extra=3)
+
+    # triangulate_point and calculate_reprojection_error with [None, None] entries: both index camera_params by position after
+    # the entries are dropped (Helpers.py:59-61, :137-138); here the positions carry different K AND different lenses
+    sc = MixedScene(4)
+    rng = np.random.default_rng(17)
+    mk = sc.markers(rng, 6)
+    cents = sc.centroids(mk, rng, 0.5)
+    H.camera_params = np.array(sc.camera_params)
+    groups, tri, obj, mse = [], [], [], []
+    for m, msk in enumerate(TRI_NONE_MASKS):
+        g = [[int(cents[c][m % 6][0]), int(cents[c][m % 6][1])] if msk[c] else [None, None] for c in range(4)]
+        r = H.triangulate_point(copy.deepcopy(g), sc.poses)
+        X = mk[m % 6] + rng.normal(0, 2e-3, 3)  # the point handed to the reprojection: near the marker, not the DLT's answer
+        e = H.calculate_reprojection_error(copy.deepcopy(g), X, sc.poses)
+        tri.append([np.nan] * 3 if r[0] is None else list(r))
+        obj.append(X)
+        mse.append(np.nan if e is None else float(e))
+        groups.append([[np.nan, np.nan] if p[0] is None else p for p in g])
+    R4, t4 = poses_arrays(sc.poses)
+    K4, d4 = params_arrays(sc.camera_params)
+    np.savez_compressed(os.path.join(OUT, "reproj_none_mixed.npz"), groups=np.array(groups, float), R=R4, t=t4, K=K4, dist=d4,
+                        out=np.array(tri, float), obj=np.array(obj, float), mse=np.array(mse, float),
+                        provenance="reference: lib/Helpers.py:43-84 (out) and reference+cvstub: :113-143 (mse of obj) with "
+                                   "[None,None] entries (NaN here) on four cameras of different K and lens")
+    print("reproj_none_mixed: mse", np.array(mse))
+
+    # residual_function (Helpers.py:161-167) on 600 groups of a two-camera rig with two different lenses, 5 % of the groups
+    # holding a [None, None]: triangulate_points skips those (:93) and calculate_reprojection_errors pairs what is left
+    # positionally (:104).  A stereo pair with a small relative rotation, so that the parameter vector with a ZERO rotation
+    # vector is still a well-conditioned triangulation.
+    full = MixedScene(4)
+    params = [full.camera_params[3], full.camera_params[2]]  # tangential + k3 barrel, pincushion
+    Ka, Kb = full.Ks[3], full.Ks[2]
+    rng = np.random.default_rng(23)
+    N = 600
+    from scipy.spatial.transform import Rotation
+    w = np.array([0.02, -0.05, 0.03])
+    Rrel = Rotation.from_rotvec(w).as_matrix()
+    trel = -Rrel @ np.array([0.8, 0.05, 0.0])
+    X = np.c_[rng.uniform(-0.6, 0.6, (N, 2)), rng.uniform(2.8, 3.8, N)]
+    Xb = X @ Rrel.T + trel
+    pa = np.c_[Ka[0, 0] * X[:, 0] / X[:, 2] + Ka[0, 2], Ka[1, 1] * X[:, 1] / X[:, 2] + Ka[1, 2]]
+    pb = np.c_[Kb[0, 0] * Xb[:, 0] / Xb[:, 2] + Kb[0, 2], Kb[1, 1] * Xb[:, 1] / Xb[:, 2] + Kb[1, 2]]
+    ip = np.floor(np.stack([pa, pb], 1) + rng.normal(0, 0.5, (N, 2, 2)))
+    valid = np.ones((N, 2), bool)
+    holes = rng.choice(N, 30, replace=False)
+    valid[holes, rng.integers(0, 2, 30)] = False
+    assert all(((holes >= lo) & (holes < hi)).any() for lo, hi in ((0, 256), (256, 512), (512, N)))
+    as_lists = [[[float(p[0]), float(p[1])] if v else [None, None] for p, v in zip(g, vg)] for g, vg in zip(ip, valid)]
+    H.camera_params = np.array(params)
+    fun, x0 = capture_residual_function(H, as_lists, [{"R": np.eye(3), "t": np.zeros(3)}, {"R": Rrel, "t": trel}])
+    assert np.abs(x0 - np.r_[w, trel]).max() < 1e-12
+    xs = [x0, x0 + rng.normal(0, 1e-3, 6), np.r_[0.0, 0.0, 0.0, trel + rng.normal(0, 1e-3, 3)]]
+    res = [np.asarray(fun(x)) for x in xs]
+    assert all(r.dtype == np.float32 and np.isfinite(r).all() for r in res)
+    Kp, dp = params_arrays(params)
+    np.savez_compressed(os.path.join(OUT, "ba_residuals_mixed.npz"), image_points=np.where(valid[..., None], ip, np.nan),
+                        valid=valid, params=np.array(xs), residuals=np.array(res), K=Kp, dist=dp,
+                        provenance="reference+cvstub: residual_function of lib/Helpers.py:161-167 captured through a patched "
+                                   "scipy.optimize.least_squares; two cameras of different K and lens, 30 of 600 groups with a "
+                                   "[None,None] (NaN here) in all three 256-group rounds, params[2] has a zero rotation vector")
+    print("ba_residuals_mixed:", np.array(res).shape, "median", np.median(res, 1), "max", np.max(res, 1))
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     H = load_reference()
     if len(sys.argv) > 1 and sys.argv[1] == "calib":  # only the calibration fixture
         gen_calibration(H)
+        return
+    if len(sys.argv) > 1 and sys.argv[1] == "mixed":  # only the rigs of unequal cameras
+        gen_mixed(H)
         return
     gen_calibration(H)
     from mocapv2_amd.synth import Scene, MILD_DIST  # noqa: E402
@@ -248,8 +363,7 @@ def main():
         prm4[c]["intrinsic_matrix"][1][1] += 7.0 * c
     H.camera_params = np.array(prm4)
     groups, outs = [], []
-    masks = [(1, 1, 1, 1), (0, 1, 1, 1), (1, 0, 1, 1), (1, 1, 0, 0), (0, 0, 1, 1), (1, 0, 0, 0), (0, 0, 0, 0)]
-    for m, msk in enumerate(masks):
+    for m, msk in enumerate(TRI_NONE_MASKS):
         g = [[int(cents[c][m % 6][0]), int(cents[c][m % 6][1])] if msk[c] else [None, None] for c in range(4)]
         r = H.triangulate_point(g, sc.poses)
         outs.append([np.nan] * 3 if r[0] is None else list(r))
@@ -320,35 +434,20 @@ def main():
 
     # ---- bundle-adjustment residual vector (Helpers.py:158-167) -----------------------------------
     H.camera_params = np.array(params)
-    captured = {}
-
-    def capture(fun, x0, **kw):
-        captured["fun"], captured["x0"] = fun, np.array(x0)
-
-        class R_:
-            x = np.array(x0)
-
-        return R_()
-
-    orig = H.optimize.least_squares
-    H.optimize.least_squares = capture
-    try:
-        with open("jsons/before_ba_extrinsics.json") as f:
-            before = json.load(f)
-        for p in before:
-            p["R"], p["t"] = np.array(p["R"]), np.array(p["t"])
-        H.bundle_adjustment(ip, before)
-    finally:
-        H.optimize.least_squares = orig
-    x0 = captured["x0"]
+    with open("jsons/before_ba_extrinsics.json") as f:
+        before = json.load(f)
+    for p in before:
+        p["R"], p["t"] = np.array(p["R"]), np.array(p["t"])
+    fun, x0 = capture_residual_function(H, ip, before)
     rng = np.random.default_rng(5)
     xs = [x0, x0 + rng.normal(0, 1e-3, x0.shape), x0 + rng.normal(0, 1e-2, x0.shape)]
-    res = [np.asarray(captured["fun"](x)) for x in xs]
+    res = [np.asarray(fun(x)) for x in xs]
     np.savez_compressed(os.path.join(OUT, "ba_residuals.npz"), image_points=ip, params=np.array(xs),
                         residuals=np.array(res), K=K, dist=dist,
                         provenance="reference+cvstub: residual_function of lib/Helpers.py:161-167 captured through "
                                    "a patched scipy.optimize.least_squares, before_ba_extrinsics.json start")
     print("ba_residuals:", np.array(res).shape, np.array(res).dtype)
+    gen_mixed(H)
 
 
 if __name__ == "__main__":

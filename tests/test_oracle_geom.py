@@ -79,6 +79,44 @@ def test_ba_residuals(golden_dir):
         assert np.allclose(got, r, rtol=2e-5, atol=1e-6)
 
 
+def test_none_entries_on_unequal_cameras(golden_dir):
+    """reproj_none_mixed: triangulate_point and calculate_reprojection_error with [None, None] entries on four cameras that
+    differ in K and lens; both take the intrinsics by position after the entries are dropped (lib/Helpers.py:59-61,
+    :137-138).  The last assertion shows that the fixture tells the two indexings apart."""
+    g = load(golden_dir, "reproj_none_mixed")
+    seen = 0
+    for grp, exp, X, mse in zip(g["groups"], g["out"], g["obj"], g["mse"]):
+        valid = ~np.isnan(grp[:, 0])
+        pose_idx = np.nonzero(valid)[0]
+        k_idx = np.arange(len(pose_idx))
+        got = oracle.triangulate(grp[valid], pose_idx, k_idx, g["K"], g["R"], g["t"])
+        e = oracle.reproj_mse(grp[valid], pose_idx, k_idx, X, g["K"], g["dist"], g["R"], g["t"])
+        if np.isnan(exp[0]):
+            assert got is None and e is None and np.isnan(mse)
+            continue
+        assert np.abs(got - exp).max() < TOL_XYZ
+        assert abs(e - mse) <= 1e-9 * max(1.0, abs(mse))
+        if not np.array_equal(pose_idx, k_idx):  # by camera number instead: far off
+            wrong = oracle.reproj_mse(grp[valid], pose_idx, pose_idx, X, g["K"], g["dist"], g["R"], g["t"])
+            assert abs(wrong - mse) > 1e-3 * mse
+            seen += 1
+    assert seen == 3
+
+
+def test_ba_residuals_on_two_unequal_cameras_with_holes(golden_dir):
+    g = load(golden_dir, "ba_residuals_mixed")
+    ip, valid = np.nan_to_num(g["image_points"]), g["valid"]
+    assert ip.shape == (600, 2, 2) and not valid.all(1)[:256].all() and not valid.all(1)[256:512].all() and not valid.all(1)[512:].all()
+    assert not np.array_equal(g["K"][0], g["K"][1]) and not np.array_equal(g["dist"][0], g["dist"][1])
+    assert (g["params"][2][:3] == 0).all()  # the small-angle branch of Rotation.from_rotvec
+    for x, r in zip(g["params"], g["residuals"]):
+        got = oracle.ba_residuals(x, 2, ip, valid, g["K"], g["dist"])
+        assert got.dtype == np.float32 and got.shape == r.shape and len(r) < valid.all(1).sum()
+        assert np.allclose(got, r, rtol=2e-5, atol=1e-6)
+        swapped = oracle.ba_residuals(x, 2, ip, valid, g["K"][::-1], g["dist"][::-1])  # the cameras' intrinsics exchanged: far off
+        assert not np.allclose(swapped, r, rtol=1e-2, atol=1e-6)
+
+
 def test_numpy_pairwise_mean():
     rng = np.random.default_rng(0)
     for n in [1, 2, 7, 8, 9, 12, 127, 128, 129, 300, 1000, 4097]:

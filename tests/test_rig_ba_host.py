@@ -147,6 +147,47 @@ def test_loop_cases_are_far_from_every_decision_boundary():
         assert ((rel > 1.2 * rb.LOOP_FTOL) | (rel < rb.LOOP_FTOL / 1.2)).all() and out["status"] == rb.STOP_FTOL
 
 
+def aligned_errors(scene, X_true, R, t):
+    """(largest rotation error, largest camera-centre error) of a state with camera 0 at the origin against the scene"""
+    Rt, tt, _ = rb.truth_in_camera0(scene, X_true)
+    s = np.linalg.norm(tt[1]) / np.linalg.norm(t[1])
+    return (max(float(np.linalg.norm(R[c] @ Rt[c].T - np.eye(3)) / np.sqrt(2)) for c in range(len(R))),
+            max(float(np.linalg.norm(-R[c].T @ t[c] * s + Rt[c].T @ tt[c])) for c in range(len(R))))
+
+
+def test_restatement_meets_the_gpu_tests_bars_on_the_rig_of_unequal_cameras():
+    """mixed6 / mixed6_clean: six cameras that all differ in K (focal lengths 1120 .. 1750 px, fy != fx, principal points off
+    centre) and in lens, no point shared by cameras 0 and 1 (tests/test_gpu_mixed_rig.py runs the GPU on them).
+    mixed6 from the perturbed truth, lambda = 1e-3: spread under 10 permutations cost 1.3e-16, gradient 5.8e-16, S 2.1e-15,
+    rhs 7.6e-16, cond(S) 2.0e4; with ftol = 1e-9 the loop takes 6 accepted iterations, every rho within 4e-4 of 1, rms
+    0.3794 px < sigma.  mixed6_clean: rms 9.6e-14 px, rotation error 5.5e-16, centre error 2.4e-15 after 37 iterations
+    (status: lambda).  With every camera given camera 0's K and lens the start of mixed6 (rms 20 px) costs 27.7 times as
+    much: a wrong-camera read cannot hide in these numbers."""
+    c = rb.case("mixed6")
+    prob = c["prob"]
+    assert len({tuple(k.ravel()) for k in prob.K}) == 6 and len({tuple(d) for d in prob.dist}) == 4
+    assert not (c["valid"][0] & c["valid"][1]).any() and all((c["valid"][1] & c["valid"][k]).sum() >= 100 for k in range(2, 6))
+    R, t, X = rb.perturbed_start(c, rb.START_SEED["mixed6"])
+    spread = rb.order_spread(prob, R, t, X, 1e-3)
+    cond = np.linalg.cond(rb.linearize(prob, R, t, X, 1e-3)["S"])
+    out = rb.lm(prob, R, t, X, ftol=rb.LOOP_FTOL)
+    same = rb.Problem(prob.pt, prob.cam, prob.uv, np.stack([prob.K[0]] * 6), np.stack([prob.dist[0]] * 6), prob.N)
+    ratio = rb.cost_of(same, R, t, X)[0] / out["cost_initial"]
+    print("mixed6 spread", spread, "cond(S)", cond, "rho", out["rho"], "iterations", out["iterations"], "rms", rms(prob, out["cost"]),
+          "start cost with camera 0's K and lens for all / true", ratio)
+    assert all(v > 0 for v in spread.values()) and cond < 1e6
+    assert (np.abs(out["rho"]) >= 1e-3).all() and out["status"] == rb.STOP_FTOL and out["history"][:, 2].all()
+    assert rms(prob, out["cost"]) < c["sigma"]
+    assert ratio > 10
+    c = rb.case("mixed6_clean")
+    out = rb.lm(c["prob"], *rb.perturbed_start(c, rb.START_SEED["mixed6_clean"]))
+    e = aligned_errors(c["scene"], c["X"], out["R"], out["t"])
+    print("mixed6_clean rms", rms(c["prob"], out["cost"]), "rotation error", e[0], "centre error", e[1], "iterations", out["iterations"],
+          "status", out["status"])
+    assert not (c["valid"][0] & c["valid"][1]).any()
+    assert rms(c["prob"], out["cost"]) < 1e-9 and e[0] < 1e-12 and e[1] < 1e-11
+
+
 def test_restatement_refuses_a_start_behind_the_cameras():
     c = rb.case("noisy6", 60)
     R, t, X = rb.perturbed_start(c, 5)
