@@ -303,6 +303,31 @@ MOCAP_API int mocap_rig_linearize(mocap_ctx_t ctx, int C, int N, int n_obs, cons
                                   const double* points_dev, double lambda, double* cost_dev, double* gradient_dev, double* S_dev,
                                   double* rhs_dev, int32_t* status_dev, void* stream);
 
+/* The two entries above with a robust loss on the observations (wand captures carry ghost reflections and wrong-blob picks
+ * that no RANSAC mask reaches once the adjustment runs); new symbols, MOCAP_ABI_VERSION stays 7, the entries above keep their
+ * signatures and results.  Per observation with residual r: s = rx^2 + ry^2.  MOCAP_RIG_LOSS_CAUCHY with loss_scale = c
+ * (pixels, a few sigma of the pixel noise): rho(s) = c^2 log1p(s / c^2), weight w = 1 / (1 + s / c^2), cost 1/2 sum rho;
+ * the linearisation is first order (iteratively reweighted: r and the Jacobian rows of the observation times sqrt(w)), the
+ * step control is unchanged (restated by tests/rig_robust_ref.py).  MOCAP_RIG_LOSS_NONE is the
+ * definition above, bit for bit; loss_scale is then ignored.  Any other loss, or with Cauchy a loss_scale that is not finite
+ * or not > 0, is MOCAP_E_INVALID and nothing is launched.
+ *   obs_err_dev           float64 [n_obs] or NULL: the length |r| of every observation's UNWEIGHTED residual at the returned state
+ *   obs_weight_dev        float64 [n_obs] or NULL: the weight w there (1 for MOCAP_RIG_LOSS_NONE)
+ * Both are zero when the status is negative.  Every other argument, the history, the result (costs are 1/2 sum rho) and the
+ * rules on streams and scratch are mocap_rig_bundle_adjust's and mocap_rig_linearize's (cost_dev: 1/2 sum rho; gradient, S
+ * and rhs from the weighted blocks). */
+enum { MOCAP_RIG_LOSS_NONE = 0, MOCAP_RIG_LOSS_CAUCHY = 1 };
+MOCAP_API int mocap_rig_bundle_adjust_robust(mocap_ctx_t ctx, int C, int N, int n_obs, const int32_t* obs_offset_dev,
+                                             const int32_t* obs_cam_dev, const double* obs_uv_dev, double* poses_dev,
+                                             double* points_dev, int max_iters, double ftol, double lambda0, double* history_dev,
+                                             double* result_dev, int loss, double loss_scale, double* obs_err_dev,
+                                             double* obs_weight_dev, void* stream);
+MOCAP_API int mocap_rig_linearize_robust(mocap_ctx_t ctx, int C, int N, int n_obs, const int32_t* obs_offset_dev,
+                                         const int32_t* obs_cam_dev, const double* obs_uv_dev, const double* poses_dev,
+                                         const double* points_dev, double lambda, double* cost_dev, double* gradient_dev,
+                                         double* S_dev, double* rhs_dev, int32_t* status_dev, int loss, double loss_scale,
+                                         void* stream);
+
 /* Intrinsic calibration of every camera of a rig from planar-board corner lists: per camera fx, fy, cx, cy, k1, k2, p1, p2, k3
  * and one board -> camera pose per view, by Levenberg-Marquardt on the device (Schur complement on the views, analytic
  * Jacobian, Marquardt scaling, Nielsen's damping rule; FP64 throughout; definition in DESIGN.md section 2, restated by

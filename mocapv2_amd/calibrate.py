@@ -16,7 +16,8 @@ What is batched that the reference loops over:
     `least_squares(..., jac='2-point')`.
 Beyond the reference (whose calibration is two-camera at heart): `calibrate_rig` = `rig_initial_poses` (all camera pairs'
 fundamental matrices in one RANSAC call, a spanning tree with a common scale) + `bundle_adjust_rig` (all poses and all points
-on the GPU over exactly the observations that exist, csrc/rig_ba.hip; definition in DESIGN.md section 2).
+on the GPU over exactly the observations that exist, csrc/rig_ba.hip; definition in DESIGN.md section 2; with
+loss="cauchy" robust against the outliers of a real capture, which it reports per observation and refits without).
 `calibrate_intrinsics` supplies the camera_params all of these take: K and distortion of every camera from board views
 (the reference's CalculateCameraIntrinsic.py:58, cv2.calibrateCamera, batched over the rig; csrc/intrinsics.hip).
 Image capture and the plotting / JSON writing of that script are outside the path.  `calculate_extrinsics` is the
@@ -403,7 +404,51 @@ def rig_initial_poses(image_points, valid, camera_params, threshold=10.0, hypoth
     return (poses, info) if details else poses
 
 
-def bundle_adjust_rig(image_points, valid, poses, camera_params, points=None, max_iters=50, ftol=1e-12, ctx=None):
+def _observation_problem(ip, vis, sel):
+    """The observations vis [C][N] of the points sel, point-major with ascending cameras as the C-ABI wants them: (obs_offset
+    [len(sel) + 1], camera [n_obs], index into sel [n_obs], uv [n_obs][2])"""
+    v = vis[:, sel]
+    n_idx, c_idx = np.nonzero(v.T)
+    offset = np.zeros(len(sel) + 1, np.int32)
+    np.cumsum(v.sum(0), out=offset[1:])
+    return offset, c_idx.astype(np.int32), n_idx, ip[c_idx, sel[n_idx]]
+
+
+def _residual_lengths(ip, vis, K, d, R, t, X):
+    """|projection - pixel| [C][N] of the points X under the poses (R, t) with the full Brown model, NaN where vis is False or
+    the point is NaN: the reporting of bundle_adjust_rig's refit (host; every value the solver works with is the GPU's)"""
+    out = np.full(vis.shape, np.nan)
+    with np.errstate(all="ignore"):
+        for c in range(len(K)):
+            p = X @ R[c].T + t[c]
+            x, y = p[:, 0] / p[:, 2], p[:, 1] / p[:, 2]
+            k1, k2, p1, p2, k3 = d[c]
+            r2 = x * x + y * y
+            cd = 1 + ((k3 * r2 + k2) * r2 + k1) * r2
+            xd = x * cd + 2 * p1 * x * y + p2 * (r2 + 2 * x * x)
+            yd = y * cd + p1 * (r2 + 2 * y * y) + 2 * p2 * x * y
+            e = np.hypot(K[c][0, 0] * xd + K[c][0, 2] - ip[c, :, 0], K[c][1, 1] * yd + K[c][1, 2] - ip[c, :, 1])
+            out[c] = np.where(vis[c], e, np.nan)
+    return out
+
+
+def _check_loss(loss, loss_scale, inlier_weight):
+    """True for a robust loss, after the checks that need no GPU"""
+    if loss is None or loss == "none":
+        return False
+    if loss != "cauchy":
+        raise ValueError(f"loss {loss!r}: None or 'cauchy' (Huber is not offered: DESIGN.md section 7)")
+    if loss_scale is None:
+        raise ValueError("loss='cauchy' needs loss_scale, the scale c in pixels: a few sigma of the pixel noise")
+    if not (np.isfinite(loss_scale) and loss_scale > 0):
+        raise ValueError(f"loss_scale = {loss_scale}: a finite number of pixels > 0")
+    if not 0 < inlier_weight < 1:
+        raise ValueError(f"inlier_weight = {inlier_weight}: between 0 and 1")
+    return True
+
+
+def bundle_adjust_rig(image_points, valid, poses, camera_params, points=None, max_iters=50, ftol=1e-12, ctx=None, loss=None,
+                      loss_scale=None, inlier_weight=0.25, refit=True):
     """Bundle adjustment of ALL cameras of a rig and all 3-D points on the GPU, over exactly the observations that exist
     (engine.MocapContext.rig_bundle_adjust -> mocap_rig_bundle_adjust; definition in DESIGN.md section 2).  The reference's
     `bundle_adjustment` (lib/Helpers.py:158-176) refines camera 1 of two and drops every point a camera missed; it stays
@@ -415,7 +460,20 @@ def bundle_adjust_rig(image_points, valid, poses, camera_params, points=None, ma
     two views, or no start point in front of its cameras), cost_initial, cost (1/2 sum r^2), rms_px (per coordinate),
     iterations, history [iterations][4] (cost, lambda, accepted, |step|), status (MOCAP_RIG_STOP_*: 1 max_iters, 2 ftol,
     3 lambda, 4 Cholesky), mirrored (the start had every point behind every camera and was adjusted as its mirror image,
-    see below)."""
+    see below).
+    loss="cauchy", loss_scale=c: the adjustment weighs every observation by 1 / (1 + |r|^2 / c^2) (cost 1/2 sum c^2 log1p(|r|^2
+    / c^2)), so that the ghost reflections and wrong-blob picks of a wand capture stop steering the
+    poses.  loss_scale is required: it is the capture's pixel noise scale (a few sigma; 2 px for sigma 0.5 was what the tests
+    use), and there is no honest default for it.  The dict gains obs_err_px [C][N] (length of the unweighted residual),
+    obs_weight [C][N] and outliers [C][N] bool = obs_weight < inlier_weight (0.25: |r| > sqrt(3) c); where no observation
+    was used the float arrays are NaN and outliers is False.  refit=True then runs a second, plain adjustment from the robust
+    result over the observations that are not outliers (a point left with fewer than two views leaves `used`): poses, points,
+    used, cost, rms_px, iterations, history and status are the refit's, the robust stage's are robust_cost (1/2 sum rho),
+    robust_iterations and robust_status, obs_err_px is recomputed at the final state for every valid observation of the
+    points still used (the rejected ones included), obs_weight and outliers stay the robust stage's.  refit=False: cost is
+    1/2 sum rho and rms_px is taken over the observations that are not outliers.  cost_initial is the robust stage's, the 1/2
+    sum rho of the start.  The defaults (loss=None) are the plain adjustment with the keys above and nothing else."""
+    robust = _check_loss(loss, loss_scale, inlier_weight)
     ip, vis, K, d = _rig_inputs(image_points, valid, camera_params)
     Cn, N = vis.shape
     if len(poses) != Cn:
@@ -449,32 +507,61 @@ def bundle_adjust_rig(image_points, valid, poses, camera_params, points=None, ma
     if not used.any():
         raise ValueError("no point with two views and a start position in front of its cameras")
     sel = np.flatnonzero(used)
-    v = vis[:, sel]
-    n_idx, c_idx = np.nonzero(v.T)  # point-major, cameras ascending
-    offset = np.zeros(len(sel) + 1, np.int32)
-    np.cumsum(v.sum(0), out=offset[1:])
-    uv = ip[c_idx, sel[n_idx]]
+    offset, c_idx, n_idx, uv = _observation_problem(ip, vis, sel)
     ctx.set_cameras(K, d, R, t)
-    out = ctx.rig_bundle_adjust(offset, c_idx.astype(np.int32), uv, np.c_[R.reshape(Cn, 9), t], X[sel], max_iters, ftol)
+    start = np.c_[R.reshape(Cn, 9), t]
+    extra = {}
+    if not robust:
+        out = ctx.rig_bundle_adjust(offset, c_idx, uv, start, X[sel], max_iters, ftol)
+        rms = float(np.sqrt(out["cost"] / len(uv)))
+    else:
+        out = ctx.rig_bundle_adjust(offset, c_idx, uv, start, X[sel], max_iters, ftol, loss=loss, loss_scale=loss_scale)
+        err, weight = np.full((Cn, N), np.nan), np.full((Cn, N), np.nan)
+        err[c_idx, sel[n_idx]], weight[c_idx, sel[n_idx]] = out["obs_err"], out["obs_weight"]
+        with np.errstate(invalid="ignore"):
+            outliers = weight < inlier_weight  # (NaN: False)
+        kept = ~np.isnan(weight) & ~outliers
+        rms = float(np.sqrt(np.sum(err[kept] ** 2) / (2 * max(1, int(kept.sum())))))
+        extra = {"obs_weight": weight, "outliers": outliers}
+        if refit:
+            used = used & (kept.sum(0) >= 2)
+            if not used.any():
+                raise ValueError("no point keeps two views that the robust stage did not reject")
+            stage = out
+            X1 = np.full((N, 3), np.nan)
+            X1[sel] = stage["points"]
+            sel = np.flatnonzero(used)
+            offset, c_idx, n_idx, uv = _observation_problem(ip, kept, sel)
+            # (the robust result is a state of the device's convention: camera 0 the world frame, mirrored if the start was)
+            out = ctx.rig_bundle_adjust(offset, c_idx, uv, stage["poses"], X1[sel], max_iters, ftol)
+            out["cost_initial"] = stage["cost_initial"]
+            rms = float(np.sqrt(out["cost"] / len(uv)))
+            extra.update(robust_cost=stage["cost"], robust_iterations=stage["iterations"], robust_status=stage["status"])
+            Xf = np.full((N, 3), np.nan)
+            Xf[sel] = out["points"]
+            err = _residual_lengths(ip, vis, K, d, out["poses"][:, :9].reshape(Cn, 3, 3), out["poses"][:, 9:], Xf)
+        extra["obs_err_px"] = err
     Rn, tn, Xn = out["poses"][:, :9].reshape(Cn, 3, 3), out["poses"][:, 9:], out["points"]
     if mirror:
         tn, Xn = -tn, -Xn
     pts = np.full((N, 3), np.nan)
     pts[sel] = (Xn - t0) @ R0  # back to the caller's world frame
     new = [{"R": Rn[c] @ R0, "t": (tn[c] + Rn[c] @ t0).reshape(3, 1)} for c in range(Cn)]
-    return {"poses": new, "points": pts, "used": used, "cost_initial": out["cost_initial"], "cost": out["cost"],
-            "rms_px": float(np.sqrt(out["cost"] / len(uv))), "iterations": out["iterations"], "history": out["history"],
-            "status": out["status"], "mirrored": mirror}
+    return {"poses": new, "points": pts, "used": used, "cost_initial": out["cost_initial"], "cost": out["cost"], "rms_px": rms,
+            "iterations": out["iterations"], "history": out["history"], "status": out["status"], "mirrored": mirror, **extra}
 
 
-def calibrate_rig(image_points, valid, camera_params, threshold=10.0, hypotheses=1000, seed=0, max_iters=50, ftol=1e-12, ctx=None):
+def calibrate_rig(image_points, valid, camera_params, threshold=10.0, hypotheses=1000, seed=0, max_iters=50, ftol=1e-12, ctx=None,
+                  loss=None, loss_scale=None, inlier_weight=0.25, refit=True):
     """From the wand points of a whole rig to its extrinsics: `rig_initial_poses`, then `bundle_adjust_rig`.  The N-camera
     counterpart of `calculate_extrinsics` (which keeps the reference's two-camera behaviour).  Returns `bundle_adjust_rig`'s
     dict plus poses_initial and init (the initialisation's details); its poses and points go to `set_origin`, `set_floor` and
-    `save_extrinsics` as the reference's do."""
+    `save_extrinsics` as the reference's do.  loss, loss_scale, inlier_weight, refit: `bundle_adjust_rig`'s (the RANSAC of
+    the initialisation protects the start; loss="cauchy" protects the adjustment from the outliers of a real capture)."""
+    _check_loss(loss, loss_scale, inlier_weight)
     ctx = ctx or default_context()
     initial, info = rig_initial_poses(image_points, valid, camera_params, threshold, hypotheses, seed, ctx, details=True)
-    out = bundle_adjust_rig(image_points, valid, initial, camera_params, None, max_iters, ftol, ctx)
+    out = bundle_adjust_rig(image_points, valid, initial, camera_params, None, max_iters, ftol, ctx, loss, loss_scale, inlier_weight, refit)
     out["poses_initial"], out["init"] = initial, info
     return out
 

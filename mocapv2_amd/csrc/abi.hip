@@ -1586,18 +1586,38 @@ static int rig_args(mocap_ctx* c, int C, int N, int n_obs, const int32_t* obs_of
     return 0;
 }
 
+// The loss of the two robust entries, checked before anything is launched: its number, and with Cauchy a finite scale > 0.
+static int rig_loss(int loss, double loss_scale)
+{
+    if (loss != MOCAP_RIG_LOSS_NONE && loss != MOCAP_RIG_LOSS_CAUCHY)
+        return fail(MOCAP_E_INVALID, "loss = %d: MOCAP_RIG_LOSS_NONE (0) or MOCAP_RIG_LOSS_CAUCHY (1)", loss);
+    if (loss == MOCAP_RIG_LOSS_CAUCHY && (!(loss_scale > 0.0) || !(loss_scale <= 1.7976931348623157e308)))
+        return fail(MOCAP_E_INVALID, "loss_scale = %g: the Cauchy loss needs a finite scale > 0 (pixels)", loss_scale);
+    return 0;
+}
+
 int mocap_rig_linearize(mocap_ctx_t c, int C, int N, int n_obs, const int32_t* obs_offset, const int32_t* obs_cam, const double* obs_uv,
                         const double* poses, const double* points, double lambda, double* cost, double* gradient, double* S,
                         double* rhs, int32_t* status, void* stream)
 {
+    return mocap_rig_linearize_robust(c, C, N, n_obs, obs_offset, obs_cam, obs_uv, poses, points, lambda, cost, gradient, S, rhs, status,
+                                      MOCAP_RIG_LOSS_NONE, 0.0, stream);
+}
+
+int mocap_rig_linearize_robust(mocap_ctx_t c, int C, int N, int n_obs, const int32_t* obs_offset, const int32_t* obs_cam,
+                               const double* obs_uv, const double* poses, const double* points, double lambda, double* cost,
+                               double* gradient, double* S, double* rhs, int32_t* status, int loss, double loss_scale, void* stream)
+{
     if (!c || !obs_offset || !obs_cam || !obs_uv || !poses || !points || !cost || !gradient || !S || !rhs || !status)
         return fail(MOCAP_E_INVALID, "null argument");
     if (!(lambda >= 0.0) || !(lambda <= 1e300)) return fail(MOCAP_E_INVALID, "lambda = %g", lambda);
+    TRY(rig_loss(loss, loss_scale));
     if (set_device(c)) return MOCAP_E_HIP;
     std::lock_guard<std::mutex> lk(c->mu);
     RigArgs a;
     // (the state handed in is only read: the init kernel copies it, no finish kernel runs)
     TRY(rig_args(c, C, N, n_obs, obs_offset, obs_cam, obs_uv, const_cast<double*>(poses), const_cast<double*>(points), a));
+    a.loss = loss; a.loss_c2 = loss_scale * loss_scale;
     hipStream_t s = (hipStream_t)stream;
     const size_t D = 6 * (size_t)(C - 1);
     HIP_TRY(hipMemsetAsync(a.state, 0, sizeof(RigState), s));
@@ -1619,21 +1639,35 @@ int mocap_rig_bundle_adjust(mocap_ctx_t c, int C, int N, int n_obs, const int32_
                             const double* obs_uv, double* poses, double* points, int max_iters, double ftol, double lambda0,
                             double* history, double* result, void* stream)
 {
+    return mocap_rig_bundle_adjust_robust(c, C, N, n_obs, obs_offset, obs_cam, obs_uv, poses, points, max_iters, ftol, lambda0, history,
+                                          result, MOCAP_RIG_LOSS_NONE, 0.0, nullptr, nullptr, stream);
+}
+
+int mocap_rig_bundle_adjust_robust(mocap_ctx_t c, int C, int N, int n_obs, const int32_t* obs_offset, const int32_t* obs_cam,
+                                   const double* obs_uv, double* poses, double* points, int max_iters, double ftol, double lambda0,
+                                   double* history, double* result, int loss, double loss_scale, double* obs_err, double* obs_weight,
+                                   void* stream)
+{
     if (!c || !obs_offset || !obs_cam || !obs_uv || !poses || !points || !history || !result) return fail(MOCAP_E_INVALID, "null argument");
     if (max_iters < 1 || max_iters > 10000 || !(ftol >= 0.0) || !(lambda0 > 0.0) || !(lambda0 <= 1e16))
         return fail(MOCAP_E_INVALID, "max_iters=%d ftol=%g lambda0=%g", max_iters, ftol, lambda0);
+    TRY(rig_loss(loss, loss_scale));
     if (set_device(c)) return MOCAP_E_HIP;
     std::lock_guard<std::mutex> lk(c->mu);
     RigArgs a;
     TRY(rig_args(c, C, N, n_obs, obs_offset, obs_cam, obs_uv, poses, points, a));
     a.history = history; a.result = result;
+    a.loss = loss; a.loss_c2 = loss_scale * loss_scale; a.obs_err = obs_err; a.obs_weight = obs_weight;
     hipStream_t s = (hipStream_t)stream;
     HIP_TRY(hipMemsetAsync(a.state, 0, sizeof(RigState), s));
     HIP_TRY(hipMemsetAsync(history, 0, 8 * 4 * (size_t)max_iters, s));
+    if (obs_err) HIP_TRY(hipMemsetAsync(obs_err, 0, 8 * (size_t)n_obs, s));
+    if (obs_weight) HIP_TRY(hipMemsetAsync(obs_weight, 0, 8 * (size_t)n_obs, s));
     launch_rig_init(a, lambda0, s);
     // every iteration is enqueued; the kernels of an iteration after the stop return at once
     for (int it = 0; it < max_iters; it++) launch_rig_iteration(a, it, max_iters, ftol, s);
     launch_rig_finish(a, s);
+    if (obs_err || obs_weight) launch_rig_residuals(a, s);
     HIP_TRY(hipGetLastError());
     return MOCAP_OK;
 }

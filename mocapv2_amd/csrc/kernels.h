@@ -373,6 +373,8 @@ struct RigArgs {
     const double* obs_uv;      // [n_obs][2]
     int C, N, n_obs;
     int n_pairs, n_lin_blocks, n_chunks; // (C - 1) C / 2 pairs of free cameras; workgroups of the point kernels; of the Schur kernel
+    int loss;                  // LOSS_* of lm.h: which instantiation of the point kernels the launchers pick
+    double loss_c2;            // the loss's squared scale c^2 in px^2 (unused by LOSS_NONE)
     double* poses_io;          // [C][12] the caller's: R row-major, then t
     double* points_io;         // [N][3] the caller's
     // scratch of the context
@@ -397,12 +399,15 @@ struct RigArgs {
     double* scalars;           // [RIG_N_SCALARS]
     double* history;           // [max_iters][4] the caller's (or null for a linearisation alone)
     double* result;            // [4] the caller's
+    double* obs_err;           // [n_obs] the caller's or null: |r| of every observation at the returned state
+    double* obs_weight;        // [n_obs] the caller's or null: the loss's weight there (1 for LOSS_NONE)
 };
 
 void launch_rig_init(const RigArgs& a, double lambda0, hipStream_t s);
 void launch_rig_linearize(const RigArgs& a, hipStream_t s);
 void launch_rig_iteration(const RigArgs& a, int it, int max_iters, double ftol, hipStream_t s);
 void launch_rig_finish(const RigArgs& a, hipStream_t s);
+void launch_rig_residuals(const RigArgs& a, hipStream_t s); // behind launch_rig_finish: obs_err, obs_weight
 int rig_lin_blocks(int N);
 int rig_schur_chunks(int N);
 

@@ -83,7 +83,14 @@ __device__ __forceinline__ void pose_columns(const double A[3], const double q[3
     j[3] = A[0]; j[4] = A[1]; j[5] = A[2];
 }
 
-// The decision of iteration `it`, by one thread.  part [n][3]: the partials of the trial step (sum r^2 of the trial state, twice
+// The robust loss of an observation with squared residual length s = rx^2 + ry^2 and squared scale c2 = c^2 (DESIGN.md
+// section 2): Cauchy's rho(s) = c2 log1p(s / c2), whose IRLS weight is rho'(s) = 1 / (1 + s / c2).  A solver scales the
+// observation's residual and Jacobian rows by sqrt(weight) and sums rho in place of s for its cost; LOSS_NONE is rho(s) = s.
+enum { LOSS_NONE = 0, LOSS_CAUCHY = 1 };
+__device__ __forceinline__ double cauchy_weight(double s, double c2) { return 1.0 / (1.0 + s / c2); }
+__device__ __forceinline__ double cauchy_rho(double s, double c2) { return c2 * log1p(s / c2); }
+
+// The decision of iteration `it`, by one thread.  part [n][3]: the partials of the trial step (sum r^2 -- under a loss, sum rho -- of the trial state, twice
 // the predicted reduction, |step|^2), summed here in ascending order, and only for a step that was solved; cam [2]: the
 // camera step's share of the last two.  Gain ratio, accept (flip the buffer index) / reject, Nielsen's damping update, the
 // four stops.  h = the history row (cost after the decision, the lambda the step was solved with, accepted, |step|).

@@ -24,6 +24,11 @@
 //                         the camera step, the trial poses
 //   rig_update_kernel     a lane owns a point: back-substitution, trial point, trial cost, predicted reduction
 //   rig_decide_kernel     one workgroup: lm_decide (gain ratio, accept / reject, Nielsen's damping update, the stops, history)
+// The two point-owning kernels take the loss (lm.h) as a template parameter.  With LOSS_CAUCHY an observation's residual and
+// Jacobian rows are scaled by sqrt(w), w = 1 / (1 + s / c^2), before anything is formed from them, and the costs sum rho(s) in
+// place of s (first-order IRLS); everything downstream reads the scaled blocks and does not know.  LOSS_NONE compiles to the
+// code without a loss.  After the loop rig_finish_kernel hands the state back and rig_residuals_kernel (a lane owns a point)
+// writes every observation's |r| and weight at that returned state.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "kernels.h"
@@ -69,6 +74,26 @@ __device__ __forceinline__ bool observe(const Cam& m, const double X[3], double 
         }
     }
     return front;
+}
+
+// The loss's part of an observation: its share of the cost from the unscaled r, and with JAC r, jc, jp scaled by sqrt(weight)
+template <int LOSS, bool JAC>
+__device__ __forceinline__ double robustify(double c2, double r[2], double jc[2][6], double jp[2][3])
+{
+    const double s = r[0] * r[0] + r[1] * r[1];
+    if (LOSS == LOSS_NONE) return s;
+    if (JAC) {
+        const double sw = sqrt(cauchy_weight(s, c2));
+#pragma unroll
+        for (int i = 0; i < 2; i++) {
+            r[i] *= sw;
+#pragma unroll
+            for (int j = 0; j < 6; j++) jc[i][j] *= sw;
+#pragma unroll
+            for (int j = 0; j < 3; j++) jp[i][j] *= sw;
+        }
+    }
+    return cauchy_rho(s, c2);
 }
 
 // the pair of free cameras of a workgroup of the Schur and the reduce kernel: pair index -> (ca, cb), 1 <= ca <= cb < C, row by row
@@ -125,6 +150,7 @@ __global__ __launch_bounds__(256) void rig_init_kernel(RigArgs a, double lambda0
 }
 
 // A lane owns a point.  Grid: ceil(N / 256).
+template <int LOSS>
 __global__ __launch_bounds__(PT_THREADS) void rig_linearize_kernel(RigArgs a)
 {
     __shared__ double s_red[2][4][27];
@@ -158,7 +184,7 @@ __global__ __launch_bounds__(PT_THREADS) void rig_linearize_kernel(RigArgs a)
         if (has) {
             const Cam m = load_cam(a.cams, pose, c);
             behind = !observe<true>(m, X, a.obs_uv[2 * (size_t)o], a.obs_uv[2 * (size_t)o + 1], r, jc, jp) || behind;
-            cost += r[0] * r[0] + r[1] * r[1];
+            cost += robustify<LOSS, true>(a.loss_c2, r, jc, jp);
             int k = 0;
 #pragma unroll
             for (int i = 0; i < 3; i++) {
@@ -414,6 +440,7 @@ __global__ __launch_bounds__(256) void rig_solve_kernel(RigArgs a, int it)
 }
 
 // A lane owns a point: dX = -V*^-1 (g_n + sum_c W_nc^T d_c), the trial point, its observations under the trial poses.
+template <int LOSS>
 __global__ __launch_bounds__(PT_THREADS) void rig_update_kernel(RigArgs a)
 {
     __shared__ double s_d[6 * 31];
@@ -461,7 +488,7 @@ __global__ __launch_bounds__(PT_THREADS) void rig_update_kernel(RigArgs a)
             const Cam cam = load_cam(a.cams, trial_pose, c);
             double r[2];
             behind = !observe<false>(cam, X, a.obs_uv[2 * (size_t)o], a.obs_uv[2 * (size_t)o + 1], r, nullptr, nullptr) || behind;
-            cost += r[0] * r[0] + r[1] * r[1];
+            cost += robustify<LOSS, false>(a.loss_c2, r, nullptr, nullptr);
         }
     }
     if (behind) atomicOr(&st->trial_behind, 1);
@@ -499,6 +526,27 @@ __global__ __launch_bounds__(256) void rig_finish_kernel(RigArgs a)
     for (int i = gid; i < 3 * a.N; i += stride) a.points_io[i] = pts[i] * s;
 }
 
+// A lane owns a point: the length of every observation's unweighted residual and the loss's weight, at the state
+// rig_finish_kernel handed back (the caller's arrays; a negative status: nothing is written, the outputs were zeroed).
+template <int LOSS>
+__global__ __launch_bounds__(PT_THREADS) void rig_residuals_kernel(RigArgs a)
+{
+    const RigState* st = a.state;
+    if (st->layout_err || st->status < 0) return;
+    const int n = blockIdx.x * PT_THREADS + threadIdx.x;
+    if (n >= a.N) return;
+    const double X[3] = {a.points_io[3 * (size_t)n], a.points_io[3 * (size_t)n + 1], a.points_io[3 * (size_t)n + 2]};
+    int o = a.obs_offset[n];
+    for (uint32_t m = a.mask[n]; m; m &= m - 1, o++) {
+        const Cam cam = load_cam(a.cams, a.poses_io, __ffs(m) - 1);
+        double r[2];
+        observe<false>(cam, X, a.obs_uv[2 * (size_t)o], a.obs_uv[2 * (size_t)o + 1], r, nullptr, nullptr);
+        const double s = r[0] * r[0] + r[1] * r[1];
+        if (a.obs_err) a.obs_err[o] = sqrt(s);
+        if (a.obs_weight) a.obs_weight[o] = LOSS == LOSS_NONE ? 1.0 : cauchy_weight(s, a.loss_c2);
+    }
+}
+
 static int grid_for(int n) { int g = (n + 255) / 256; return g < 1 ? 1 : (g > 1024 ? 1024 : g); }
 
 void launch_rig_init(const RigArgs& a, double lambda0, hipStream_t s)
@@ -509,7 +557,8 @@ void launch_rig_init(const RigArgs& a, double lambda0, hipStream_t s)
 
 void launch_rig_linearize(const RigArgs& a, hipStream_t s)
 {
-    hipLaunchKernelGGL(rig_linearize_kernel, dim3(a.n_lin_blocks), dim3(PT_THREADS), 0, s, a);
+    if (a.loss == LOSS_CAUCHY) hipLaunchKernelGGL(rig_linearize_kernel<LOSS_CAUCHY>, dim3(a.n_lin_blocks), dim3(PT_THREADS), 0, s, a);
+    else hipLaunchKernelGGL(rig_linearize_kernel<LOSS_NONE>, dim3(a.n_lin_blocks), dim3(PT_THREADS), 0, s, a);
     hipLaunchKernelGGL(rig_schur_kernel, dim3(a.n_pairs, a.n_chunks), dim3(256), 0, s, a);
     hipLaunchKernelGGL(rig_reduce_kernel, dim3(a.n_pairs), dim3(64), 0, s, a);
 }
@@ -518,13 +567,20 @@ void launch_rig_iteration(const RigArgs& a, int it, int max_iters, double ftol, 
 {
     launch_rig_linearize(a, s);
     hipLaunchKernelGGL(rig_solve_kernel, dim3(1), dim3(256), 0, s, a, it);
-    hipLaunchKernelGGL(rig_update_kernel, dim3(a.n_lin_blocks), dim3(PT_THREADS), 0, s, a);
+    if (a.loss == LOSS_CAUCHY) hipLaunchKernelGGL(rig_update_kernel<LOSS_CAUCHY>, dim3(a.n_lin_blocks), dim3(PT_THREADS), 0, s, a);
+    else hipLaunchKernelGGL(rig_update_kernel<LOSS_NONE>, dim3(a.n_lin_blocks), dim3(PT_THREADS), 0, s, a);
     hipLaunchKernelGGL(rig_decide_kernel, dim3(1), dim3(64), 0, s, a, it, max_iters, ftol);
 }
 
 void launch_rig_finish(const RigArgs& a, hipStream_t s)
 {
     hipLaunchKernelGGL(rig_finish_kernel, dim3(grid_for(3 * a.N)), dim3(256), 0, s, a);
+}
+
+void launch_rig_residuals(const RigArgs& a, hipStream_t s)
+{
+    if (a.loss == LOSS_CAUCHY) hipLaunchKernelGGL(rig_residuals_kernel<LOSS_CAUCHY>, dim3(a.n_lin_blocks), dim3(PT_THREADS), 0, s, a);
+    else hipLaunchKernelGGL(rig_residuals_kernel<LOSS_NONE>, dim3(a.n_lin_blocks), dim3(PT_THREADS), 0, s, a);
 }
 
 int rig_lin_blocks(int N) { return (N + PT_THREADS - 1) / PT_THREADS; }

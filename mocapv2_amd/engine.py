@@ -22,6 +22,7 @@ MAX_BLOBS = 128       # centroid record capacity per camera image (SURVEY.md sec
 # settles it wherever cv2 can be imported (it cannot in the build container).
 GRAY_SHIFT = 15
 REC_INTS = 2 + 2 * MAX_BLOBS  # int32 record: count, pad, xy[MAX_BLOBS][2]
+RIG_LOSSES = {"none": 0, "cauchy": 1}  # MOCAP_RIG_LOSS_*
 
 
 def _ptr(t):
@@ -413,10 +414,22 @@ class MocapContext:
         return (Cn, N, n_obs, torch.from_numpy(off).to(dev), torch.from_numpy(cam).to(dev), torch.from_numpy(uv).to(dev),
                 torch.from_numpy(poses).to(dev), torch.from_numpy(points).to(dev))
 
-    def rig_linearize(self, obs_offset, obs_cam, obs_uv, poses, points, lam):
+    @staticmethod
+    def _rig_loss(loss, loss_scale):
+        """(MOCAP_RIG_LOSS_* number, scale) of the loss keywords: a name of RIG_LOSSES, or a number handed to the library as it
+        is (which refuses what it does not know)"""
+        if isinstance(loss, str):
+            if loss not in RIG_LOSSES:
+                raise ValueError(f"loss {loss!r}: one of {sorted(RIG_LOSSES)}")
+            loss = RIG_LOSSES[loss]
+        return int(loss), 0.0 if loss_scale is None else float(loss_scale)
+
+    def rig_linearize(self, obs_offset, obs_cam, obs_uv, poses, points, lam, loss=None, loss_scale=None):
         """The pieces of one iteration of rig_bundle_adjust at a given state and damping (mocap_rig_linearize): dict with cost
         (1/2 sum r^2), gradient [6 (C - 1) + 3 N], S [D][D] (damped reduced camera matrix), rhs [D], behind (a point is not
-        in front of a camera that sees it).  Arguments as rig_bundle_adjust; K and dist come from set_cameras."""
+        in front of a camera that sees it).  Arguments as rig_bundle_adjust; K and dist come from set_cameras.  loss,
+        loss_scale: as rig_bundle_adjust's (mocap_rig_linearize_robust: cost 1/2 sum rho, the rest from the weighted blocks)."""
+        robust = () if loss is None else self._rig_loss(loss, loss_scale)
         Cn, N, n_obs, d_off, d_cam, d_uv, d_poses, d_pts = self._rig_upload(obs_offset, obs_cam, obs_uv, poses, points)
         D = 6 * (Cn - 1)
         dev = self.device
@@ -425,9 +438,9 @@ class MocapContext:
         S = torch.zeros((D, D), dtype=torch.float64, device=dev)
         rhs = torch.zeros((D,), dtype=torch.float64, device=dev)
         status = torch.zeros((2,), dtype=torch.int32, device=dev)
-        _abi.check(self.lib.mocap_rig_linearize(self._h, Cn, N, n_obs, _ptr(d_off), _ptr(d_cam), _ptr(d_uv), _ptr(d_poses),
-                                                _ptr(d_pts), float(lam), _ptr(cost), _ptr(grad), _ptr(S), _ptr(rhs), _ptr(status),
-                                                _stream()))
+        fn = self.lib.mocap_rig_linearize_robust if robust else self.lib.mocap_rig_linearize
+        _abi.check(fn(self._h, Cn, N, n_obs, _ptr(d_off), _ptr(d_cam), _ptr(d_uv), _ptr(d_poses), _ptr(d_pts), float(lam), _ptr(cost),
+                      _ptr(grad), _ptr(S), _ptr(rhs), _ptr(status), *robust, _stream()))
         self.sync()
         status = status.cpu().numpy()
         if status[0]:
@@ -435,7 +448,8 @@ class MocapContext:
         return {"cost": float(cost.cpu().numpy()[0]), "gradient": grad.cpu().numpy(), "S": S.cpu().numpy(), "rhs": rhs.cpu().numpy(),
                 "behind": bool(status[1])}
 
-    def rig_bundle_adjust(self, obs_offset, obs_cam, obs_uv, poses, points, max_iters=50, ftol=1e-12, lambda0=1e-3):
+    def rig_bundle_adjust(self, obs_offset, obs_cam, obs_uv, poses, points, max_iters=50, ftol=1e-12, lambda0=1e-3, loss=None,
+                          loss_scale=None):
         """Bundle adjustment of a whole rig on the device (mocap_rig_bundle_adjust; the N-camera, partial-visibility
         generalisation of reference lib/Helpers.py:158-176): one upload, ONE call that enqueues every iteration, one sync.
         obs_offset int32 [N + 1], obs_cam int32 [n_obs] (true camera numbers, ascending within a point), obs_uv [n_obs][2]:
@@ -443,14 +457,26 @@ class MocapContext:
         start.  K and dist come from set_cameras.  Returns dict: poses [C][12], points [N][3] (|t_1| as at the start),
         status (MOCAP_RIG_STOP_* > 0), iterations, cost_initial, cost (1/2 sum r^2), history [iterations][4] = (cost after
         the iteration, lambda it was solved with, accepted, |step|).  A negative status (MOCAP_RIG_E_*) raises MocapError:
-        nothing is returned silently wrong."""
+        nothing is returned silently wrong.
+        loss: None (mocap_rig_bundle_adjust), or "none" / "cauchy" with loss_scale = c in pixels
+        (mocap_rig_bundle_adjust_robust: rho(s) = c^2 log1p(s / c^2) of s = |r|^2 per observation, first-order reweighting,
+        costs 1/2 sum rho; "none" gives the bits of loss=None).  The robust call returns two more keys: obs_err [n_obs], the
+        length of every observation's unweighted residual at the returned state, and obs_weight [n_obs], its weight
+        1 / (1 + s / c^2) there (1 for "none")."""
+        robust = () if loss is None else self._rig_loss(loss, loss_scale)
         Cn, N, n_obs, d_off, d_cam, d_uv, d_poses, d_pts = self._rig_upload(obs_offset, obs_cam, obs_uv, poses, points)
         max_iters = int(max_iters)
         hist = torch.empty((max_iters, 4), dtype=torch.float64, device=self.device)
         result = torch.zeros((4,), dtype=torch.float64, device=self.device)
-        _abi.check(self.lib.mocap_rig_bundle_adjust(self._h, Cn, N, n_obs, _ptr(d_off), _ptr(d_cam), _ptr(d_uv), _ptr(d_poses),
-                                                    _ptr(d_pts), max_iters, float(ftol), float(lambda0), _ptr(hist), _ptr(result),
-                                                    _stream()))
+        if robust:
+            per_obs = torch.empty((2, n_obs), dtype=torch.float64, device=self.device)
+            _abi.check(self.lib.mocap_rig_bundle_adjust_robust(self._h, Cn, N, n_obs, _ptr(d_off), _ptr(d_cam), _ptr(d_uv), _ptr(d_poses),
+                                                               _ptr(d_pts), max_iters, float(ftol), float(lambda0), _ptr(hist),
+                                                               _ptr(result), *robust, _ptr(per_obs[0]), _ptr(per_obs[1]), _stream()))
+        else:
+            _abi.check(self.lib.mocap_rig_bundle_adjust(self._h, Cn, N, n_obs, _ptr(d_off), _ptr(d_cam), _ptr(d_uv), _ptr(d_poses),
+                                                        _ptr(d_pts), max_iters, float(ftol), float(lambda0), _ptr(hist), _ptr(result),
+                                                        _stream()))
         self.sync()
         result = result.cpu().numpy()
         status, iters = int(result[0]), int(result[1])
@@ -459,8 +485,12 @@ class MocapContext:
                     -3: "in the start state a point is not in front of a camera that sees it, or the cost is not finite "
                         "(MOCAP_RIG_E_BEHIND)"}.get(status, f"status {status}")
             raise _abi.MocapError(status, "mocap_rig_bundle_adjust: " + what)
-        return {"poses": d_poses.cpu().numpy(), "points": d_pts.cpu().numpy(), "status": status, "iterations": iters,
-                "cost_initial": float(result[2]), "cost": float(result[3]), "history": hist.cpu().numpy()[:iters].copy()}
+        out = {"poses": d_poses.cpu().numpy(), "points": d_pts.cpu().numpy(), "status": status, "iterations": iters,
+               "cost_initial": float(result[2]), "cost": float(result[3]), "history": hist.cpu().numpy()[:iters].copy()}
+        if robust:
+            per_obs = per_obs.cpu().numpy()
+            out["obs_err"], out["obs_weight"] = per_obs[0].copy(), per_obs[1].copy()
+        return out
 
     def _intr_upload(self, view_offset, point_offset, obj_xy, img_uv):
         """Host offsets and device copies of a board-view problem in the layout of mocap_intrinsics_calibrate.  Only the

@@ -40,7 +40,7 @@ def main():
         ks = kernels_of(os.path.join(CSRC, f))
         names = subprocess.run([FILT], input="\n".join(k["name"] for k in ks), capture_output=True, text=True).stdout.split("\n")
         for k, nm in zip(ks, names):
-            nm = re.sub(r"^void mocap::(\(anonymous namespace\)::)?", "", nm)
+            nm = re.sub(r"^void ", "", nm).replace("(anonymous namespace)::", "")  # (a template's name comes with its return type)
             nm = re.sub(r"\(.*\)$", "", nm)
             print(f"| {f} | `{nm}` | {k['vgpr']} | {k['agpr']} | {k['sgpr']} | {k['lds']} | {k['scratch']} | {k['spill']} | {k['wg']} |")
 
