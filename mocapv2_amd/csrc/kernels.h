@@ -1,4 +1,4 @@
-// kernels.h -- internal launch interface between the C-ABI (abi.hip) and the HIP kernels.
+// kernels.h -- internal launch interface between the C-ABI (abi_*.hip) and the HIP kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -33,7 +33,7 @@ def kernels_of(src):
 
 
 def main():
-    files = sys.argv[1:] or sorted(f for f in os.listdir(CSRC) if f.endswith(".hip") and f != "abi.hip")
+    files = sys.argv[1:] or sorted(f for f in os.listdir(CSRC) if f.endswith(".hip") and not f.startswith("abi_"))
     print("| file | kernel | VGPR | AGPR | SGPR | static LDS B | scratch B/lane | spilled VGPRs | max wg |")
     print("|---|---|---|---|---|---|---|---|---|")
     for f in files:

@@ -29,6 +29,23 @@ def test_library_exports_every_declared_symbol():
     assert lib.mocap_abi_version() == _abi.ABI_VERSION
 
 
+def test_library_exports_nothing_but_the_declared_symbols():
+    """The functions the library defines for others (`T` in nm's dynamic table) are exactly the header's: what the host files share
+    among themselves (fail, prof_begin, ...) stays hidden.  Weak template instantiations (`W`) and the kernels' handles are data
+    or weak symbols and no part of this."""
+    import shutil
+    import subprocess
+    if not shutil.which("nm"):
+        pytest.skip("nm is not on the path")
+    from mocapv2_amd import _abi
+    if not os.path.exists(_abi.LIB_PATH):
+        import __graft_entry__
+        __graft_entry__.build()
+    out = subprocess.run(["nm", "-D", "--defined-only", _abi.LIB_PATH], check=True, capture_output=True, text=True).stdout
+    exported = sorted(f[2] for f in (line.split() for line in out.splitlines()) if len(f) == 3 and f[1] == "T")
+    assert exported == declared_symbols()
+
+
 def test_no_gpu_is_reported_not_hidden():
     """Without a GPU every compute entry point must fail loudly (no CPU fallback)."""
     import torch

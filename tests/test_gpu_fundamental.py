@@ -66,6 +66,29 @@ def test_counts_winner_mask_and_matrices_equal_the_restatement(ctx, name):
     compare_with_restatement(name, got, ref, len(a))
 
 
+def test_an_odd_number_of_pairs_times_an_odd_number_of_hypotheses(ctx):
+    """s11, s13 and s14 in one call, each with the first five rows of its sample table: n_pairs = 3 and n_pairs * H = 15 are odd,
+    so the matrices of all hypotheses (72 bytes each) end on an odd multiple of 8 bytes and the counters, the pairs' error words
+    and the offsets behind them in the call's scratch start 8 bytes further on than a packed layout would put them.  Every pair:
+    the full comparison with the restatement on the same five samples.
+    The restatement (CPU) on these: winners 4, 4, 0 with 218, 201, 54 inliers, no (hypothesis, point) pair within the band, and
+    every winner ahead of the other four hypotheses (37, 130, 53 at most) -- checked here before the GPU is asked.
+    Measured on an MI355X: every count, winner and mask equal; |dF_sample| <= 4.6e-16, |dF_refit| <= 2.3e-16 over the three."""
+    names = ("s11", "s13", "s14")
+    cases = [reference(n)[:4] for n in names]
+    assert all(c[3] == 3.0 for c in cases)
+    tables = [np.ascontiguousarray(c[2][:5]) for c in cases]
+    refs = [fr.ransac(c[0], c[1], S, 3.0) for c, S in zip(cases, tables)]
+    for name, ref in zip(names, refs):
+        lead = ref["counts"] + ref["banded"]
+        lead[ref["best"]] = -1
+        assert ref["best"] >= 0 and ref["counts"][ref["best"]] - ref["banded"][ref["best"]] > lead.max(), name
+    res = ctx.fundamental_ransac([(c[0], c[1]) for c in cases], tables, 3.0, refit=True, with_counts=True)
+    assert len(res) == 3
+    for name, c, got, ref in zip(names, cases, res, refs):
+        compare_with_restatement(name + " (5 samples)", got, ref, len(c[0]))
+
+
 def test_the_restatements_table_of_winners():
     """What the yardstick itself gives on the small cases (CPU arithmetic; here so that a change of the generators shows)."""
     want = {"bundled": (28, 54), "s11": (108, 1398), "s12": (358, 295), "s13": (528, 241), "s14": (0, 54), "s15": (294, 575)}
