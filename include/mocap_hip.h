@@ -42,6 +42,7 @@ enum {
                                      8192) by default, raised with mocap_set_tuning(ctx, "corr_step_groups", n) */
     MOCAP_CORR_E_TRUNCATED = -3,  /* a camera holds more image points than the P that mocap_correspond was told to read */
     MOCAP_CORR_E_BLOB = -4,       /* a camera's point count is negative: its blob stage reported MOCAP_BLOB_E_* */
+    MOCAP_CORR_E_OUTPUT = -5,     /* mocap_correspond_visible: more accepted markers in the time step than the Q output rows */
     MOCAP_FUND_E_SAMPLE = -2,     /* mocap_fundamental_ransac: a sample index outside its pair's point list */
     MOCAP_FUND_E_DEGENERATE = -3  /* no valid hypothesis (e.g. coincident points), a winner with fewer than 8 inliers, or
                                      inliers that do not span a model in the refit */
@@ -196,6 +197,46 @@ MOCAP_API int mocap_correspond(mocap_ctx_t ctx, const void* pts_dev, long pt_str
                      int P, double cutoff, int max_groups, double* root_xyz_dev, double* root_err_dev,
                      double* root_grp_dev, int32_t* root_idx_dev, int32_t* order_dev, int32_t* n_roots_dev,
                      void* stream);
+
+/* Correspondence and triangulation of markers that only SOME cameras see, from any camera pair, for T time steps.  The
+ * reference has no counterpart: mocap_correspond (its find_point_correspondance_and_object_points) starts from camera 0's
+ * points and triangulates only groups in which no camera is missing (lib/Helpers.py:93,178-280), so it reports a marker only
+ * when every camera of the rig sees it.  The contract is the definition of DESIGN.md section 2, restated by
+ * tests/correspond_visible_ref.py; FP64 throughout, every operation rounded on its own.  New symbol, MOCAP_ABI_VERSION stays 7.
+ * Points and counts are read through strides exactly as mocap_correspond reads them (centroid records and all-gathered
+ * records work in place).  K, dist, R, t come from mocap_set_cameras; mocap_set_fundamentals is not needed: the pair matrices
+ * F_ab = K_b^-T [t]x R K_a^-1 are formed on the device.
+ *   distorted   0: the points are pixels of undistorted images (what mocap_blob_centroids delivers); 1: every point is first
+ *               mapped to its ideal pinhole pixel (cv.undistortPoints' five fixed-point rounds).  Everything after lives in
+ *               ideal pinhole pixels
+ *   cutoff      a pair of points of two cameras is a seed when the second lies closer than this (px) to the first's epipolar line
+ *   gate        a camera's nearest unclaimed point supports a seed when it lies closer than this (px) to the projection of the
+ *               seed's two-view point
+ *   min_views   fewest member cameras of an accepted marker, 2..C
+ *   max_err     a hypothesis is kept when its error (mean of the squared reprojection residuals over both coordinates of all
+ *               members, px^2: root_err's convention) is below this
+ *   max_passes  hypotheses are sorted by (more members, smaller error, a, i, b, j) and accepted in that order when none of
+ *               their points is claimed yet; passes over the points still unclaimed repeat until one accepts nothing
+ *   max_hyp     1..65535: seeds one pass of one time step may hold (in LDS up to a cap, beyond it in scratch the context owns
+ *               and grows on demand: calls on one context must be ordered on one stream)
+ *   Q           1..65535: output rows per time step
+ * Per time step, in acceptance order (more views first, then smaller error, pass by pass):
+ *   xyz_dev   float64 [T][Q][3]   the DLT over the members in ascending camera order
+ *   err_dev   float64 [T][Q]
+ *   idx_dev   int32 [T][Q][C]     index of the member point in each camera, -1 = the camera is no member
+ *   views_dev uint32 [T][Q]       bit c set: camera c is a member
+ *   n_dev     int32 [T]           markers, or MOCAP_CORR_E_* (< 0): the time step has no result -- a count above P (TRUNCATED),
+ *                                 a negative count (BLOB), more than max_hyp seeds in a pass (GROUPS), more than Q markers
+ *                                 (OUTPUT).  Nothing is ever shortened silently; the other time steps are unaffected
+ * Rows at and beyond n_dev[t] (all rows of a failed step) are UNSPECIFIED: they are not zero-filled and must not be read (a
+ * step that fails in its second or a later pass has already written the rows of the passes before).
+ * A combination of P and C whose points, camera table and C (C - 1) / 2 pair matrices leave no room for 64 hypotheses in a
+ * workgroup's LDS is MOCAP_E_UNSUPPORTED.  Asynchronous on `stream`.  No floating-point atomics: the same call gives the same bits. */
+MOCAP_API int mocap_correspond_visible(mocap_ctx_t ctx, const void* pts_dev, long pt_stride_t, long pt_stride_c,
+                                       const int32_t* counts_dev, long cnt_stride_t, long cnt_stride_c, int pts_f64, int T, int C,
+                                       int P, int distorted, double cutoff, double gate, int min_views, double max_err,
+                                       int max_passes, int max_hyp, int Q, double* xyz_dev, double* err_dev, int32_t* idx_dev,
+                                       uint32_t* views_dev, int32_t* n_dev, void* stream);
 
 /* The scoring step of find_point_correspondance_and_object_points on its own (lib/Helpers.py:205-220), for one camera
  * pair: the epipolar line of every root point under Fs[f_index] (cv.computeCorrespondEpilines on the float32 point, :207;
@@ -416,9 +457,10 @@ MOCAP_API int mocap_allgather_centroids(mocap_ctx_t ctx, const int32_t* local_re
  * disables it.  mocap_tile_stats: number of (strip, chunk) tiles of the most recent batch and how many of them were
  * resolved that way.  Synchronises the device. */
 MOCAP_API int mocap_tile_stats(mocap_ctx_t ctx, uint64_t* tiles, uint64_t* skipped);
-/* HIP-event timing of the kernels launched by mocap_blob_centroids / mocap_filter_mask / mocap_correspond, recorded
+/* HIP-event timing of the kernels launched by mocap_blob_centroids / mocap_filter_mask / mocap_correspond / mocap_correspond_visible, recorded
  * on their stream.  mocap_profile_read synchronises, returns accumulated milliseconds and launch counts and resets:
- * index 0 = box_filter_kernel (or the general filter_mask_kernel), 1 = contours_kernel, 2 = correspond_kernel,
+ * index 0 = box_filter_kernel (or the general filter_mask_kernel), 1 = contours_kernel, 2 = correspond_kernel and
+ * correspond_visible_kernel,
  * 3 = bright_cells_kernel, 4 = settle_tiles_kernel. */
 MOCAP_API int mocap_profile_enable(mocap_ctx_t ctx, int on);
 MOCAP_API int mocap_profile_read(mocap_ctx_t ctx, double ms[5], int launches[5]);

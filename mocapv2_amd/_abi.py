@@ -57,6 +57,8 @@ SIGNATURES = {
     "mocap_demosaic_u8": [_vp, _vp, _vp, _i, _i, _i, _vp],
     "mocap_bayer_gray_u8": [_vp, _vp, _vp, _i, _i, _i, _l, _l, _sz, _sz, _i, _i, _vp],
     "mocap_correspond": [_vp, _vp, _l, _l, _vp, _l, _l, _i, _i, _i, _i, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "mocap_correspond_visible": [_vp, _vp, _l, _l, _vp, _l, _l, _i, _i, _i, _i, _i, _d, _d, _i, _d, _i, _i, _i, _vp, _vp, _vp, _vp,
+                                 _vp, _vp],
     "mocap_epipolar_scores": [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp],
     "mocap_ba_residuals": [_vp, _dp, _i, _vp, _vp, _i, _i, C.POINTER(C.c_float), _ip, _vp],
     "mocap_fundamental_ransac": [_vp, _i, _vp, _vp, _ip, _vp, _i, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp],

@@ -45,6 +45,45 @@ int mocap_correspond(mocap_ctx_t c, const void* pts, long pt_st, long pt_sc, con
     return MOCAP_OK;
 }
 
+int mocap_correspond_visible(mocap_ctx_t c, const void* pts, long pt_st, long pt_sc, const int32_t* counts, long cnt_st, long cnt_sc,
+                             int pts_f64, int T, int C, int P, int distorted, double cutoff, double gate, int min_views, double max_err,
+                             int max_passes, int max_hyp, int Q, double* xyz, double* err, int32_t* idx, uint32_t* views, int32_t* n,
+                             void* stream)
+{
+    if (!c || !pts || !counts || !xyz || !err || !idx || !views || !n) return fail(MOCAP_E_INVALID, "null argument");
+    if ((pt_st | pt_sc) & 1) return fail(MOCAP_E_INVALID, "point strides must be even (whole points)");
+    if (T < 1 || C < 2 || C > 32 || P < 1 || P > 255) return fail(MOCAP_E_INVALID, "T=%d C=%d P=%d (C: 2..32, P: 1..255)", T, C, P);
+    if (min_views < 2 || min_views > C) return fail(MOCAP_E_INVALID, "min_views=%d outside 2..C=%d", min_views, C);
+    if (!(isfinite(cutoff) && cutoff > 0) || !(isfinite(gate) && gate > 0) || !(isfinite(max_err) && max_err > 0))
+        return fail(MOCAP_E_INVALID, "cutoff=%g gate=%g max_err=%g must be finite and > 0", cutoff, gate, max_err);
+    if (max_passes < 1 || max_hyp < 1 || max_hyp > 65535 || Q < 1 || Q > 65535 || (distorted != 0 && distorted != 1))
+        return fail(MOCAP_E_INVALID, "max_passes=%d max_hyp=%d Q=%d distorted=%d (max_passes >= 1, max_hyp and Q: 1..65535, distorted: 0 / 1)",
+                    max_passes, max_hyp, Q, distorted);
+    if (c->n_cam < C) return fail(MOCAP_E_STATE, "mocap_set_cameras: %d cameras set, %d needed", c->n_cam, C);
+    if (set_device(c)) return MOCAP_E_HIP;
+    if (!correspond_visible_fits(P, C))
+        return fail(MOCAP_E_UNSUPPORTED, "P=%d points x C=%d cameras needs %zu bytes of LDS per time step", P, C, correspond_visible_smem_bytes(P, C));
+    // the hypotheses of a pass that outgrows LDS live in the error scratch mocap_correspond uses (the context's calls are ordered on one stream)
+    const size_t step_bytes = correspond_visible_step_bytes(C, max_hyp);
+    const size_t need = ((size_t)T * step_bytes + 7) / 8;
+    if (need > c->scratch.n) {
+        std::lock_guard<std::mutex> lk(c->mu);
+        TRY(c->scratch.reserve(need));
+    }
+    VisArgs a;
+    a.cams = c->cams; a.pts = pts; a.counts = counts; a.pt_st = pt_st; a.pt_sc = pt_sc; a.cnt_st = cnt_st; a.cnt_sc = cnt_sc;
+    a.pts_f64 = pts_f64; a.T = T; a.C = C; a.P = P; a.distorted = distorted; a.cutoff = cutoff; a.gate2 = gate * gate; a.max_err = max_err;
+    a.min_views = min_views; a.max_passes = max_passes; a.max_hyp = max_hyp; a.Q = Q;
+    a.xyz = xyz; a.err = err; a.idx = idx; a.views = views; a.n = n;
+    a.scratch = (unsigned char*)(double*)c->scratch; a.step_bytes = step_bytes; a.lds_budget = 0;
+    EvPair p; bool on;
+    prof_begin(c, (hipStream_t)stream, p, on);
+    launch_correspond_visible(a, (hipStream_t)stream);
+    prof_end(c, PROF_CORRESPOND, (hipStream_t)stream, p, on);
+    HIP_TRY(hipGetLastError());
+    return MOCAP_OK;
+}
+
 int mocap_epipolar_scores(mocap_ctx_t c, const void* roots, int n_roots, const void* cand, int n_cand, int pts_f64, int f_index,
                           double* dist, float* lines, void* stream)
 {

@@ -290,6 +290,29 @@ struct CorrArgs {
     int lds_budget;            // set by launch_correspond: bytes of dynamic LDS the kernel's plan is made for
 };
 
+// correspondence from any camera pair, for markers only some cameras see (correspond_visible.hip)
+struct VisArgs {
+    const CameraTable* cams;   // K, dist, R, t of cameras 0..C-1 (F is not used: the pair matrices are formed on the device)
+    const void* pts;           // points and counts through strides, as CorrArgs
+    const int32_t* counts;
+    long pt_st, pt_sc, cnt_st, cnt_sc;
+    int pts_f64;
+    int T, C, P;
+    int distorted;             // 1 = the points are pixels of the distorted images: mapped to ideal pinhole pixels when loaded
+    double cutoff, gate2, max_err; // epipolar limit (px), support limit squared (px^2), error limit (px^2)
+    int min_views, max_passes;
+    int max_hyp;               // seeds of one pass at most; beyond it the time step reports CORR_ERR_GROUPS
+    int Q;                     // output rows per time step
+    double* xyz;               // [T][Q][3]
+    double* err;               // [T][Q]
+    int32_t* idx;              // [T][Q][C] member point per camera, -1 = none
+    uint32_t* views;           // [T][Q] bit c: camera c is a member
+    int32_t* n;                // [T] markers, or CORR_ERR_*
+    unsigned char* scratch;    // [T][correspond_visible_step_bytes(C, max_hyp)] hypothesis records and sort order of the steps that outgrow LDS
+    size_t step_bytes;
+    int lds_budget;            // set by launch_correspond_visible
+};
+
 struct TriArgs {
     const CameraTable* cams;
     const double* pts;         // [N][C][2]
@@ -457,7 +480,7 @@ void launch_intr_linearize(const IntrArgs& a, int it, bool solve, hipStream_t s)
 void launch_intr_iteration(const IntrArgs& a, int it, double ftol, hipStream_t s);
 void launch_intr_finish(const IntrArgs& a, hipStream_t s);
 
-enum { CORR_ERR_GROUPS = -2, CORR_ERR_TRUNCATED = -3, CORR_ERR_BLOB = -4 };
+enum { CORR_ERR_GROUPS = -2, CORR_ERR_TRUNCATED = -3, CORR_ERR_BLOB = -4, CORR_ERR_OUTPUT = -5 };
 enum { FUND_ERR_SAMPLE = -2, FUND_ERR_DEGENERATE = -3 };
 
 void launch_fundamental_ransac(const FundArgs& a, hipStream_t s);
@@ -465,6 +488,10 @@ void launch_fundamental_ransac(const FundArgs& a, hipStream_t s);
 void launch_correspond(const CorrArgs& a, hipStream_t s);
 size_t correspond_smem_bytes(int P, int C);
 bool correspond_fits(int P, int C); // the kernel's LDS plan for P points x C cameras fits a workgroup
+void launch_correspond_visible(const VisArgs& a, hipStream_t s);
+size_t correspond_visible_smem_bytes(int P, int C);
+bool correspond_visible_fits(int P, int C);               // the kernel's LDS plan for P points x C cameras fits a workgroup
+size_t correspond_visible_step_bytes(int C, int max_hyp); // scratch of one time step
 void launch_epipolar_scores(const EpiArgs& a, hipStream_t s);
 void launch_ba_residuals(const BaArgs& a, hipStream_t s);
 void launch_triangulate(const TriArgs& a, hipStream_t s);

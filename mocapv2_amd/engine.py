@@ -290,6 +290,54 @@ class MocapContext:
                                              _ptr(out["root"]), _ptr(out["order"]), _ptr(out["n"]), _stream()))
         return out
 
+    def _vis_out(self, T, Q, Cn):
+        dev = self.device
+        return {"xyz": torch.empty((T, Q, 3), dtype=torch.float64, device=dev),
+                "err": torch.empty((T, Q), dtype=torch.float64, device=dev),
+                "idx": torch.empty((T, Q, Cn), dtype=torch.int32, device=dev),
+                "views": torch.empty((T, Q), dtype=torch.int32, device=dev),  # the uint32 masks' bits (bit 31 = the sign)
+                "n": torch.empty((T,), dtype=torch.int32, device=dev)}
+
+    def _vis_call(self, pts_ptr, pt_st, pt_sc, cnt_ptr, cnt_st, cnt_sc, f64, T, Cn, P, distorted, cutoff, gate, min_views, max_err,
+                  max_passes, max_hyp, Q, out):
+        Q = Cn * P // 2 if Q is None else int(Q)  # every marker claims at least two points: these rows can never run out
+        out = out or self._vis_out(T, Q, Cn)
+        assert out["xyz"].shape == (T, Q, 3) and out["idx"].shape == (T, Q, Cn), (out["xyz"].shape, out["idx"].shape, T, Q, Cn)
+        _abi.check(self.lib.mocap_correspond_visible(self._h, pts_ptr, pt_st, pt_sc, cnt_ptr, cnt_st, cnt_sc, int(f64), T, Cn, P,
+                                                     int(bool(distorted)), float(cutoff), float(gate), int(min_views), float(max_err),
+                                                     int(max_passes), int(max_hyp), Q, _ptr(out["xyz"]), _ptr(out["err"]),
+                                                     _ptr(out["idx"]), _ptr(out["views"]), _ptr(out["n"]), _stream()))
+        return out
+
+    def correspond_visible(self, pts, counts, distorted=False, cutoff=10.0, gate=10.0, min_views=2, max_err=25.0, max_passes=3,
+                           max_hyp=8192, Q=None, out=None):
+        """Markers that only some cameras see, from any camera pair (mocap_correspond_visible; the definition is DESIGN.md
+        section 2).  pts [T, C, P, 2] (int32 or float64), counts [T, C] int32, both on the GPU; needs set_cameras only.
+        distorted: the points are pixels of the distorted images (False: of undistorted ones, as blob_centroids delivers).
+        Returns a dict of device tensors: n [T] (markers per time step, or MOCAP_CORR_E_* < 0), xyz [T, Q, 3], err [T, Q],
+        idx [T, Q, C] (the member point of each camera, -1 = none), views [T, Q] (bit c = camera c is a member; int32 holding
+        the uint32's bits).  Only rows below n[t] are results: the rest is unspecified and must not be read.  Q defaults to
+        C * P // 2, which the markers of a time step cannot exceed."""
+        assert pts.is_cuda and pts.is_contiguous() and counts.is_contiguous() and counts.dtype == torch.int32
+        T, Cn, P, _ = pts.shape
+        f64 = pts.dtype == torch.float64
+        assert f64 or pts.dtype == torch.int32
+        return self._vis_call(_ptr(pts), Cn * P * 2, P * 2, _ptr(counts), Cn, 1, f64, T, Cn, P, distorted, cutoff, gate, min_views,
+                              max_err, max_passes, max_hyp, Q, out)
+
+    def correspond_visible_records(self, records, T, Cn, t0=0, stride_t=None, stride_c=None, P=None, distorted=False, cutoff=10.0,
+                                   gate=10.0, min_views=2, max_err=25.0, max_passes=3, max_hyp=8192, Q=None, out=None):
+        """correspond_visible straight from centroid records, laid out and read as correspond_records reads them."""
+        rec_ints = records.shape[-1]
+        flat = records.reshape(-1, rec_ints)
+        stride_t = Cn if stride_t is None else stride_t
+        stride_c = 1 if stride_c is None else stride_c
+        P = P or min(255, (rec_ints - 2) // 2)
+        base = flat.data_ptr() + 4 * rec_ints * stride_t * t0
+        return self._vis_call(C.c_void_p(base + 8), rec_ints * stride_t, rec_ints * stride_c, C.c_void_p(base), rec_ints * stride_t,
+                              rec_ints * stride_c, False, T, Cn, P, distorted, cutoff, gate, min_views, max_err, max_passes,
+                              max_hyp, Q, out)
+
     def epipolar_scores(self, roots, cand, f_index=0, with_lines=False):
         """The scoring step of the correspondence search for one camera pair (reference lib/Helpers.py:205-220): roots [R, 2]
         camera-0 points, cand [N, 2] points of camera f_index + 1 (host arrays, integer or float) -> distances [R, N] float64

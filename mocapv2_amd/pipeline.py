@@ -139,25 +139,31 @@ CORR_STATUS = {
         "step than max(2 * max_groups, 8192) (raise it with MocapContext.set_tuning('corr_step_groups', n))",
     -3: "a camera holds more image points than the tracker's max_points (MOCAP_CORR_E_TRUNCATED): raise max_points",
     -4: "a camera's blob stage exceeded an internal capacity (MOCAP_CORR_E_BLOB; its record count holds the MOCAP_BLOB_E_* code)",
+    -5: "more markers accepted than the output rows of mocap_correspond_visible hold (MOCAP_CORR_E_OUTPUT): pass a larger Q to "
+        "MocapContext.correspond_visible (the trackers use C * max_points // 2 rows, which a time step cannot exceed)",
 }
+# what -2 means with visibility="any" (mocap_correspond_visible has no groups: its capacity is the seeds of one pass)
+VIS_STATUS = dict(CORR_STATUS)
+VIS_STATUS[-2] = ("more seed pairs in one pass of a time step than mocap_correspond_visible's max_hyp (MOCAP_CORR_E_GROUPS): "
+                  "raise the tracker's max_hyp (at most 65535) or lower its cutoff")
 
 
 class CapacityError(RuntimeError):
     """A time step has no result because a fixed capacity was exceeded.  The reference has no such limits
     (lib/Helpers.py:191,203-245), so the batched path never passes a shortened point list for a result: it fails."""
 
-    def __init__(self, step, code):
-        super().__init__(f"time step {step}: {CORR_STATUS.get(code, 'status %d' % code)}")
+    def __init__(self, step, code, texts=CORR_STATUS):
+        super().__init__(f"time step {step}: {texts.get(code, 'status %d' % code)}")
         self.step, self.code = step, code
 
 
-def check_status(n_roots, first_step=0):
+def check_status(n_roots, first_step=0, texts=CORR_STATUS):
     """n_roots: host array of the per-time-step root counts of a batch.  Raises CapacityError for the first failed
     time step."""
     n_roots = np.asarray(n_roots)
     bad = np.flatnonzero(n_roots < 0)
     if len(bad):
-        raise CapacityError(first_step + int(bad[0]), int(n_roots[bad[0]]))
+        raise CapacityError(first_step + int(bad[0]), int(n_roots[bad[0]]), texts)
     return n_roots
 
 
@@ -179,8 +185,16 @@ class BatchTracker:
 
     def __init__(self, K, dist, R, t, F, width, height, steps_per_rank, world=1, rank=0, device=0, group=None,
                  max_points=32, max_groups=4096, depth=1, bayer_pattern=None, gray_shift=GRAY_SHIFT, collective="auto",
-                 force_collective=False):
-        """collective: how the centroid records are exchanged when world > 1 --
+                 force_collective=False, visibility="all", min_views=2, gate=10.0, max_err=25.0, max_passes=3, cutoff=10.0,
+                 max_hyp=8192):
+        """visibility: which markers stage B reports --
+             "all"   the reference's find_point_correspondance_and_object_points (mocap_correspond): a marker every camera sees,
+                     searched from camera 0's points; the outputs are MocapContext.correspond's;
+             "any"   mocap_correspond_visible: a marker at least min_views cameras see, from any camera pair (cutoff, gate,
+                     max_err, max_passes, max_hyp: its parameters; "all" keeps the reference's cutoff of
+                     10 and ignores them); the outputs are MocapContext.correspond_visible's, and F may be None (the pair
+                     matrices come from the poses).  MocapContext.profile counts its kernel under corr_ms.
+           collective: how the centroid records are exchanged when world > 1 --
              "rccl"  mocap_allgather_centroids: ncclAllGather called by the library on the batch's own HIP stream; ONE
                      communicator per rank, shared by the batches in flight (the library chains their all-gathers with
                      an event); its unique id travels through torch.distributed once, at set-up (negotiate_rccl);
@@ -192,6 +206,13 @@ class BatchTracker:
         self.world, self.rank, self.group = world, rank, group
         self.t_total = self.T * world
         self.max_points, self.max_groups = max_points, max_groups
+        if visibility not in ("all", "any"):
+            raise ValueError(f"visibility {visibility!r}: 'all' or 'any'")
+        if visibility == "all" and F is None:
+            raise ValueError("visibility='all' needs the fundamental matrices F")
+        self.visibility = visibility
+        self.vis_params = {"min_views": min_views, "gate": gate, "max_err": max_err, "max_passes": max_passes, "cutoff": cutoff,
+                           "max_hyp": max_hyp}
         # raw sensor frames: the camera loop's Bayer -> BGR -> gray (RealtimeTracking_FLIR.py:103-104) comes first, with no gray
         # frame in memory: the library forms the gray values where its kernels read them (pattern 0..3 = BG, GB, RG, GR; None =
         # gray frames; MocapContext.blob_centroids says where a context scratch buffer takes over)
@@ -214,7 +235,8 @@ class BatchTracker:
                 for c in local_cams:
                     ctx.set_undistort(self.slot_of[c], K[c], dist[c], warn_dense=d == 0)
             ctx.set_cameras(K, dist, R, t)
-            ctx.set_fundamentals(F)
+            if F is not None:
+                ctx.set_fundamentals(F)
             records = torch.zeros((self.per, self.rec_ints), dtype=torch.int32, device=ctx.device)
             stream = torch.cuda.Stream(device=ctx.device) if depth > 1 else None
             self.lanes.append(_Lane(ctx, records, stream))
@@ -308,7 +330,11 @@ class BatchTracker:
         """Stage B for this rank's time steps [rank * T, (rank + 1) * T) from the records of all cameras
         (world == 1: self.records, time-major; else the all-gathered records, camera-major)."""
         ctx = self.ctx
-        if self.world == 1:
+        if self.visibility == "any":
+            t0, st, sc = (0, self.n_cam, 1) if self.world == 1 else (self.rank * self.T, 1, self.t_total)
+            self.out = ctx.correspond_visible_records(gathered, self.T, self.n_cam, t0=t0, stride_t=st, stride_c=sc,
+                                                      P=self.max_points, out=self.out, **self.vis_params)
+        elif self.world == 1:
             self.out = ctx.correspond_records(gathered, self.T, self.n_cam, t0=0, stride_t=self.n_cam, stride_c=1,
                                               P=self.max_points, max_groups=self.max_groups, out=self.out)
         else:
@@ -360,9 +386,9 @@ class BatchTracker:
 
     def finish(self, out=None, first_step=0):
         """Wait for the batch that produced `out` (default: the most recent one) and return its per-time-step root
-        counts as a host array.  Raises CapacityError when a time step failed (more image points in a camera than
-        max_points, a blob-stage capacity error, too many candidate groups): a batch is never answered with shortened
-        point lists."""
+        counts as a host array (visibility="any": its marker counts).  Raises CapacityError when a time step failed (more
+        image points in a camera than max_points, a blob-stage capacity error, too many candidate groups; "any": too many
+        seeds, more markers than output rows): a batch is never answered with shortened point lists."""
         lane = self._cur
         if out is not None:
             lane = next((l for l in self.lanes if l.out is out), lane)
@@ -371,7 +397,7 @@ class BatchTracker:
             lane.stream.synchronize()
         else:
             torch.cuda.current_stream(lane.ctx.device).synchronize()
-        return check_status(out["n"].cpu().numpy(), first_step)
+        return check_status(out["n"].cpu().numpy(), first_step, VIS_STATUS if self.visibility == "any" else CORR_STATUS)
 
     def profile(self, on=True):
         """HIP-event timing of the kernels of every batch in flight (MocapContext.profile)."""

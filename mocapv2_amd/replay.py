@@ -37,8 +37,12 @@ class ReplayTracker:
     them from the same detections.  `batch` time steps go through the GPU at once."""
 
     def __init__(self, K, dist, R, t, F, width, height, batch=64, obj_count=OBJ_COUNT, device=0, max_points=32,
-                 max_groups=4096, bayer_pattern=None, gray_shift=GRAY_SHIFT, depth=1):
-        """depth > 1: that many batches are in flight on HIP streams of their own (BatchTracker's software pipelining): while
+                 max_groups=4096, bayer_pattern=None, gray_shift=GRAY_SHIFT, depth=1, visibility="all", min_views=2, gate=10.0,
+                 max_err=25.0, max_passes=3, cutoff=10.0, max_hyp=8192):
+        """visibility="any" (BatchTracker's): a time step yields the markers at least min_views cameras see, found from any
+        camera pair, in acceptance order (more views first, then smaller error) -- the first obj_count + 1 of them as
+        object_points, image_points [markers, C, 2] float64 with NaN where a camera does not see the marker; F may be None.
+        depth > 1: that many batches are in flight on HIP streams of their own (BatchTracker's software pipelining): while
         the results of one batch are read back and turned into messages, the next ones are already on the GPU.  The time steps
         come out in order either way."""
         self.n_cam = len(K)
@@ -47,7 +51,10 @@ class ReplayTracker:
         self.width, self.height = width, height
         self.depth = max(1, int(depth))
         self.tracker = BatchTracker(K, dist, R, t, F, width, height, self.batch, device=device, max_points=max_points,
-                                    max_groups=max_groups, bayer_pattern=bayer_pattern, gray_shift=gray_shift, depth=self.depth)
+                                    max_groups=max_groups, bayer_pattern=bayer_pattern, gray_shift=gray_shift, depth=self.depth,
+                                    visibility=visibility, min_views=min_views, gate=gate, max_err=max_err, max_passes=max_passes,
+                                    cutoff=cutoff, max_hyp=max_hyp)
+        self.visibility = visibility
         self.point = [0, 0, 0, 0, 0, 0, 0, 0]  # RealtimeTracking_FLIR.py:171 (eight zeros until the first detection)
         # raw sensor frames: the camera loop's cvtColor(BAYER_GR2BGR) + cvtColor(BGR2GRAY) (:103-104) run on the GPU first, with
         # no gray frame in memory (BatchTracker.extract); bayer_pattern 0..3 = BG, GB, RG, GR (the reference: 3), None = the
@@ -93,6 +100,8 @@ class ReplayTracker:
         steps at once: the `obj_count + 1` selection of lib/Helpers.py:274-279, the image points, and the message bytes -- built
         in bulk (batch_messages), the previous message repeated for time steps without a point (RealtimeTracking_FLIR.py:181-188)."""
         n = self.tracker.finish(out, first_step=b0)[:nb]  # raises CapacityError: no time step is answered from shortened lists
+        if self.visibility == "any":
+            return self._collect_any(b0, nb, out, n)
         xyz = out["xyz"].cpu().numpy()[:nb]
         grp = out["grp"].cpu().numpy()[:nb].astype(np.int64)
         order = out["order"].cpu().numpy()[:nb]
@@ -106,6 +115,30 @@ class ReplayTracker:
         if has.any():
             self.point = [0, 0, 0, 0] + list(obj[np.flatnonzero(has)[-1], 0])  # :184-185
         return {"first_step": b0, "n_steps": nb, "n_roots": n, "kept": kept, "object_points": obj, "image_points": grp, "messages": msgs}
+
+    def _collect_any(self, b0, nb, out, n):
+        """_collect for visibility="any": the rows below n[s] are the markers, already in their order; nothing beyond them is
+        read (mocap_correspond_visible leaves those rows unspecified)."""
+        lane = next(l for l in self.tracker.lanes if l.out is out)
+        xyz = out["xyz"].cpu().numpy()[:nb]
+        idx = out["idx"].cpu().numpy()[:nb]
+        xy, _ = MocapContext.record_views(lane.records)
+        xy = xy.cpu().numpy().reshape(self.batch, self.n_cam, -1, 2)[:nb]
+        Q = xyz.shape[1]
+        live = np.arange(Q)[None, :] < n[:, None]                     # [nb, Q]: the row holds a marker
+        oc = self.obj_count
+        kept = np.where(n >= oc, np.minimum(n, oc + 1), n)
+        width = min(oc + 1, Q)
+        obj = np.where(live[:, :width, None], xyz[:, :width], 0.0)   # sliced by n before anything else looks at it
+        member = live[:, :, None] & (idx >= 0)                        # [nb, Q, C]
+        pick = np.where(member, idx, 0)
+        img = xy[np.arange(nb)[:, None, None], np.arange(self.n_cam)[None, None, :], pick].astype(np.float64)  # [nb, Q, C, 2]
+        img[~member] = np.nan
+        has = kept > 0
+        msgs = batch_messages(obj[:, 0], has, tracker_message(self.point))
+        if has.any():
+            self.point = [0, 0, 0, 0] + list(obj[np.flatnonzero(has)[-1], 0])
+        return {"first_step": b0, "n_steps": nb, "n_roots": n, "kept": kept, "object_points": obj, "image_points": img, "messages": msgs}
 
     def run_batches(self, frames, send_many=None):
         """Generator over BATCHES of time steps: dicts with first_step, n_steps, n_roots [n], kept [n] (object points per time

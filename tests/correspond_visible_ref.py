@@ -1,0 +1,403 @@
+"""NumPy restatement of mocap_correspond_visible's definition: markers that only some cameras see,
+found from any camera pair.  The same FP64 operations in the same order as csrc/correspond_visible.hip -- every product and
+sum written out (no np.sum, no @), the Jacobi rotations of smallest_eigvec4 included -- evaluated for all seeds of a pass at
+once: an elementwise NumPy operation rounds as the scalar one does, and what the kernel decides per lane (the sweeps' early
+exit, skipped rotations) is decided per element here with masks.
+
+correspond_visible() handles one time step and also returns the smallest decision margin of the run: how far the closest of
+its comparisons was from going the other way.  scene_case() builds the inputs with ground truth from synth.Scene, and
+exact_hypotheses() evaluates given member sets independently (extended-precision sums, np.linalg.eigh)."""
+import numpy as np
+
+E_GROUPS, E_TRUNCATED, E_BLOB, E_OUTPUT = -2, -3, -4, -5
+
+
+# ---- the library's device helpers ---------------------------------------------------------------------------------------
+def smallest_eigvec4(B):
+    """geom_dev.h: smallest_eigvec4 for B [N, 4, 4] -> v [N, 4] (cyclic Jacobi, the same rotations)"""
+    B = np.array(B, np.float64)
+    N = len(B)
+    V = np.zeros((N, 4, 4))
+    for k in range(4):
+        V[:, k, k] = 1.0
+    active = np.ones(N, bool)
+    with np.errstate(all="ignore"):
+        for _ in range(60):
+            off, diag = np.zeros(N), np.zeros(N)
+            for p in range(4):
+                diag = diag + B[:, p, p] * B[:, p, p]
+                for q in range(p + 1, 4):
+                    off = off + B[:, p, q] * B[:, p, q]
+            active = active & ~((off == 0.0) | (off <= 1e-40 * diag))
+            if not active.any():
+                break
+            for p in range(3):
+                for q in range(p + 1, 4):
+                    apq = B[:, p, q].copy()
+                    m = active & (apq != 0.0)
+                    theta = (B[:, q, q] - B[:, p, p]) / (2.0 * apq)
+                    t = np.where(theta >= 0, 1.0, -1.0) / (np.abs(theta) + np.sqrt(theta * theta + 1.0))
+                    c = 1.0 / np.sqrt(t * t + 1.0)
+                    s = t * c
+                    for k in range(4):
+                        bkp, bkq = B[:, k, p].copy(), B[:, k, q].copy()
+                        B[:, k, p] = np.where(m, c * bkp - s * bkq, bkp)
+                        B[:, k, q] = np.where(m, s * bkp + c * bkq, bkq)
+                    for k in range(4):
+                        bpk, bqk = B[:, p, k].copy(), B[:, q, k].copy()
+                        B[:, p, k] = np.where(m, c * bpk - s * bqk, bpk)
+                        B[:, q, k] = np.where(m, s * bpk + c * bqk, bqk)
+                    for k in range(4):
+                        vkp, vkq = V[:, k, p].copy(), V[:, k, q].copy()
+                        V[:, k, p] = np.where(m, c * vkp - s * vkq, vkp)
+                        V[:, k, q] = np.where(m, s * vkp + c * vkq, vkq)
+    best = B[:, 0, 0].copy()
+    sel = np.zeros(N, np.int64)
+    for k in range(1, 4):
+        lt = B[:, k, k] < best
+        best = np.where(lt, B[:, k, k], best)
+        sel = np.where(lt, k, sel)
+    return V[np.arange(N)[:, None], np.arange(4)[None, :], sel[:, None]]
+
+
+def dlt_rows(Pm, x, y):
+    """DltAcc::add_rows: the 4x4 contribution r0 r0^T + r1 r1^T of one view; Pm [N, 12], x, y [N] -> [N, 4, 4]"""
+    r0 = [y * Pm[:, 8 + k] - Pm[:, 4 + k] for k in range(4)]
+    r1 = [Pm[:, k] - x * Pm[:, 8 + k] for k in range(4)]
+    T = np.empty((len(x), 4, 4))
+    for j in range(4):
+        for k in range(4):
+            T[:, j, k] = r0[j] * r0[k] + r1[j] * r1[k]
+    return T
+
+
+def undistort_points(pts, K, dist):
+    """calibrate.undistort_points (cv.undistortPoints(p, K, dist, P=K)): five fixed-point rounds, the same operations"""
+    K = np.asarray(K, float).reshape(9)
+    k1, k2, p1, p2, k3 = np.asarray(dist, float).ravel()[:5]
+    fx, cx, fy, cy = K[0], K[2], K[4], K[5]
+    x0, y0 = (pts[..., 0] - cx) / fx, (pts[..., 1] - cy) / fy
+    x, y = x0, y0
+    for _ in range(5):
+        r2 = x * x + y * y
+        icd = 1.0 / (1 + ((k3 * r2 + k2) * r2 + k1) * r2)
+        dx, dy = 2 * p1 * x * y + p2 * (r2 + 2 * x * x), p1 * (r2 + 2 * y * y) + 2 * p2 * x * y
+        x, y = (x0 - dx) * icd, (y0 - dy) * icd
+    return np.stack([fx * x + cx, fy * y + cy], -1)
+
+
+class Cameras:
+    """What the kernel forms once per time step: P = K [R|t], K^-1 = adj(K) / det(K), and F_ab for every a < b"""
+
+    def __init__(self, K, dist, R, t):
+        self.K = np.asarray(K, float).reshape(-1, 9)
+        self.C = C = len(self.K)
+        self.dist = np.asarray(dist, float).reshape(C, 5)
+        self.R = np.asarray(R, float).reshape(C, 9)
+        self.t = np.asarray(t, float).reshape(C, 3)
+        self.P = np.empty((C, 12))
+        self.Ki = np.empty((C, 9))
+        for c in range(C):
+            Kc, Rc, tc = self.K[c], self.R[c], self.t[c]
+            for r in range(3):
+                for cc in range(4):
+                    s = 0.0
+                    for k in range(3):
+                        s = s + Kc[3 * r + k] * (Rc[3 * k + cc] if cc < 3 else tc[k])
+                    self.P[c, 4 * r + cc] = s
+            c00, c01, c02 = Kc[4] * Kc[8] - Kc[5] * Kc[7], Kc[2] * Kc[7] - Kc[1] * Kc[8], Kc[1] * Kc[5] - Kc[2] * Kc[4]
+            c10, c11, c12 = Kc[5] * Kc[6] - Kc[3] * Kc[8], Kc[0] * Kc[8] - Kc[2] * Kc[6], Kc[2] * Kc[3] - Kc[0] * Kc[5]
+            c20, c21, c22 = Kc[3] * Kc[7] - Kc[4] * Kc[6], Kc[1] * Kc[6] - Kc[0] * Kc[7], Kc[0] * Kc[4] - Kc[1] * Kc[3]
+            det = Kc[0] * c00 + Kc[1] * c10 + Kc[2] * c20
+            self.Ki[c] = [v / det for v in (c00, c01, c02, c10, c11, c12, c20, c21, c22)]
+        self.pairs = [(a, b) for a in range(C) for b in range(a + 1, C)]
+        self.F = np.array([self._pair(a, b) for a, b in self.pairs])
+
+    def _pair(self, a, b):
+        Ra, Rb, ta, tb, Kia, Kib = self.R[a], self.R[b], self.t[a], self.t[b], self.Ki[a], self.Ki[b]
+
+        def mat(f):
+            out = np.empty(9)
+            for i in range(3):
+                for j in range(3):
+                    s = 0.0
+                    for k in range(3):
+                        s = s + f(i, j, k)
+                    out[3 * i + j] = s
+            return out
+        Rr = mat(lambda i, j, k: Rb[3 * i + k] * Ra[3 * j + k])
+        tr = np.empty(3)
+        for i in range(3):
+            s = 0.0
+            for k in range(3):
+                s = s + Rr[3 * i + k] * ta[k]
+            tr[i] = tb[i] - s
+        tx = np.array([0.0, -tr[2], tr[1], tr[2], 0.0, -tr[0], -tr[1], tr[0], 0.0])
+        E = mat(lambda i, j, k: tx[3 * i + k] * Rr[3 * k + j])
+        M = mat(lambda i, j, k: Kib[3 * k + i] * E[3 * k + j])
+        return mat(lambda i, j, k: M[3 * i + k] * Kia[3 * k + j])
+
+    def depth(self, c, X):
+        R, t = self.R[c], self.t[c]
+        return R[6] * X[:, 0] + R[7] * X[:, 1] + R[8] * X[:, 2] + t[2]
+
+    def pinhole(self, c, X):
+        R, t, K = self.R[c], self.t[c], self.K[c]
+        x = R[0] * X[:, 0] + R[1] * X[:, 1] + R[2] * X[:, 2] + t[0]
+        y = R[3] * X[:, 0] + R[4] * X[:, 1] + R[5] * X[:, 2] + t[1]
+        z = self.depth(c, X)
+        xn, yn = x / z, y / z
+        return K[0] * xn + K[2], K[4] * yn + K[5]
+
+
+def _solve_members(cams, pts, M):
+    """X [N, 3] of member sets M [N, C] (-1 = none): DLT in ascending camera order; valid = finite and in front of every member"""
+    N, C = M.shape
+    B = np.zeros((N, 4, 4))
+    for c in range(C):
+        has = M[:, c] >= 0
+        p = np.where(has, M[:, c], 0)
+        T = dlt_rows(np.broadcast_to(cams.P[c], (N, 12)), pts[c, p, 0], pts[c, p, 1])
+        B = np.where(has[:, None, None], B + T, B)
+    v = smallest_eigvec4(B)
+    X = v[:, :3] / v[:, 3:4]
+    valid = np.isfinite(X).all(axis=1)
+    for c in range(C):
+        valid = valid & ((M[:, c] < 0) | (cams.depth(c, X) > 0.0))
+    return X, valid
+
+
+def _member_err(cams, pts, M, X):
+    N, C = M.shape
+    s = np.zeros(N)
+    for c in range(C):
+        has = M[:, c] >= 0
+        p = np.where(has, M[:, c], 0)
+        u, v = cams.pinhole(c, X)
+        du, dv = pts[c, p, 0] - u, pts[c, p, 1] - v
+        s = np.where(has, (s + du * du) + dv * dv, s)
+    return s / (2 * (M >= 0).sum(axis=1)).astype(np.float64)
+
+
+def correspond_visible(pts, counts, K, dist, R, t, distorted=0, cutoff=10.0, gate=10.0, min_views=2, max_err=25.0, max_passes=3,
+                       max_hyp=8192, Q=None):
+    """One time step.  pts [C, P, 2] (any numeric type), counts [C].  Returns dict: n (markers, or E_*), xyz [n, 3], err [n],
+    idx [n, C] (-1 = none), views [n] (uint32 masks), margin (the smallest decision margin), seeds (per pass), passes."""
+    pts = np.asarray(pts).astype(np.float64)
+    counts = np.asarray(counts).astype(np.int64)
+    C, P = pts.shape[:2]
+    Q = C * P // 2 if Q is None else Q
+    fail = lambda code, **kw: dict(n=code, xyz=np.zeros((0, 3)), err=np.zeros(0), idx=np.zeros((0, C), np.int32),
+                                   views=np.zeros(0, np.uint32), margin=np.inf, **kw)
+    if (counts < 0).any():
+        return fail(E_BLOB)
+    if (counts > P).any():
+        return fail(E_TRUNCATED)
+    cams = Cameras(K, dist, R, t)
+    if distorted:
+        pts = np.stack([undistort_points(pts[c], cams.K[c], cams.dist[c]) for c in range(C)])
+    gate2 = gate * gate
+    claimed = np.zeros((C, P), bool)
+    out_xyz, out_err, out_idx = [], [], []
+    margin = np.inf
+    seeds_per_pass = []
+    err_state = np.seterr(all="ignore")
+    try:
+        for _ in range(max_passes):
+            free = [np.flatnonzero(~claimed[c, :counts[c]]) for c in range(C)]
+            # 1. seeds
+            sa, si, sb, sj = [], [], [], []
+            for pr, (a, b) in enumerate(cams.pairs):
+                ia, jb = free[a], free[b]
+                if not len(ia) or not len(jb):
+                    continue
+                F = cams.F[pr]
+                x, y = pts[a, ia, 0], pts[a, ia, 1]
+                la = F[0] * x + F[1] * y + F[2]
+                lb = F[3] * x + F[4] * y + F[5]
+                lc = F[6] * x + F[7] * y + F[8]
+                nu = la * la + lb * lb
+                ok = nu > 0.0
+                sc = 1.0 / np.sqrt(nu)
+                la, lb, lc = la * sc, lb * sc, lc * sc
+                d = np.abs(la[:, None] * pts[b, jb, 0][None, :] + lb[:, None] * pts[b, jb, 1][None, :] + lc[:, None])
+                d = np.where(ok[:, None], d, np.inf)
+                if np.isfinite(d).any():
+                    margin = min(margin, np.abs(d[np.isfinite(d)] - cutoff).min())
+                ii, jj = np.nonzero(d < cutoff)
+                sa += [a] * len(ii); sb += [b] * len(ii)
+                si += ia[ii].tolist(); sj += jb[jj].tolist()
+            N = len(sa)
+            seeds_per_pass.append(N)
+            if N > max_hyp:
+                return fail(E_GROUPS, seeds=seeds_per_pass)
+            if N == 0:
+                break
+            sa, si, sb, sj = (np.array(v, np.int64) for v in (sa, si, sb, sj))
+            # 2. seed point
+            B = np.zeros((N, 4, 4))
+            B = B + dlt_rows(cams.P[sa], pts[sa, si, 0], pts[sa, si, 1])
+            B = B + dlt_rows(cams.P[sb], pts[sb, sj, 0], pts[sb, sj, 1])
+            v = smallest_eigvec4(B)
+            X2 = v[:, :3] / v[:, 3:4]
+            ok = (v[:, 3] != 0.0) & np.isfinite(X2).all(axis=1)
+            for c in range(C):
+                ok = ok & (((sa != c) & (sb != c)) | (cams.depth(c, X2) > 0.0))
+            # 3. support
+            M = np.full((N, C), -1, np.int64)
+            M[np.arange(N), sa] = si
+            M[np.arange(N), sb] = sj
+            for c in range(C):
+                sel = ok & (sa != c) & (sb != c) & (cams.depth(c, X2) > 0.0)
+                if not sel.any() or not len(free[c]):
+                    continue
+                u, vv = cams.pinhole(c, X2)
+                du = pts[c, free[c], 0][None, :] - u[:, None]
+                dv = pts[c, free[c], 1][None, :] - vv[:, None]
+                d2 = du * du + dv * dv
+                fin = np.isfinite(d2) & sel[:, None]
+                if fin.any():
+                    margin = min(margin, np.abs(d2[fin] - gate2).min())
+                d2 = np.where(d2 < gate2, d2, np.inf)  # (NaN compares false, as in the kernel)
+                best = np.argmin(d2, axis=1)           # the first of the smallest: ties go to the lowest index
+                bestv = d2[np.arange(N), best]
+                has = sel & np.isfinite(bestv)
+                M[has, c] = free[c][best[has]]
+                if d2.shape[1] > 1 and has.any():      # gap to the second-best candidate inside the gate
+                    rest = d2.copy()
+                    rest[np.arange(N), best] = np.inf
+                    gap = rest.min(axis=1) - bestv
+                    gap = gap[has & np.isfinite(rest.min(axis=1))]
+                    if len(gap):
+                        margin = min(margin, gap.min())
+            # 4. hypothesis
+            m = (M >= 0).sum(axis=1)
+            cand = np.flatnonzero(ok & (m >= min_views))
+            kept = []
+            if len(cand):
+                X, valid = _solve_members(cams, pts, M[cand])
+                err = _member_err(cams, pts, M[cand], X)
+                if valid.any():
+                    margin = min(margin, np.abs(err[valid] - max_err).min())
+                for q in np.flatnonzero(valid & (err < max_err)):
+                    h = cand[q]
+                    kept.append(((-int(m[h]), float(err[q]), int(sa[h]), int(si[h]), int(sb[h]), int(sj[h])), tuple(M[h]), X[q]))
+            # 5. selection
+            kept.sort(key=lambda r: r[0])
+            last = None
+            for r in kept:  # err gap between neighbouring hypotheses of equal view count with different members
+                if last is not None and last[0][0] == r[0][0] and last[1] != r[1]:
+                    margin = min(margin, abs(r[0][1] - last[0][1]))
+                last = r
+            accepted = 0
+            for key, members, X in kept:
+                if any(p >= 0 and claimed[c, p] for c, p in enumerate(members)):
+                    continue
+                if len(out_xyz) >= Q:
+                    return fail(E_OUTPUT, seeds=seeds_per_pass)
+                for c, p in enumerate(members):
+                    if p >= 0:
+                        claimed[c, p] = True
+                out_xyz.append(X); out_err.append(key[1]); out_idx.append(members)
+                accepted += 1
+            if accepted == 0:
+                break
+    finally:
+        np.seterr(**err_state)
+    n = len(out_xyz)
+    idx = np.array(out_idx, np.int32).reshape(n, C)
+    views = ((idx >= 0).astype(np.uint64) << np.arange(C, dtype=np.uint64)[None, :]).sum(axis=1).astype(np.uint32)
+    return dict(n=n, xyz=np.array(out_xyz, np.float64).reshape(n, 3), err=np.array(out_err, np.float64), idx=idx, views=views,
+                margin=float(margin), seeds=seeds_per_pass, passes=len(seeds_per_pass))
+
+
+# ---- an independent evaluation of given member sets ---------------------------------------------------------------------
+def exact_hypotheses(pts, idx, K, dist, R, t, distorted=0):
+    """xyz [n, 3] and err [n] of the member sets idx [n, C], evaluated another way: projection matrices and A^T A summed in
+    extended precision (np.longdouble), the eigenvector from np.linalg.eigh, the residuals in extended precision."""
+    ld = np.longdouble
+    pts = np.asarray(pts).astype(np.float64)
+    C = pts.shape[0]
+    K = np.asarray(K, float).reshape(C, 3, 3)
+    R, t = np.asarray(R, float).reshape(C, 3, 3), np.asarray(t, float).reshape(C, 3)
+    if distorted:
+        pts = np.stack([undistort_points(pts[c], K[c], np.asarray(dist, float).reshape(C, 5)[c]) for c in range(C)])
+    Pm = [K[c].astype(ld) @ np.concatenate([R[c], t[c][:, None]], axis=1).astype(ld) for c in range(C)]
+    xyz, err = [], []
+    for row in np.asarray(idx):
+        rows = []
+        for c, p in enumerate(row):
+            if p >= 0:
+                x, y = ld(pts[c, p, 0]), ld(pts[c, p, 1])
+                rows += [y * Pm[c][2] - Pm[c][1], Pm[c][0] - x * Pm[c][2]]
+        A = np.array(rows, ld)
+        w, V = np.linalg.eigh((A.T @ A).astype(np.float64))
+        v = V[:, 0].astype(ld)
+        X = v[:3] / v[3]
+        s, m = ld(0), 0
+        for c, p in enumerate(row):
+            if p >= 0:
+                pc = R[c].astype(ld) @ X + t[c].astype(ld)
+                u, vv = K[c, 0, 0] * (pc[0] / pc[2]) + K[c, 0, 2], K[c, 1, 1] * (pc[1] / pc[2]) + K[c, 1, 2]
+                s += (ld(pts[c, p, 0]) - u) ** 2 + (ld(pts[c, p, 1]) - vv) ** 2
+                m += 1
+        xyz.append(X.astype(np.float64)); err.append(float(s / (2 * m)))
+    n = len(xyz)
+    return np.array(xyz, np.float64).reshape(n, 3), np.array(err, np.float64)
+
+
+def deviation(xyz, err, xyz_ref, err_ref):
+    """The relative deviation the GPU test's tolerance is made from: per marker |X - X_ref| / |X_ref| and |err - err_ref| / err_ref,
+    the larger of the two over all markers.  (Every scene of the tests carries jitter or floored pixels, so err_ref is 1e-3 px^2
+    at the least and the quotient is well defined.)"""
+    if not len(xyz_ref):
+        return 0.0
+    dx = np.linalg.norm(np.asarray(xyz) - xyz_ref, axis=1) / np.linalg.norm(xyz_ref, axis=1)
+    de = np.abs(np.asarray(err) - err_ref) / err_ref
+    return float(max(dx.max(), de.max()))
+
+
+# ---- scenes with ground truth ------------------------------------------------------------------------------------------------
+def scene_arrays(scene):
+    C = scene.n_cam
+    return (np.stack([scene.K] * C), np.stack([scene.dist] * C), np.stack([p["R"] for p in scene.poses]),
+            np.stack([p["t"] for p in scene.poses]))
+
+
+def scene_case(n_cam, n_markers, p_hide, seed, jitter=0.5, blind=(), false_blobs=0, P=None, dist=None, distorted=False):
+    """A synth.Scene ring rig in 1920x1080 with markers in a 1 m cube; every view hidden independently with probability p_hide
+    (cameras in `blind` see nothing), Gaussian jitter on the pixels, `false_blobs` uniformly placed extra points per camera,
+    every camera's list shuffled.  Returns (scene, pts [C, P, 2] float64, counts [C] int32, truth [M, C]: the index of marker
+    m in camera c's list or -1, markers [M, 3])."""
+    from mocapv2_amd.synth import ZERO_DIST, Scene
+    rng = np.random.default_rng(seed)
+    scene = Scene(n_cam, 1920, 1080, dist=ZERO_DIST if dist is None else dist)
+    markers = scene.markers(rng, n_markers)
+    hidden = rng.random((n_markers, n_cam)) < p_hide
+    hidden[:, list(blind)] = True
+    P = P or n_markers + false_blobs
+    pts = np.zeros((n_cam, P, 2))
+    counts = np.zeros(n_cam, np.int32)
+    truth = np.full((n_markers, n_cam), -1, np.int64)
+    for c in range(n_cam):
+        px = scene.pixels(markers, c, distorted=distorted) + rng.normal(0, jitter, (n_markers, 2))
+        vis = np.flatnonzero(~hidden[:, c])
+        rows = [(px[m], m) for m in vis] + [(rng.uniform((0, 0), (1920, 1080)), -1) for _ in range(false_blobs)]
+        order = rng.permutation(len(rows))
+        for slot, k in enumerate(order):
+            pts[c, slot] = rows[k][0]
+            if rows[k][1] >= 0:
+                truth[rows[k][1], c] = slot
+        counts[c] = len(rows)
+    return scene, pts, counts, truth, markers
+
+
+def check_against_truth(res, truth, markers, min_views=2):
+    """(missed, ghosts, worst distance to truth): every marker with >= min_views views must come out with exactly its index
+    row; every other output row is a ghost."""
+    want = {tuple(row): m for m, row in enumerate(truth) if (row >= 0).sum() >= min_views}
+    got = [tuple(int(v) for v in row) for row in res["idx"]]
+    missed = [m for row, m in want.items() if row not in got]
+    ghosts = [row for row in got if row not in want]
+    worst = max([float(np.linalg.norm(res["xyz"][q] - markers[want[row]])) for q, row in enumerate(got) if row in want], default=0.0)
+    return missed, ghosts, worst
