@@ -217,10 +217,11 @@ def apply_step(kd, R, t, dc, dp):
     return kd + dc, R2, t + dp[:, 3:]
 
 
-def lm(cam, kd, R, t, max_iters=50, ftol=1e-12, lambda0=1e-3):
+def lm(cam, kd, R, t, max_iters=50, ftol=1e-12, lambda0=1e-3, trace=None):
     """The loop of one camera.  dict: kd, R, t, status, iterations, cost_initial, cost, rms_px, view_rms, history
     [iterations][4] = (cost after the iteration, lambda it was solved with, accepted, |step|), rho [iterations] (nan for a
-    failed factorisation).  status E_BEHIND: the start is returned."""
+    failed factorisation).  status E_BEHIND: the start is returned.  trace: a list that gets one dict per iteration, lam, lin (the
+    pieces of linearize at that damping) and trial (the trial kd, R, t; None for a failed solve)."""
     kd, R, t = np.array(kd, float).reshape(9), np.array(R, float).reshape(-1, 3, 3), np.array(t, float).reshape(-1, 3)
     vc, front = view_costs(cam, kd, R, t)
     cost0 = cost_of(cam, kd, R, t)[0]
@@ -231,11 +232,16 @@ def lm(cam, kd, R, t, max_iters=50, ftol=1e-12, lambda0=1e-3):
 
     def try_step(state, lam):  # a state: (kd, R, t, its sum r^2 per view)
         kd, R, t, _ = state
-        step = schur_step(linearize(cam, kd, R, t, lam), lam)
+        lin = linearize(cam, kd, R, t, lam)
+        step = schur_step(lin, lam)
+        if trace is not None:
+            trace.append({"lam": lam, "lin": lin, "trial": None})
         if step is None:
             return None
         dc, dp, pred, n2 = step
         kd2, R2, t2 = apply_step(kd, R, t, dc, dp)
+        if trace is not None:
+            trace[-1]["trial"] = (kd2, R2, t2)
         vc2, ok = view_costs(cam, kd2, R2, t2)
         return (kd2, R2, t2, vc2), cost_of(cam, kd2, R2, t2)[0], ok, pred, float(np.sqrt(n2))
 
@@ -489,19 +495,37 @@ def order_spread(cam, kd, R, t, lam, n_perm=10):
     return out
 
 
-def loop_spread(cam, kd, R, t, ftol=LOOP_FTOL, n_perm=10):
-    """The loop on the problem and on n_perm seeded permutations: (base run, every run took the base run's decisions, largest
-    relative spread of the per-iteration cost)"""
-    base = lm(cam, kd, R, t, ftol=ftol)
-    same, spread = True, 0.0
+def loop_spreads(cam, kd, R, t, ftol=LOOP_FTOL, max_iters=50, lambda0=1e-3, n_perm=10):
+    """The loop on the problem and on n_perm seeded permutations: (base run, with its trace; every run took the base run's
+    decisions: iterations, status, accept sequence, failed solves; spread).  spread: dict of cost, lambda, step [iterations], the largest
+    relative difference of that history column from the base run's in each iteration (0 where the base entry is 0), and of
+    kd, poses: the largest difference of the returned state, relative to the array's largest entry (poses: R and t of every
+    view as [12], views back in the problem's order).  Runs that decided otherwise are left out of the spread."""
+    trace = []
+    base = lm(cam, kd, R, t, max_iters, ftol, lambda0, trace=trace)
+    base["trace"] = trace
+    n = base["iterations"]
+    same, spread = True, {"cost": np.zeros(n), "lambda": np.zeros(n), "step": np.zeros(n), "kd": 0.0, "poses": 0.0}
+    state = lambda run, order=None: np.c_[run["R"].reshape(-1, 9), run["t"]] if order is None else np.c_[run["R"].reshape(-1, 9), run["t"]][np.argsort(order)]
     for s in range(n_perm):
-        cam2, R2, t2, _ = permuted(cam, R, t, 2000 + s)
-        run = lm(cam2, kd, R2, t2, ftol=ftol)
-        if run["iterations"] != base["iterations"] or run["status"] != base["status"] or not np.array_equal(run["history"][:, 2], base["history"][:, 2]):
+        cam2, R2, t2, order = permuted(cam, R, t, 2000 + s)
+        run = lm(cam2, kd, R2, t2, max_iters, ftol, lambda0)
+        if (run["iterations"] != n or run["status"] != base["status"] or not np.array_equal(run["history"][:, 2], base["history"][:, 2])
+                or not np.array_equal(np.isnan(run["rho"]), np.isnan(base["rho"]))):
             same = False
             continue
-        spread = max(spread, float(np.abs(run["history"][:, 0] / base["history"][:, 0] - 1).max()))
+        for k, col in (("cost", 0), ("lambda", 1), ("step", 3)):
+            a, b = base["history"][:, col], run["history"][:, col]
+            spread[k] = np.maximum(spread[k], np.where(a == 0, np.abs(b), np.abs(b / np.where(a == 0, 1.0, a) - 1)))
+        spread["kd"] = max(spread["kd"], float(np.abs(run["kd"] - base["kd"]).max() / np.abs(base["kd"]).max()))
+        spread["poses"] = max(spread["poses"], float(np.abs(state(run, order) - state(base)).max() / np.abs(state(base)).max()))
     return base, same, spread
+
+
+def loop_spread(cam, kd, R, t, ftol=LOOP_FTOL, n_perm=10, max_iters=50, lambda0=1e-3):
+    """loop_spreads with the spread of the per-iteration cost only, as one number: (base run, same decisions, spread)"""
+    base, same, spread = loop_spreads(cam, kd, R, t, ftol, max_iters, lambda0, n_perm)
+    return base, same, float(spread["cost"].max()) if len(spread["cost"]) else 0.0
 
 
 def param_errors(kd, truth):

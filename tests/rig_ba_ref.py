@@ -226,9 +226,10 @@ def rescale(R, t, X, t1_norm):
     return R, t * s, X * s
 
 
-def lm(prob, R, t, X, max_iters=50, ftol=1e-12, lambda0=1e-3):
+def lm(prob, R, t, X, max_iters=50, ftol=1e-12, lambda0=1e-3, trace=None):
     """The loop.  dict: R, t, X (gauge restored), status, iterations, cost_initial, cost, history [iterations][4] = (cost after
-    the iteration, lambda it was solved with, accepted, |step|), rho [iterations] (nan for a Cholesky failure)."""
+    the iteration, lambda it was solved with, accepted, |step|), rho [iterations] (nan for a Cholesky failure).  trace: a list
+    that gets one dict per iteration, S (the damped reduced matrix) and trial (the trial state, None for a failed solve)."""
     R, t, X = np.array(R, float), np.array(t, float).reshape(-1, 3), np.array(X, float)
     R[0], t[0] = np.eye(3), 0.0
     t1_norm = float(np.sqrt((t[1, 0] * t[1, 0] + t[1, 1] * t[1, 1]) + t[1, 2] * t[1, 2]))
@@ -237,11 +238,16 @@ def lm(prob, R, t, X, max_iters=50, ftol=1e-12, lambda0=1e-3):
         raise ValueError("the state handed in has a point behind a camera that sees it")
 
     def try_step(state, lam):
-        step = schur_step(prob, linearize(prob, *state, lam), lam)
+        lin = linearize(prob, *state, lam)
+        step = schur_step(prob, lin, lam)
+        if trace is not None:
+            trace.append({"S": lin["S"], "trial": None})
         if step is None:
             return None
         dc, dp, pred = step
         trial_state = apply_step(prob, *state, dc, dp)
+        if trace is not None:
+            trace[-1]["trial"] = trial_state
         return (trial_state, *cost_of(prob, *trial_state), pred, float(np.sqrt(np.sum(dp * dp) + np.sum(dc * dc))))
 
     (R, t, X), cost, status, history, rho = lm_ref.control((R, t, X), cost0, try_step, max_iters, ftol, lambda0)

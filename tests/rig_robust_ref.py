@@ -69,8 +69,9 @@ def linearize(prob, R, t, X, lam, c):
     return lin
 
 
-def lm(prob, R, t, X, c, max_iters=50, ftol=1e-12, lambda0=1e-3):
-    """The loop of rig_ba_ref.lm under the loss; the dict of rig_ba_ref.lm plus err, w [n_obs] at the returned state"""
+def lm(prob, R, t, X, c, max_iters=50, ftol=1e-12, lambda0=1e-3, trace=None):
+    """The loop of rig_ba_ref.lm under the loss; the dict of rig_ba_ref.lm plus err, w [n_obs] at the returned state.  trace: as
+    rig_ba_ref.lm's"""
     R, t, X = np.array(R, float), np.array(t, float).reshape(-1, 3), np.array(X, float)
     R[0], t[0] = np.eye(3), 0.0
     t1_norm = float(np.sqrt((t[1, 0] * t[1, 0] + t[1, 1] * t[1, 1]) + t[1, 2] * t[1, 2]))
@@ -79,11 +80,16 @@ def lm(prob, R, t, X, c, max_iters=50, ftol=1e-12, lambda0=1e-3):
         raise ValueError("the state handed in has a point behind a camera that sees it")
 
     def try_step(state, lam):
-        step = rb.schur_step(prob, linearize(prob, *state, lam, c), lam)
+        lin = linearize(prob, *state, lam, c)
+        step = rb.schur_step(prob, lin, lam)
+        if trace is not None:
+            trace.append({"S": lin["S"], "trial": None})
         if step is None:
             return None
         dc, dp, pred = step
         trial_state = rb.apply_step(prob, *state, dc, dp)
+        if trace is not None:
+            trace[-1]["trial"] = trial_state
         return (trial_state, *cost_of(prob, *trial_state, c), pred, float(np.sqrt(np.sum(dp * dp) + np.sum(dc * dc))))
 
     (R, t, X), cost, status, history, rhos = lm_ref.control((R, t, X), cost0, try_step, max_iters, ftol, lambda0)
