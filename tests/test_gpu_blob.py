@@ -82,26 +82,42 @@ def test_filter_mask_against_scipy_without_the_c_oracle(torch_cuda, W, H):
         assert exp.any()
 
 
+def ring_frame(rng, H, W, n=24):
+    """saturated discs on black with a dark core, some cores off-centre, every third core with a bright dot in it"""
+    img = np.zeros((H, W), np.uint8)
+    yy, xx = np.mgrid[0:H, 0:W]
+    for k in range(n):
+        cx, cy, r = rng.uniform(0, W), rng.uniform(0, H), rng.uniform(18, 40)
+        img[(xx - cx) ** 2 + (yy - cy) ** 2 <= r * r] = 255
+        hx, hy, q = cx + rng.uniform(-0.2, 0.2) * r, cy + rng.uniform(-0.2, 0.2) * r, rng.uniform(0.3, 0.55) * r
+        img[(xx - hx) ** 2 + (yy - hy) ** 2 <= q * q] = 0
+        if k % 3 == 0:
+            img[(xx - hx) ** 2 + (yy - hy) ** 2 <= (0.4 * q) ** 2] = 255
+    return img
+
+
 def test_borders_against_scipy_labels_and_picks_theorem(torch_cuda):
     """Oracle-free properties of the contour stage (SURVEY.md 8c lists them as stand-ins for the missing cv2 pair), on the GPU's own
     mask of 1080p frames with 24 discs: as many outer borders as 8-connected foreground components and as many hole borders as
     enclosed 4-connected background components (scipy.ndimage.label); every border's polygon area obeys Pick's theorem with the
     lattice points the walk visits -- outer border of a hole-free component: pixels - steps / 2 - 1 -- and the truncated centroid of
-    a disc lies within a pixel of its pixel centroid."""
+    a disc lies within a pixel of its pixel centroid.  A hole border runs through the foreground pixels round the hole: where it
+    visits none twice and the hole encloses no foreground, its area is hole pixels + steps / 2 - 1."""
     import scipy.ndimage as ndi
     from gpu_util import unpack_mask
     torch = torch_cuda
     W, H = 1920, 1080
     rng = np.random.default_rng(77)
     frames = dark_frames(rng, 2, H, W, n_discs=24, salt=0.001)
+    frames = np.concatenate([frames, ring_frame(rng, H, W)[None]])  # discs have no holes: a third frame of rings
     ctx, K, ident = make_ctx(W, H)
     ctx.set_blob_params(min_area=50.0, min_circ=0.3)
     mask_dev = ctx.filter_mask(torch.from_numpy(frames).cuda())
     masks, _ = unpack_mask(mask_dev, W)
     xy, cnt, recs = ctx.contours_from_mask(mask_dev, max_blobs=128, debug_cap=384)
     eight = np.ones((3, 3), int)
-    checked = 0
-    for i in range(2):
+    checked = checked_holes = 0
+    for i in range(3):
         m = masks[i]
         lab, n_fg = ndi.label(m, structure=eight)
         bg, n_bg = ndi.label(~np.pad(m, 1))  # 4-connected background, the frame's margin joins everything outside
@@ -126,7 +142,25 @@ def test_borders_against_scipy_labels_and_picks_theorem(torch_cuda):
                     assert abs(r["cx"] + 0.5 - cents[k - 1][1]) <= 1.0 and abs(r["cy"] + 0.5 - cents[k - 1][0]) <= 1.0
             else:  # a pixel of a one-pixel-wide part is visited twice: the polygon's lattice points are fewer than the steps
                 assert r["area"] > sizes[k - 1] - r["steps"] / 2 - 1
-    assert checked >= 30
+        hole_sizes = ndi.sum(np.ones_like(bg), bg, index=np.arange(1, n_bg + 1))
+        for r in holes:
+            assert not m[r["sy"], r["sx"] + 1] and m[r["sy"], r["sx"]]  # the start: the foreground pixel left of the hole's first pixel
+            j = bg[r["sy"] + 1, r["sx"] + 2]                             # (bg is labelled on the mask padded by one pixel)
+            assert j > 0 and j != bg[0, 0] and r["a00"] > 0 and r["steps"] >= 4
+            region = bg == j
+            ys, xs = np.nonzero(region)
+            assert (ys[0] - 1, xs[0] - 2) == (r["sy"], r["sx"])          # ... and that pixel is the region's raster-first one
+            pick = hole_sizes[j - 1] + r["steps"] / 2 - 1
+            if ndi.binary_fill_holes(region, structure=eight).sum() != hole_sizes[j - 1]:
+                assert r["area"] > pick  # foreground inside the hole: the polygon encloses it too
+            elif r["area"] == pick:
+                checked_holes += 1
+            else:  # a pixel visited twice: fewer lattice points on the polygon than steps
+                assert r["area"] < pick
+        if i == 1:
+            assert checked >= 30  # on the two frames of discs
+    print("Pick: outer borders", checked, "hole borders", checked_holes)
+    assert checked_holes >= 10
 
 
 @pytest.mark.parametrize("W,H", [(64, 48), (250, 130), (251, 77), (500, 300), (960, 540)])
