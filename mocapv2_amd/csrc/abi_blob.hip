@@ -107,7 +107,7 @@ static void read_probe(mocap_ctx* c, int thr_mul)
 }
 
 // dark-tile early-out: largest doubled excess sum 2E (E = sum of max(0, p - base)) per 16x16 block that still proves an
-// all-zero mask:   2E * Wmax < 1024 * taps_min * (2 * thr_mul - 2 * base - 1)     (derivation: blob_filter.hip)
+// all-zero mask:   2E * Wmax < 1024 * taps_min * (2 * thr_mul - 2 * base - 1)     (derivation: blob_scan.hip)
 struct ScanBounds {
     int thr_mul;
     int fixed_base;      // >= 0: the pinned base (excess_base switch)

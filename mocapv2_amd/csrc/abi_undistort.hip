@@ -40,7 +40,7 @@ int mocap_set_undistort(mocap_ctx_t c, int slot, const double K[9], const double
     std::vector<int> reach32((size_t)ncx_ * ncy_ * 4);  // per source cell: x0, x1, y0, y1 of the output pixels that read it
     for (size_t i = 0; i < reach32.size(); i += 2) { reach32[i] = 0x7fffffff; reach32[i + 1] = -0x7fffffff - 1; }
     if (c->slot_state[slot] == 2) {
-        // statistics for the dark-tile early-out (see blob_filter.hip): total weight per source pixel, tap extents
+        // statistics for the dark-tile early-out (see blob_scan.hip): total weight per source pixel, tap extents
         Buf<uint32_t> tmp; // (released at every return)
         const size_t edge_words = edge.size();
         TRY(tmp.reserve(per + 4 + edge_words + reach32.size()));

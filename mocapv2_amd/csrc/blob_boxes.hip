@@ -1,5 +1,5 @@
 // blob_boxes.hip -- the sparse half of the filter stage: undistort -> 5x5 in-bounds box sum -> threshold -> 5x5 majority,
-// run only where the streaming scan (bright_cells_kernel, blob_filter.hip) could not prove the mask to be zero.
+// run only where the streaming scan (bright_cells_kernel, blob_scan.hip) could not prove the mask to be zero.
 //
 // Replaces, for the boxes of one batch of camera images,
 //   cv.undistort (reference lib/ImageOperations.py:38) -> fast_cuda_blur (lib/CudaOperations.py:5-41)
@@ -8,7 +8,7 @@
 // Two kernels per batch, behind the scan:
 //   settle_tiles_kernel  one thread per (tile, image): turns the box the scan left on the tile (reachable mask rows and
 //                        columns) into work items of a bounded size in ONE global list -- or, a wide box, into an entry of the
-//                        wide-tile list that the sliding row pipeline of blob_filter.hip works through --, clears what the
+//                        wide-tile list that the sliding row pipeline of blob_rows.hip works through --, clears what the
 //                        previous batch left in the mask where this batch will not write, empties the next batch's boxes;
 //   box_filter_kernel    a fixed grid of single-wave workgroups consumes the list.  One wave owns one item and keeps
 //                        everything in LDS: the source pixels its undistortion reads (staged with coalesced row loads,
@@ -24,28 +24,15 @@
 #include <type_traits>
 #include "kernels.h"
 #include "bayer.h"
+#include "filter_dev.h"
 
 namespace mocap {
 
 namespace {
 
-__device__ __forceinline__ uint32_t from_prev(uint32_t v)
-{ // lane L receives lane L-1's value, lane 0 receives 0
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138 /*wave_shr:1*/, 0xf, 0xf, true);
-}
-__device__ __forceinline__ uint32_t from_next(uint32_t v)
-{ // lane L receives lane L+1's value, lane 63 receives 0
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x130 /*wave_shl:1*/, 0xf, 0xf, true);
-}
-__device__ __forceinline__ uint32_t dot4(uint32_t a, uint32_t sel, uint32_t acc) { return __builtin_amdgcn_udot4(a, sel, acc, false); }
 __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
 __device__ __forceinline__ int imin(int a, int b) { return a < b ? a : b; }
 __device__ __forceinline__ int imax(int a, int b) { return a > b ? a : b; }
-__device__ __forceinline__ int taps5(int v, int n)
-{ // number of in-image taps of a 5-wide window centred on v
-    int lo = v - 2 < 0 ? 0 : v - 2, hi = v + 2 > n - 1 ? n - 1 : v + 2;
-    return hi - lo + 1;
-}
 // floor(n / d) for 0 <= n < 4096, 1 <= d <= 4096 (float reciprocal, +0.5 keeps every quotient away from an integer)
 __device__ __forceinline__ int small_div(int n, float rcp_d) { return (int)(((float)n + 0.5f) * rcp_d); }
 
@@ -336,7 +323,7 @@ __global__ __launch_bounds__(256) void settle_tiles_kernel(BoxArgs a)
 //   threshold rows  [ty0, ty1] = [oy0 - 2, oy1 + 2] clipped to the image (the median replicates the border rows)
 //   patch           columns [px0, px0 + 4 Q) with px0 = ox0 - 4, Q = 2 * bytes + 2 quads; rows [hy0, hy1] = [ty0 - 2, ty1 + 2]
 //   exact region    the patch pixels inside the scan's box and the image; every other patch pixel counts as 0, which is
-//                   exact for the mask (blob_filter.hip, "dark-tile early-out")
+//                   exact for the mask (blob_scan.hip, "dark-tile early-out")
 // Lane -> (rsub, q): q = lane % Q the quad, rsub = lane / Q the row of the trip; trip k handles rows k * rpw + rsub.
 // Global memory latency is taken out of the item loop: the next item's header and the box of source pixels it will read
 // are fetched while the current item is filtered, all staging loads of an item are in flight together, and the table
@@ -428,14 +415,7 @@ __global__ __attribute__((amdgpu_waves_per_eu(MOCAP_BOX_WAVES, MOCAP_BOX_WAVES))
     uint64_t* const a_timing = a.timing;
     const BayerK bk{a.bayer.ry, a.bayer.rx, a.bayer.cb, a.bayer.cg, a.bayer.cr, a.bayer.shift};
     if (a.prio) __builtin_amdgcn_s_setprio(2); // A/B switch: these waves compute, the scan's waves of the next batch wait on HBM
-    // lut[w]: byte k = number of set bits among bits k..k+4 of the 8-bit window w
-#pragma unroll
-    for (int e = 0; e < 4; e++) {
-        uint32_t i = (uint32_t)(lane + 64 * e), v = 0;
-#pragma unroll
-        for (int k = 0; k < 4; k++) v |= (uint32_t)__popc((i >> k) & 0x1fu) << (8 * k);
-        lut[i] = v;
-    }
+    fill_window_counts(lut, lane);
     uint32_t n_items = *a_n_items;
     n_items = n_items < a_cap_items ? n_items : a_cap_items;
     // The list is cut into 8 runs of consecutive items, one per XCD (blocks b and b + 8 share an XCD; consecutive items share
@@ -522,7 +502,7 @@ __global__ __attribute__((amdgpu_waves_per_eu(MOCAP_BOX_WAVES, MOCAP_BOX_WAVES))
         // ---- pass A: undistorted patch -> horizontal 5-sums of every patch row, in LDS -----------------------------------
         // hsum of one patch row's quad B (4 bytes): packed 16-bit sums of the 5 columns around each pixel
         auto store_h = [&](uint32_t B, int r) __attribute__((always_inline)) {
-            const uint32_t A = from_prev(B), C = from_next(B);
+            const uint32_t A = lane_from_prev(B), C = lane_from_next(B);
             const uint32_t sB = dot4(B, 0x01010101u, 0u);
             const uint32_t h0_ = dot4(A, 0x01010000u, dot4(B, 0x00010101u, 0u));
             const uint32_t h1_ = dot4(A, 0x01000000u, sB);
@@ -809,7 +789,7 @@ __global__ __attribute__((amdgpu_waves_per_eu(MOCAP_BOX_WAVES, MOCAP_BOX_WAVES))
                 if (EDGE) {
                     // medianBlur replicates the border: columns outside the image take the edge column's bit
                     if (left_edge) { // quad 0 = columns -4..-1, quad 1 starts at column 0
-                        const uint32_t e = from_next(nib) & 1u;
+                        const uint32_t e = lane_from_next(nib) & 1u;
                         if (q == 0) nib = e ? 0xfu : 0u;
                     }
                     if (right_edge) {
@@ -819,7 +799,7 @@ __global__ __attribute__((amdgpu_waves_per_eu(MOCAP_BOX_WAVES, MOCAP_BOX_WAVES))
                         else if (q == qe) nib = (nib & keep) | (e ? (0xfu & ~keep) : 0u);
                     }
                 }
-                const uint32_t nl = from_prev(nib), nr = from_next(nib);
+                const uint32_t nl = lane_from_prev(nib), nr = lane_from_next(nib);
                 const uint32_t win = (nl >> 2) | (nib << 2) | ((nr & 3u) << 6);
                 const uint32_t c = lut[win & 0xffu];
                 const int at = (lane_on && y <= ty1) ? __mul24(y - ty0, Q) + q : BOX_HCAP + lane;
@@ -860,7 +840,7 @@ __global__ __attribute__((amdgpu_waves_per_eu(MOCAP_BOX_WAVES, MOCAP_BOX_WAVES))
                 const uint32_t mm = ((Cv + 0x73737373u) >> 7) & 0x01010101u;
                 const uint32_t t1 = mm | (mm >> 7);
                 const uint32_t mn = (t1 | (t1 >> 14)) & colmask & 0xfu;
-                const uint32_t odd = from_next(mn);
+                const uint32_t odd = lane_from_next(mn);
                 const uint32_t byte = mn | ((odd & 0xfu) << 4);
                 const bool st = stores && y <= oy1;
                 if (st) mrow[mask_byte_index(y, out_byte, a_words_per_row)] = (uint8_t)byte;

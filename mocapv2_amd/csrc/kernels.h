@@ -10,7 +10,7 @@ namespace mocap {
 // pixels).  Every consumer works on 2-D neighbourhoods some 50-64 pixels across (contour windows, blob boxes, cleared regions):
 // a 64 x 64 window is at most 3 x 3 lines, a lane-per-row load of 64 rows touches 2-3 lines.  An image takes
 // mask_image_words(H, wpr) words, H padded up to a multiple of 32; the padding rows are zero from allocation and never written.
-// (The C-ABI's caller-owned masks stay row-major: abi.hip converts at the boundary.)
+// (The C-ABI's caller-owned masks stay row-major: abi_blob.hip converts at the boundary.)
 __host__ __device__ __forceinline__ uint32_t mask_word_index(int y, int k, int wpr)
 {
     return ((uint32_t)(y >> 5) * (uint32_t)wpr + (uint32_t)k) * 32u + (uint32_t)(y & 31);
@@ -72,6 +72,8 @@ struct FilterArgs {
 };
 void launch_rowbox(const uint32_t* map4, ushort4* rowbox, int H, int W, int n_strips, hipStream_t s);
 int rows_stage_dwords();
+// (blob_rows_staged.hip; launch_filter_mask / launch_filter_tiles go through it when a.staged is set)
+void launch_filter_rows_staged(const FilterArgs& a, bool list, int blocks, hipStream_t s);
 
 // Bayer -> gray (bayer_gray.hip): red sites at row parity ry / column parity rx, luma coefficients cb, cg, cr >> shift
 struct BayerArgs {

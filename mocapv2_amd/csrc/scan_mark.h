@@ -1,6 +1,6 @@
 // scan_mark.h -- device helpers shared by the kernels that look at every frame byte (bright_cells_kernel in
-// blob_filter.hip, bayer_gray_scan_kernel in bayer_gray.hip): the excess sum of a cell row and what a hot cell does.
-// The bound behind them is derived in blob_filter.hip ("dark-tile early-out").
+// blob_scan.hip, bayer_gray_scan_kernel in bayer_gray.hip): the excess sum of a cell row and what a hot cell does.
+// The bound behind them is derived in blob_scan.hip ("dark-tile early-out").
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -80,7 +80,7 @@ def remap_u8(img, iu, iv):
 
 
 def compact_disp(iu, iv):
-    """(dx4, dy4): the compact table's displacements, tap origin limited to [-2, W] x [-2, H] (blob_filter.hip)."""
+    """(dx4, dy4): the compact table's displacements, tap origin limited to [-2, W] x [-2, H] (blob_setup.hip)."""
     H, W = iu.shape
     sx, sy = int_parts(iu, iv)
     xx, yy = np.meshgrid(np.arange(W), np.arange(H))

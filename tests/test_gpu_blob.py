@@ -773,6 +773,30 @@ def test_blob_centroids_from_bayer_equals_the_two_steps(torch_cuda, monkeypatch,
             assert rec[:, 0].sum() >= (4 if W >= 640 else 0)
 
 
+def test_wide_tiles_remap_width_not_a_multiple_of_4(torch_cuda, monkeypatch):
+    """The list form of the row pipeline with the per-pixel gather (filter_mask_kernel<remap, list> without the pipelined
+    gather, which needs W % 4 == 0): a remapped lens on the sparse path, every marked tile routed to the wide-tile list, W = 250.
+    Two strips (the second one cut by the image's right edge) and two chunks per image.  The launch counts show that the sparse path
+    ran (scan, then settle_tiles_kernel, which with this threshold lists every marked tile); the context has no count of list entries."""
+    from gpu_util import unpack_mask
+    torch = torch_cuda
+    monkeypatch.setenv("MOCAP_WIDE_QUADS", "0,0")
+    W, H = 250, 130
+    rng = np.random.default_rng(1)
+    frames = dark_frames(rng, 2, H, W, n_discs=4, salt=0.001)
+    dist = np.array(MILD_DIST)
+    ctx, K, ident = make_ctx(W, H, dist=dist)
+    assert not ident
+    ctx.profile(True)
+    got, _ = unpack_mask(ctx.filter_mask(torch.from_numpy(frames).cuda()), W)
+    launches = ctx.profile_read()
+    assert launches["scan_launches"] > 0 and launches["settle_launches"] > 0 and launches["filter_launches"] > 0, launches
+    for i in range(2):
+        exp = oracle.image_filter(oracle.undistort(frames[i], K, dist), 0) != 0
+        assert exp.any() and (i == 1 or (exp[:, 240:].any() and exp[0].any() and exp[-1].any()))  # frame 0 touches three image edges
+        assert np.array_equal(got[i], exp), i
+
+
 @pytest.mark.parametrize("env", [
     {"MOCAP_WIDE_QUADS": "0,0"},                              # every marked tile through the row pipeline's list form
     {"MOCAP_WIDE_QUADS": "1000,1000"},                        # every marked tile through the box kernel
@@ -910,13 +934,13 @@ def test_crowded_scenes_switch_the_marking_to_the_hot_map_and_back(torch_cuda):
                 assert np.array_equal(got[i], m != 0), (b, i)
 
 
-@pytest.mark.parametrize("W,H", [(64, 48), (250, 130), (251, 77), (500, 300), (961, 541), (1920, 1080)])
+@pytest.mark.parametrize("W,H", [(64, 48), (64, 44), (250, 130), (251, 77), (500, 300), (961, 541), (1920, 1080)])
 @pytest.mark.parametrize("scale", [0.0, 1.0])
 def test_hot_map_marking_at_any_size(torch_cuda, W, H, scale):
     """The hot map (two bits per 8x8 source cell, written by whole waves of the scan, read 256 words per wave by mark_tiles_kernel) on
     frame sizes that end in part-cells, part-words and part-waves, in both forms of the scan (16-byte loads where the width allows,
-    8-byte loads otherwise), with and without a lens table: masks and centroids equal the oracle's, and equal what the scan's own
-    marking gives on the same context right afterwards."""
+    8-byte loads otherwise; 64 x 44: 16-byte loads with a last cell row of 4 image rows), with and without a lens table: masks and
+    centroids equal the oracle's, and equal what the scan's own marking gives on the same context right afterwards."""
     from gpu_util import unpack_mask
     torch = torch_cuda
     from mocapv2_amd.engine import MocapContext
