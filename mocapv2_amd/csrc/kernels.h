@@ -181,7 +181,7 @@ struct ContourArgs {
     uint64_t* timing;      // optional [n_images][8] phase clock (debugging aid), else null
     void* work;            // [n_images] per-image workspace of contour_work_bytes() each
     int prio;              // wave priority (s_setprio 0..3): the walks are serial chains, cheap to favour and costly to delay
-    uint64_t* walk_list;   // split form: [n_images * contour_walk_bytes() / 8] candidate walks of the batch (blob_contours.hip: walk_entry), or
+    uint64_t* walk_list;   // split form: [n_images * contour_walk_bytes() / 8] candidate walks of the batch (contours_dev.h: walk_entry), or
                            //   null = one kernel per image
     uint64_t* link_list;   // split form: [n_images * contour_link_bytes() / 8] link walks of the batch (second follow pass)
     uint32_t* walk_count;  // split form: [8] entries in walk_list, its head, entries in link_list, its head, entries in wait_list
@@ -246,6 +246,8 @@ struct StatArgs { const uint32_t* map; const uint32_t* mapw; uint32_t* acc; uint
 void launch_remap_stats(const StatArgs& a, hipStream_t s);
 void launch_undistort_map(const MapArgs& m, hipStream_t s);
 void launch_contours(const ContourArgs& a, hipStream_t s);
+// (blob_contour_follow.hip; launch_contours goes through it for the candidate walks and for the link walks)
+void launch_contour_follow(const ContourArgs& a, int grid, hipStream_t s);
 size_t contour_work_bytes();
 size_t contour_walk_bytes(); // walk list bytes per image (split form of the contour stage)
 size_t contour_link_bytes(); // link list bytes per image

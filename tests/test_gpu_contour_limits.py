@@ -1,4 +1,4 @@
-"""The contour stage's capacity limits at their edges (csrc/blob_contours.hip: MAXC 1024 start candidates, MAXR 384 borders,
+"""The contour stage's capacity limits at their edges (csrc/contours_dev.h: MAXC 1024 start candidates, MAXR 384 borders,
 MAXK 256 kept contours, MAXD 8 nesting levels, MAXA 64 deferred links): at the limit the result is the reference's, one
 past it the image carries that limit's MOCAP_BLOB_E_* code and nothing else of the batch changes.  The masks are the
 constructions of tests/contour_cases.py (tests/test_contour_cases_host.py pins them against the oracle without a GPU);
@@ -60,7 +60,7 @@ def built(name, H=None, W=None, gates=None):
     return mask, (case if gates is None else None), table
 
 
-def run(masks, gates, form, max_blobs=256, xy_rows=None):
+def run(masks, gates, form, max_blobs=256, xy_rows=None, tuning=None):
     """the batch through mocap_contours_from_mask -> xy [n, rows, 2] (pre-filled with SENTINEL), count [n], records"""
     import torch
     from gpu_util import pack_mask
@@ -69,7 +69,7 @@ def run(masks, gates, form, max_blobs=256, xy_rows=None):
     H, W = masks[0].shape
     ctx = MocapContext(W, H)
     ctx.set_blob_params(min_area=gates[0], min_circ=gates[1])
-    for k, v in FORMS[form].items():
+    for k, v in {**FORMS[form], **(tuning or {})}.items():
         ctx.set_tuning(k, v)
     xy = torch.full((len(masks), xy_rows or max_blobs, 2), SENTINEL, dtype=torch.int32, device="cuda")
     xy, cnt, recs = ctx.contours_from_mask(pack_mask(np.stack(masks)), max_blobs=max_blobs, debug_cap=384, xy=xy)
@@ -164,7 +164,7 @@ def disc_frame(H, W, seed, n=6):
 
 
 def listed_cells(mask, rows=68):
-    """How many cells the candidates kernel lists for this mask (blob_contours.hip, phase A), restated from the tiling: strips of
+    """How many cells the candidates kernel lists for this mask (blob_contour_image.hip, phase A), restated from the tiling: strips of
     240 columns, chunks of `rows` rows (68; frames lower than 128 rows: a quarter of the height, at least 8) cut into groups of 8
     rows; a group is listed when it, the group above it (the last group of the chunk above for a chunk's first) or the same
     group of the strip left of it holds a set pixel.  (The filter's occupancy words may mark more groups, never fewer.)"""
@@ -223,3 +223,114 @@ def test_a_frame_with_every_cell_occupied_is_not_refused(W, H, over):
     assert cnt == [len(r) for r in ref] and got == ref
     got, cnt = centroids(ctx, [bars])
     assert cnt == [0]
+
+
+# ---- the per-image kernels as a fixed grid looping over the images (contour_blocks_per_cu > 0, more images than workgroups) ----
+LOOP_W, LOOP_H, LOOP_GATES = 96, 64, (1.0, 0.05)
+
+
+def _dots():
+    """an isolated pixel on every second column of every second row: 48 x 32 = 1536 start candidates, one over MAXC and a half"""
+    m = np.zeros((LOOP_H, LOOP_W), np.uint8)
+    m[1::2, 1::2] = 255
+    return m
+
+
+LOOP_MASKS = [lambda: rings(2, 3)[0], lambda: ring_column(13)[0],   # 13 links that only a walk settles: the wait list, the second passes
+              lambda: rings(4, 7)[0],                               # a kept border at depth 9: MOCAP_BLOB_E_DEPTH, from the tree kernel
+              lambda: squares(5, 3, H=LOOP_H, W=LOOP_W)[0], lambda: rings(3, 3)[0],
+              _dots,                                                # MOCAP_BLOB_E_CANDIDATES, from the candidates kernel
+              lambda: np.rot90(ring_column(9)[0]), lambda: rings(3, 0)[0][::-1, ::-1]]
+LOOP_CODES = {2: -5, 5: -2}
+
+
+@functools.lru_cache(maxsize=None)
+def loop_masks():
+    """the eight masks, embedded top-left in a 96 x 64 frame, and the oracle's table of each for LOOP_GATES"""
+    out = []
+    for make in LOOP_MASKS:
+        big = np.zeros((LOOP_H, LOOP_W), np.uint8)
+        m = np.asarray(make())
+        big[:m.shape[0], :m.shape[1]] = m
+        big.setflags(write=False)
+        out.append((big, oracle.find_contours(big, min_area=LOOP_GATES[0], min_circ=LOOP_GATES[1])))
+    return out
+
+
+def looping_batch():
+    """(number of workgroups, number of images, which of `k` distinct inputs image i takes): 37 more images than the device has
+    CUs, so that with one workgroup per CU the first 37 workgroups take two images and the rest one; the second round is shifted
+    by one, so that the two images of a workgroup are never the same input"""
+    import torch
+    assert torch.cuda.is_available(), "these tests need the MI355X"
+    grid = torch.cuda.get_device_properties(0).multi_processor_count
+    return grid, grid + 37, lambda i, k: (i + i // grid) % k
+
+
+@pytest.mark.parametrize("defer", [0, 2], ids=["links_in_place", "links_deferred"])
+def test_looping_grid_over_a_callers_masks(defer):
+    """contour_blocks_per_cu = 1 and more images than CUs: the candidates and the tree kernel run as a fixed grid whose workgroups
+    take a second image with the first one's state still in LDS.  Every image equals the oracle's table of its mask (borders,
+    measurements, parents, order, centroids); the two over-limit masks carry their codes -- one raised by the candidates kernel,
+    one by the tree kernel -- as the first and as the second image of a workgroup, and the image that shares the workgroup with
+    them is as good as any other."""
+    grid, n, pick = looping_batch()
+    cases = loop_masks()
+    which = [pick(i, len(cases)) for i in range(n)]
+    assert all(which[b] != which[b + grid] for b in range(n - grid))
+    for k, code in LOOP_CODES.items():  # an over-limit image first and second in a workgroup, a good one beside it
+        assert any(which[b] == k and which[b + grid] not in LOOP_CODES for b in range(n - grid))
+        assert any(which[b + grid] == k and which[b] not in LOOP_CODES for b in range(n - grid))
+        table = cases[k][1]
+        assert (local_candidates(cases[k][0]) > 1024) if code == -2 else any(c["kept"] for c in table[8:]) and len(table) == 9
+    nested = [sum(c["parent_order"] >= 0 for c in t) for _, t in cases]
+    assert nested[1] >= 14 and nested[0] >= 4  # rings within rings: links that need a walk
+    xy, cnt, recs = run([cases[k][0] for k in which], LOOP_GATES, "links_in_place", max_blobs=64,
+                        tuning={"contour_blocks_per_cu": 1, "contour_defer": defer})
+    print("images", n, "workgroups", grid, "counts of the first 16", cnt[:16].tolist())
+    for i, k in enumerate(which):
+        mask, table = cases[k]
+        if k in LOOP_CODES:
+            assert cnt[i] == LOOP_CODES[k] and recs[i] == [] and (xy[i] == SENTINEL).all(), (i, k, cnt[i])
+            continue
+        assert cnt[i] >= 0, (i, k, cnt[i])
+        check_image(mask, None, table, LOOP_GATES, xy[i], cnt[i], recs[i], 64)
+
+
+def loop_frame(seed):
+    """64 x 44: dark noise, one disc large enough to be kept (or, seed 3, none), a small one, and (seed 4) a hole in the large one"""
+    rng = np.random.default_rng(900 + seed)
+    W, H = 64, 44
+    img = rng.integers(0, 50, (H, W), dtype=np.uint8)
+    yy, xx = np.mgrid[0:H, 0:W]
+    cx, cy, r = 20 + 6 * seed, 20 + (seed % 3), 15 + seed % 2
+    if seed != 3:
+        img[(xx - cx) ** 2 + (yy - cy) ** 2 <= r * r] = 255
+    if seed == 4:
+        img[(xx - cx) ** 2 + (yy - cy) ** 2 <= 36] = 0
+    sx = 56 if cx < 32 else 6
+    img[(xx - sx) ** 2 + (yy - 8 - 5 * seed) ** 2 <= 16] = 255
+    return img
+
+
+@pytest.mark.parametrize("defer", [0, 2], ids=["links_in_place", "links_deferred"])
+def test_looping_grid_over_filtered_frames(defer):
+    """The same grid on the context's own mask, where the candidates kernel lists the occupied cells (in the LDS its next image
+    reuses): five distinct 64 x 44 frames, cycled, against oracle.find_dot."""
+    from mocapv2_amd.engine import MocapContext
+    grid, n, pick = looping_batch()
+    W, H = 64, 44
+    K = np.array([[0.7 * W, 0, W / 2.0], [0, 0.7 * W, H / 2.0], [0, 0, 1]])
+    distinct = [loop_frame(s) for s in range(5)]
+    ref = [oracle.find_dot(f, K, np.zeros(5)) for f in distinct]
+    assert sum(len(r) for r in ref) >= 3 and len({str(r) for r in ref}) >= 4
+    which = [pick(i, 5) for i in range(n)]
+    assert all(which[b] != which[b + grid] for b in range(n - grid))
+    ctx = MocapContext(W, H, 1)
+    assert ctx.set_undistort(0, K, np.zeros(5))
+    ctx.set_tuning("contour_blocks_per_cu", 1)
+    ctx.set_tuning("contour_defer", defer)
+    got, cnt = centroids(ctx, [distinct[k] for k in which])
+    print("images", n, "workgroups", grid, "reference", ref)
+    for i, k in enumerate(which):
+        assert cnt[i] == len(ref[k]) and got[i] == ref[k], (i, k, cnt[i])

@@ -1,4 +1,4 @@
-"""The contour kernels (csrc/blob_contours.hip: `follow`, its pair-of-lanes form in contour_follow_kernel, select_contour and
+"""The contour kernels (csrc/blob_contour_image.hip: `follow`; blob_contour_follow.hip: its pair-of-lanes form in contour_follow_kernel; contours_dev.h: select_contour and
 the tree passes) held to the oracle-free reference of tests/contour_poly_ref.py -- scipy.ndimage's labelling for which borders
 exist, where they start and how they nest; exact integer and rational arithmetic, float32 roots and mpmath for what is measured
 on them -- instead of to oracle/blob_oracle.c, which was written beside the kernels from the same reading of OpenCV
