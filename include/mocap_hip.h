@@ -43,6 +43,10 @@ enum {
     MOCAP_CORR_E_TRUNCATED = -3,  /* a camera holds more image points than the P that mocap_correspond was told to read */
     MOCAP_CORR_E_BLOB = -4,       /* a camera's point count is negative: its blob stage reported MOCAP_BLOB_E_* */
     MOCAP_CORR_E_OUTPUT = -5,     /* mocap_correspond_visible: more accepted markers in the time step than the Q output rows */
+    MOCAP_TRACK_E_FULL = -2,      /* mocap_track_markers, status[t]: no free slot for a new marker of the step (its rows hold -1) */
+    MOCAP_TRACK_E_IDS = -3,       /* the identity counter stands at INT32_MAX: no new marker gets an identity (the counter never wraps) */
+    MOCAP_TRACK_E_INPUT = -4,     /* a blind step: its count n[t] is negative (the correspondence's own failure code) */
+    MOCAP_TRACK_E_COUNT = -5,     /* a blind step: its count n[t] exceeds 256 or the Q rows of a step */
     MOCAP_FUND_E_SAMPLE = -2,     /* mocap_fundamental_ransac: a sample index outside its pair's point list */
     MOCAP_FUND_E_DEGENERATE = -3  /* no valid hypothesis (e.g. coincident points), a winner with fewer than 8 inliers, or
                                      inliers that do not span a model in the refit */
@@ -237,6 +241,48 @@ MOCAP_API int mocap_correspond_visible(mocap_ctx_t ctx, const void* pts_dev, lon
                                        int P, int distorted, double cutoff, double gate, int min_views, double max_err,
                                        int max_passes, int max_hyp, int Q, double* xyz_dev, double* err_dev, int32_t* idx_dev,
                                        uint32_t* views_dev, int32_t* n_dev, void* stream);
+
+/* Marker identities across time steps.  mocap_correspond and mocap_correspond_visible report every time step's markers in an
+ * order of that step alone; this call walks T time steps in order and gives every detection the identity of the track it
+ * continues.  The reference has no counterpart (its {"tracker1": object_points[0]} message assumes one marker): the contract is
+ * the definition of DESIGN.md section 2, restated by tests/track_ref.py -- FP64 throughout, every operation rounded on its own,
+ * so the device equals the restatement bit for bit.  New symbol, MOCAP_ABI_VERSION stays 7.
+ * Per step: every live slot predicts p = pos + vel; (slot, detection) is a candidate when |D - p|^2 < (gate * (1 + miss))^2;
+ * candidates are accepted in ascending (d2, slot, detection) when neither side is taken; a matched slot takes vel += beta * (D - p),
+ * pos = D, miss = 0, hits += 1; an unmatched one coasts (pos = p, miss += 1) and dies once miss > max_miss; then the unmatched
+ * detections, in ascending row, take the lowest free slots with identity next_id++ (vel = 0, hits = 1).
+ *   xyz_dev     float64 [T][Q][3]  detections (mocap_correspond_visible's xyz_dev as it is); rows at and beyond n_dev[t] take
+ *                                  no part in anything and may hold any bytes
+ *   n_dev       int32 [T]          detections of the step.  A negative count (MOCAP_CORR_E_*) or one above min(Q, 256) makes the
+ *                                  step BLIND: it has no detections, every track coasts, status_dev[t] says why
+ *   state_dev   MOCAP_TRACK_STATE_BYTES(max_tracks) bytes the caller owns: a mocap_track_header, then max_tracks mocap_track_slot.
+ *               All-zero bytes are the empty tracker.  The call reads it when it starts and writes it when it ends, so calls on
+ *               one state must be ordered (one stream, or events between streams); several trackers need nothing from the context
+ *   max_tracks  1..256 slots;  gate finite and > 0 (world units);  beta in [0, 1];  max_miss >= 0
+ *   id_dev, slot_dev, age_dev  int32 [T][Q] each: identity, slot and age (detections so far) of the track the row's detection
+ *               continues or starts; -1 in all three for a detection that found no free slot or identity, and in every row at
+ *               and beyond n_dev[t] (all rows of a blind step)
+ *   status_dev  int32 [T]  0 or MOCAP_TRACK_E_*: nothing is silent, and the other detections and steps are unaffected
+ * T = 0 is a no-op.  Bad arguments are MOCAP_E_INVALID and launch nothing.  Asynchronous on `stream`.  No atomics: the same call
+ * on the same state gives the same bits. */
+typedef struct mocap_track_header {
+    int32_t next_id;      /* the next identity to hand out */
+    int32_t reserved0;
+    int64_t steps;        /* time steps seen */
+    int64_t reserved[6];
+} mocap_track_header;     /* 64 bytes */
+typedef struct mocap_track_slot {
+    double pos[3], vel[3]; /* position; velocity per time step */
+    int32_t id;            /* identity */
+    int32_t miss;          /* consecutive steps without a detection */
+    int32_t hits;          /* detections so far */
+    int32_t alive;         /* the slot holds a track (a dead slot keeps the fields of its last track) */
+} mocap_track_slot;        /* 64 bytes */
+#define MOCAP_TRACK_STATE_BYTES(max_tracks) (64u * (1u + (unsigned)(max_tracks)))
+MOCAP_API int mocap_track_markers(mocap_ctx_t ctx, const double* xyz_dev /*[T][Q][3]*/, const int32_t* n_dev /*[T]*/,
+                                  int T, int Q, void* state_dev, int max_tracks, double gate, double beta, int max_miss,
+                                  int32_t* id_dev, int32_t* slot_dev, int32_t* age_dev /*[T][Q] each*/, int32_t* status_dev /*[T]*/,
+                                  void* stream);
 
 /* The scoring step of find_point_correspondance_and_object_points on its own (lib/Helpers.py:205-220), for one camera
  * pair: the epipolar line of every root point under Fs[f_index] (cv.computeCorrespondEpilines on the float32 point, :207;

@@ -486,6 +486,27 @@ void launch_intr_finish(const IntrArgs& a, hipStream_t s);
 
 enum { CORR_ERR_GROUPS = -2, CORR_ERR_TRUNCATED = -3, CORR_ERR_BLOB = -4, CORR_ERR_OUTPUT = -5 };
 enum { FUND_ERR_SAMPLE = -2, FUND_ERR_DEGENERATE = -3 };
+enum { TRACK_ERR_FULL = -2, TRACK_ERR_IDS = -3, TRACK_ERR_INPUT = -4, TRACK_ERR_COUNT = -5 };
+
+// marker identities across time steps (track.hip).  The caller's state buffer: a 64-byte header, then one
+// 64-byte record per slot (include/mocap_hip.h: mocap_track_header / mocap_track_slot; all-zero bytes = the empty tracker).
+constexpr int TRACK_MAX = 256; // slots of a tracker and detections of a time step at most
+struct TrackHeader { int32_t next_id, reserved0; int64_t steps; int64_t reserved[6]; };
+struct TrackSlot { double pos[3], vel[3]; int32_t id, miss, hits, alive; };
+static_assert(sizeof(TrackHeader) == 64 && sizeof(TrackSlot) == 64, "the state buffer's layout is part of the ABI");
+struct TrackArgs {
+    const double* xyz;         // [T][Q][3] detections; rows at and beyond n[t] take no part
+    const int32_t* n;          // [T] detections of the step; < 0 or > min(Q, 256): a blind step
+    int T, Q, M;
+    void* state;               // TrackHeader, then M TrackSlot
+    double gate, beta;
+    int max_miss;
+    int32_t* id;               // [T][Q] each: identity, slot, age of the detection of that row; -1 = none
+    int32_t* slot;
+    int32_t* age;
+    int32_t* status;           // [T] 0 or TRACK_ERR_*
+};
+void launch_track_markers(const TrackArgs& a, hipStream_t s);
 
 void launch_fundamental_ransac(const FundArgs& a, hipStream_t s);
 

@@ -338,6 +338,41 @@ class MocapContext:
                               rec_ints * stride_c, False, T, Cn, P, distorted, cutoff, gate, min_views, max_err, max_passes,
                               max_hyp, Q, out)
 
+    def track_state(self, max_tracks):
+        """The state buffer of one tracker for track_markers (MOCAP_TRACK_STATE_BYTES: a 64-byte header and one 64-byte record per
+        slot, include/mocap_hip.h), zeroed = the empty tracker.  The caller owns it; NumPy reads a copy of it with a structured dtype."""
+        if not 1 <= int(max_tracks) <= 256:
+            raise ValueError(f"max_tracks {max_tracks}: 1..256")
+        return torch.zeros(64 * (1 + int(max_tracks)), dtype=torch.uint8, device=self.device)
+
+    def track_markers(self, xyz, n, state, gate, beta=0.5, max_miss=5, out=None, steps=None):
+        """Marker identities across time steps (mocap_track_markers; the definition is DESIGN.md section 2).  xyz [T, Q, 3] float64
+        and n [T] int32 on the GPU (correspond_visible's xyz and n as they are: a negative count is a blind step), state from
+        track_state (updated in place; calls on one state must be ordered on the device), gate in world units.  steps: only the
+        first `steps` time steps are walked (a batch padded at its end must not age the tracks).  Returns a dict of device
+        tensors: id, slot, age [T, Q] int32 (-1 = the row holds no tracked detection) and status [T] int32 (0 or MOCAP_TRACK_E_*);
+        the rows of time steps at and beyond `steps` are not written (a fresh `out` holds -1 / 0 there)."""
+        assert xyz.is_cuda and xyz.is_contiguous() and xyz.dtype == torch.float64 and xyz.dim() == 3 and xyz.shape[2] == 3, xyz.shape
+        assert n.is_cuda and n.is_contiguous() and n.dtype == torch.int32
+        assert state.is_cuda and state.is_contiguous()
+        T, Q = int(xyz.shape[0]), int(xyz.shape[1])
+        assert n.numel() >= T, (n.shape, T)
+        steps = T if steps is None else int(steps)
+        if not 0 <= steps <= T:
+            raise ValueError(f"steps {steps} outside 0..{T}")
+        nbytes = state.numel() * state.element_size()
+        max_tracks = nbytes // 64 - 1
+        if nbytes % 64 or max_tracks < 1:
+            raise ValueError(f"a state of {nbytes} bytes is not one of track_state()")
+        if out is None:
+            out = {k: torch.full((T, Q), -1, dtype=torch.int32, device=self.device) for k in ("id", "slot", "age")}
+            out["status"] = torch.zeros((T,), dtype=torch.int32, device=self.device)
+        assert all(out[k].shape == (T, Q) and out[k].is_contiguous() for k in ("id", "slot", "age")) and out["status"].shape == (T,)
+        _abi.check(self.lib.mocap_track_markers(self._h, _ptr(xyz), _ptr(n), steps, Q, _ptr(state), max_tracks, float(gate), float(beta),
+                                                int(max_miss), _ptr(out["id"]), _ptr(out["slot"]), _ptr(out["age"]),
+                                                _ptr(out["status"]), _stream()))
+        return out
+
     def epipolar_scores(self, roots, cand, f_index=0, with_lines=False):
         """The scoring step of the correspondence search for one camera pair (reference lib/Helpers.py:205-220): roots [R, 2]
         camera-0 points, cand [N, 2] points of camera f_index + 1 (host arrays, integer or float) -> distances [R, N] float64

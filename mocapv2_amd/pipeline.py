@@ -186,7 +186,7 @@ class BatchTracker:
     def __init__(self, K, dist, R, t, F, width, height, steps_per_rank, world=1, rank=0, device=0, group=None,
                  max_points=32, max_groups=4096, depth=1, bayer_pattern=None, gray_shift=GRAY_SHIFT, collective="auto",
                  force_collective=False, visibility="all", min_views=2, gate=10.0, max_err=25.0, max_passes=3, cutoff=10.0,
-                 max_hyp=8192):
+                 max_hyp=8192, track=None):
         """visibility: which markers stage B reports --
              "all"   the reference's find_point_correspondance_and_object_points (mocap_correspond): a marker every camera sees,
                      searched from camera 0's points; the outputs are MocapContext.correspond's;
@@ -200,7 +200,22 @@ class BatchTracker:
                      an event); its unique id travels through torch.distributed once, at set-up (negotiate_rccl);
              "torch" torch.distributed (all_gather_into_tensor on nccl = RCCL, or gloo through the host);
              "auto"  "rccl" when the process group's backend is nccl, else "torch".
-           force_collective: run the exchange even with world == 1 (a one-rank all-gather; tests)."""
+           force_collective: run the exchange even with world == 1 (a one-rank all-gather; tests).
+           track: None, or {"gate": world units, "max_tracks": 64, "beta": 0.5, "max_miss": 5} -- marker identities across time
+             steps and batches (MocapContext.track_markers): the outputs gain id, slot, age [T, rows] and
+             status [T].  Their rows are the rows of xyz with visibility="any"; with "all" they are the positions in `order` (row
+             k = the k-th reported root: xyz is gathered through `order` on the device first).  One state per tracker, shared
+             by its batches in flight, whose track calls are chained by events.  Needs world == 1: time is sharded across
+             ranks, and a hand-off of the state between ranks is not implemented."""
+        self.track = None
+        if track is not None:
+            if world > 1:
+                raise ValueError("track needs world == 1: the time steps are sharded across ranks and the tracks are not handed from rank to rank")
+            unknown = set(track) - {"gate", "max_tracks", "beta", "max_miss"}
+            if unknown or "gate" not in track:
+                raise ValueError(f"track: a dict with gate (required), max_tracks, beta, max_miss; got {sorted(track)}")
+            self.track = {"gate": float(track["gate"]), "beta": float(track.get("beta", 0.5)), "max_miss": int(track.get("max_miss", 5))}
+            self.max_tracks = int(track.get("max_tracks", 64))
         self.n_cam = len(K)
         self.T = int(steps_per_rank)
         self.world, self.rank, self.group = world, rank, group
@@ -242,6 +257,8 @@ class BatchTracker:
             self.lanes.append(_Lane(ctx, records, stream))
         self._k = 0
         self._cur = self.lanes[0]
+        self.track_state = self.lanes[0].ctx.track_state(self.max_tracks) if self.track else None
+        self._track_done = None  # event behind the most recent track call (depth > 1): the next batch's call waits for it
         self.force_collective = bool(force_collective)
         self.collective = None
         if world > 1 or self.force_collective:
@@ -343,20 +360,39 @@ class BatchTracker:
                                               out=self.out)
         return self.out
 
-    def step(self, frames):
-        """One pass of the hot path over this rank's block: extract -> (all-gather) -> triangulate.  Returns the
+    def track_ids(self, out, steps=None):
+        """Identities for the markers of a batch, in the order the batches are submitted (the tracker was built with `track`):
+        adds id, slot, age and status to `out`.  Batches in flight on several streams share the one state, so every call waits
+        for the event recorded behind the call before it."""
+        lane = self._cur
+        xyz = out["xyz"]
+        if self.visibility == "all":  # the reported roots, in their order (rows beyond n: whatever `order` holds, clamped)
+            pick = out["order"].clamp(0, xyz.shape[1] - 1).to(torch.int64)[:, :, None].expand(-1, -1, 3)
+            xyz = torch.gather(xyz, 1, pick)
+        if lane.stream is not None and self._track_done is not None:
+            torch.cuda.current_stream().wait_event(self._track_done)
+        ids = {k: out[k] for k in ("id", "slot", "age", "status")} if "id" in out else None
+        out.update(lane.ctx.track_markers(xyz, out["n"], self.track_state, out=ids, steps=steps, **self.track))
+        if lane.stream is not None:
+            self._track_done = torch.cuda.Event()
+            self._track_done.record(torch.cuda.current_stream())
+        return out
+
+    def step(self, frames, steps=None):
+        """One pass of the hot path over this rank's block: extract -> (all-gather) -> triangulate (-> identities).  Returns the
         correspondence outputs (dict of device tensors, see MocapContext.correspond) for this rank's time steps.
-        With depth > 1 the work is queued on the batch's own stream and the call returns at once."""
+        With depth > 1 the work is queued on the batch's own stream and the call returns at once.
+        steps: with `track`, the number of valid time steps of the batch (the rest is padding and does not age the tracks)."""
         lane = self.lanes[self._k % len(self.lanes)]
         self._k += 1
         self._cur = lane
         if lane.stream is None:
-            return self._run(self._resident(lane, frames))
+            return self._run(self._resident(lane, frames), steps)
         lane.stream.wait_stream(torch.cuda.current_stream())  # the frames were produced on the caller's stream
         if frames.is_cuda:
             frames.record_stream(lane.stream)  # the caller may drop them right after this call: keep the memory until the lane is done
         with torch.cuda.stream(lane.stream):
-            return self._run(self._resident(lane, frames))
+            return self._run(self._resident(lane, frames), steps)
 
     def _resident(self, lane, frames):
         """Frames in (pinned) host memory are uploaded into the batch's own staging buffer on its stream, so the copy
@@ -368,13 +404,14 @@ class BatchTracker:
         lane.staging.copy_(frames, non_blocking=True)
         return lane.staging
 
-    def _run(self, frames):
+    def _run(self, frames, steps=None):
         records = self.extract(frames)
         if self.collective == "rccl":    # [C * T_total, REC] camera-major when world > 1
             gathered = self._cur.ctx.allgather_centroids(records, self._cur.gathered)
         else:
             gathered = allgather_records(records, self.world, self.group, force=self.force_collective)
-        return self.triangulate(gathered)
+        out = self.triangulate(gathered)
+        return self.track_ids(out, steps) if self.track else out
 
     def synchronize(self):
         """Wait for every batch submitted so far."""

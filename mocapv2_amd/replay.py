@@ -38,13 +38,16 @@ class ReplayTracker:
 
     def __init__(self, K, dist, R, t, F, width, height, batch=64, obj_count=OBJ_COUNT, device=0, max_points=32,
                  max_groups=4096, bayer_pattern=None, gray_shift=GRAY_SHIFT, depth=1, visibility="all", min_views=2, gate=10.0,
-                 max_err=25.0, max_passes=3, cutoff=10.0, max_hyp=8192):
+                 max_err=25.0, max_passes=3, cutoff=10.0, max_hyp=8192, track=None):
         """visibility="any" (BatchTracker's): a time step yields the markers at least min_views cameras see, found from any
         camera pair, in acceptance order (more views first, then smaller error) -- the first obj_count + 1 of them as
         object_points, image_points [markers, C, 2] float64 with NaN where a camera does not see the marker; F may be None.
         depth > 1: that many batches are in flight on HIP streams of their own (BatchTracker's software pipelining): while
         the results of one batch are read back and turned into messages, the next ones are already on the GPU.  The time steps
-        come out in order either way."""
+        come out in order either way.
+        track (BatchTracker's): marker identities across time steps and batches; the dicts of run_batches and run gain `ids` and
+        `ages`, row for row beside object_points (-1 = the row's marker got no track).  The black frames that pad the last batch
+        are not walked: they do not age the tracks.  The messages stay as they are."""
         self.n_cam = len(K)
         self.batch = int(batch)
         self.obj_count = obj_count
@@ -53,8 +56,9 @@ class ReplayTracker:
         self.tracker = BatchTracker(K, dist, R, t, F, width, height, self.batch, device=device, max_points=max_points,
                                     max_groups=max_groups, bayer_pattern=bayer_pattern, gray_shift=gray_shift, depth=self.depth,
                                     visibility=visibility, min_views=min_views, gate=gate, max_err=max_err, max_passes=max_passes,
-                                    cutoff=cutoff, max_hyp=max_hyp)
+                                    cutoff=cutoff, max_hyp=max_hyp, track=track)
         self.visibility = visibility
+        self.tracked = track is not None
         self.point = [0, 0, 0, 0, 0, 0, 0, 0]  # RealtimeTracking_FLIR.py:171 (eight zeros until the first detection)
         # raw sensor frames: the camera loop's cvtColor(BAYER_GR2BGR) + cvtColor(BGR2GRAY) (:103-104) run on the GPU first, with
         # no gray frame in memory (BatchTracker.extract); bayer_pattern 0..3 = BG, GB, RG, GR (the reference: 3), None = the
@@ -87,7 +91,8 @@ class ReplayTracker:
                 if nb < self.batch:  # pad the last batch with black frames (they produce no points)
                     pad = torch.zeros((self.batch - nb,) + tuple(chunk.shape[1:]), dtype=torch.uint8, device=dev)
                     chunk = torch.cat([chunk, pad], dim=0)
-                out = self.tracker.step(chunk.reshape(self.batch * self.n_cam, self.height, self.width).contiguous())
+                out = self.tracker.step(chunk.reshape(self.batch * self.n_cam, self.height, self.width).contiguous(),
+                                        steps=nb if self.tracked else None)
                 pending.append((t_base + p0, nb, out))
                 if len(pending) >= self.depth:  # the oldest batch's lane is the next one to be reused: read it back first
                     yield pending.pop(0)
@@ -114,7 +119,17 @@ class ReplayTracker:
         msgs = batch_messages(obj[:, 0] if width else np.zeros((nb, 3)), has, tracker_message(self.point))
         if has.any():
             self.point = [0, 0, 0, 0] + list(obj[np.flatnonzero(has)[-1], 0])  # :184-185
-        return {"first_step": b0, "n_steps": nb, "n_roots": n, "kept": kept, "object_points": obj, "image_points": grp, "messages": msgs}
+        res = {"first_step": b0, "n_steps": nb, "n_roots": n, "kept": kept, "object_points": obj, "image_points": grp, "messages": msgs}
+        return self._with_ids(res, out, n, width)
+
+    def _with_ids(self, res, out, n, width):
+        """ids / ages [n_steps, width] beside object_points (the tracker's rows are object_points' rows in both visibilities)"""
+        if self.tracked:
+            nb = res["n_steps"]
+            live = np.arange(width)[None, :] < n[:, None]
+            for name, key in (("ids", "id"), ("ages", "age")):
+                res[name] = np.where(live, out[key].cpu().numpy()[:nb, :width], -1)
+        return res
 
     def _collect_any(self, b0, nb, out, n):
         """_collect for visibility="any": the rows below n[s] are the markers, already in their order; nothing beyond them is
@@ -138,12 +153,14 @@ class ReplayTracker:
         msgs = batch_messages(obj[:, 0], has, tracker_message(self.point))
         if has.any():
             self.point = [0, 0, 0, 0] + list(obj[np.flatnonzero(has)[-1], 0])
-        return {"first_step": b0, "n_steps": nb, "n_roots": n, "kept": kept, "object_points": obj, "image_points": img, "messages": msgs}
+        res = {"first_step": b0, "n_steps": nb, "n_roots": n, "kept": kept, "object_points": obj, "image_points": img, "messages": msgs}
+        return self._with_ids(res, out, n, width)
 
     def run_batches(self, frames, send_many=None):
         """Generator over BATCHES of time steps: dicts with first_step, n_steps, n_roots [n], kept [n] (object points per time
         step), object_points [n, <= obj_count + 1, 3] (rows beyond kept[s] unused), image_points [n, P, C, 2] int64 (rows
-        beyond n_roots[s] unused), messages (list of n bytes objects).  `send_many(list_of_bytes)` is called once per batch when
+        beyond n_roots[s] unused), messages (list of n bytes objects); with `track`, ids and ages [n, <= obj_count + 1] int32 beside
+        object_points.  `send_many(list_of_bytes)` is called once per batch when
         given.  The bulk form of run(): no Python work per time step."""
         for b0, nb, out in self._submit(frames):
             res = self._collect(b0, nb, out)
@@ -154,15 +171,19 @@ class ReplayTracker:
     def run(self, frames, send=None):
         """Generator over time steps.  frames: uint8 [T, C, H, W] NumPy array or torch tensor (host or device).
         Yields dicts: object_points [<= obj_count+1, 3] (or shape (0,)), image_points [roots, C, 2] (or (0,)),
-        message (bytes).  `send(bytes)` is called per time step when given."""
+        message (bytes); with `track`, ids and ages [<= obj_count+1] beside object_points.  `send(bytes)` is called per time step when given."""
         empty = np.array([])
+        none = np.array([], np.int32)
         for res in self.run_batches(frames):
             n, kept, obj, img, msgs = res["n_roots"], res["kept"], res["object_points"], res["image_points"], res["messages"]
             for s in range(res["n_steps"]):
                 if send is not None:
                     send(msgs[s])
                 k = int(n[s])
-                yield {"object_points": obj[s, :kept[s]] if k else empty, "image_points": img[s, :k] if k else empty, "message": msgs[s]}
+                one = {"object_points": obj[s, :kept[s]] if k else empty, "image_points": img[s, :k] if k else empty, "message": msgs[s]}
+                if self.tracked:
+                    one["ids"], one["ages"] = (res[f][s, :kept[s]] if k else none for f in ("ids", "ages"))
+                yield one
 
 
 _MSG_HEAD = bytes([0x81, 0xa8]) + b"tracker1" + bytes([0x97, 0, 0, 0, 0])  # map of 1, fixstr(8), array of 7, four zero ints
