@@ -1,5 +1,6 @@
 // bayer.h -- the per-site arithmetic of Bayer -> gray (orc_bayer_gray_u8 in oracle/blob_oracle.c), shared by the Bayer pass
-// (bayer_gray.hip) and the box kernel's Bayer form (blob_boxes.hip), so that both form every gray value the same way.
+// (bayer_gray.hip) and the box kernel's Bayer form (boxes_dev.h: bayer_gray4 / bayer_gray1, used by blob_boxes.hip), so that both form
+// every gray value the same way.
 // A = any struct with the luma coefficients cb, cg, cr and the shift (BayerArgs, or the box kernel's scalar copy).
 #pragma once
 #include <hip/hip_runtime.h>

@@ -12,7 +12,7 @@
 //                        running sums whose history sits in a per-wave LDS ring).  Off the hot path: tiny images, tables
 //                        the compact format cannot hold, the single-image entry points.  Its list form works through the
 //                        wide tiles of the sparse path.
-// The rest of the stage: blob_scan.hip (which tiles can be skipped), blob_boxes.hip (the boxes the scan leaves),
+// The rest of the stage: blob_scan.hip (which tiles can be skipped), blob_settle.hip and blob_boxes.hip (the boxes the scan leaves),
 // blob_rows_staged.hip (this pipeline on the compact table; rows_dev.h holds what the two share), blob_setup.hip (undistort tables, single-image kernels).
 #include <hip/hip_runtime.h>
 #include <stdint.h>

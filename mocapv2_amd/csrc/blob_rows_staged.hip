@@ -20,27 +20,6 @@ constexpr int ROWS_LOADS = 9;                    // 16-byte staging loads per la
 constexpr int ROWS_STAGE_U = 64 * ROWS_LOADS;    // 16-byte units of source pixels per wave and band (9 KB; 61 KB of LDS per workgroup in all)
 constexpr int ROWS_STAGE_DW = 4 * ROWS_STAGE_U;
 
-// per (row, strip): box of the tap coordinates the row's pixels of the strip (columns 240 strip - 8 .. + 255) read, + 2
-__global__ void rowbox_kernel(const uint32_t* __restrict__ map4, ushort4* __restrict__ rowbox, int H, int W, int n_strips)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= H * n_strips) return;
-    const int row = i / n_strips, strip = i - row * n_strips;
-    const int xa = strip * 240 - 8 > 0 ? strip * 240 - 8 : 0, xb = strip * 240 + 247 < W - 1 ? strip * 240 + 247 : W - 1;
-    int x0 = 0x7fff, x1 = -0x8000, y0 = 0x7fff, y1 = -0x8000;
-    for (int x = xa; x <= xb; x++) {
-        const uint32_t w = map4[(size_t)row * W + x];
-        const int sx = x + ((int)(w << 21) >> 21), sy = row + ((int)(w << 10) >> 21);
-        x0 = sx < x0 ? sx : x0; x1 = sx + 1 > x1 ? sx + 1 : x1; y0 = sy < y0 ? sy : y0; y1 = sy + 1 > y1 ? sy + 1 : y1;
-    }
-    rowbox[i] = make_ushort4((unsigned short)(x0 + 2), (unsigned short)(x1 + 2), (unsigned short)(y0 + 2), (unsigned short)(y1 + 2));
-}
-void launch_rowbox(const uint32_t* map4, ushort4* rowbox, int H, int W, int n_strips, hipStream_t s)
-{
-    const int n = H * n_strips;
-    hipLaunchKernelGGL(rowbox_kernel, dim3((n + 63) / 64), dim3(64), 0, s, map4, rowbox, H, W, n_strips);
-}
-
 // source rectangle of a band in 16-byte units: origin (sxa a multiple of 16), pitch SP bytes = q units, SR rows, n units; its part
 // inside the image: origin (ux0, iy0), iq units x iSR rows, first / last unit at li0 / llast of the rectangle
 typedef uint32_t rows_u32x4 __attribute__((ext_vector_type(4))); // (a native vector: an array of HIP's uint4 filled by memcpy stays in scratch memory)
@@ -183,31 +162,21 @@ __global__ __launch_bounds__(256) void filter_rows_staged_kernel(FilterArgs a)
                 const int rowbase = __mul24(rc - R.sya, R.SP) + (lc.addr_x - R.sxa);
 #pragma unroll
                 for (int k = 0; k < 4; k++) {
-                    const uint32_t w = ww[k];
-                    const int dx = (int)(w << 21) >> 21, dy = (int)(w << 10) >> 21;
-                    const uint32_t fa = (w >> 22) & 31u, fb = w >> 27;
-                    const int A0 = __mul24(dy, R.SP) + (rowbase + k) + dx;
-                    const uint32_t p00 = Sbytes[A0], p01 = Sbytes[A0 + 1], p10 = Sbytes[A0 + R.SP], p11 = Sbytes[A0 + R.SP + 1];
-                    const uint32_t wa = 32u - fa, wb = 32u - fb;
-                    const uint32_t top = __umul24(p00, wa) + __umul24(p01, fa), bot = __umul24(p10, wa) + __umul24(p11, fa);
-                    B |= ((__umul24(top, wb) + __umul24(bot, fb) + 512u) >> 10) << (8 * k); // == (sum of 32*w*p + 2^14) >> 15
+                    const Map4 m = map4_decode(ww[k]);
+                    const int A0 = __mul24(m.dy, R.SP) + (rowbase + k) + m.dx;
+                    B |= map4_blend(m, Sbytes[A0], Sbytes[A0 + 1], Sbytes[A0 + R.SP], Sbytes[A0 + R.SP + 1]) << (8 * k);
                 }
             } else { // the band's source rectangle outgrew the buffer (strong local distortion): taps from memory
 #pragma unroll
                 for (int k = 0; k < 4; k++) {
-                    const uint32_t w = ww[k];
-                    const int dx = (int)(w << 21) >> 21, dy = (int)(w << 10) >> 21;
-                    const uint32_t fa = (w >> 22) & 31u, fb = w >> 27;
-                    const int sx = lc.addr_x + k + dx, sy = rc + dy;
+                    const Map4 m = map4_decode(ww[k]);
+                    const int sx = lc.addr_x + k + m.dx, sy = rc + m.dy;
                     const int sx0 = sx < 0 ? 0 : (sx > W - 1 ? W - 1 : sx), sx1 = sx + 1 < 0 ? 0 : (sx + 1 > W - 1 ? W - 1 : sx + 1);
                     const int sy0 = sy < 0 ? 0 : (sy > Hm1 ? Hm1 : sy), sy1 = sy + 1 < 0 ? 0 : (sy + 1 > Hm1 ? Hm1 : sy + 1);
                     const uint32_t o0 = (uint32_t)sy0 * (uint32_t)pitch, o1 = (uint32_t)sy1 * (uint32_t)pitch;
                     const uint32_t t00 = img[o0 + (uint32_t)sx0], t01 = img[o0 + (uint32_t)sx1], t10 = img[o1 + (uint32_t)sx0], t11 = img[o1 + (uint32_t)sx1];
                     const bool c0 = sx0 == sx, c1 = sx1 == sx + 1, q0 = sy0 == sy, q1 = sy1 == sy + 1;
-                    const uint32_t p00 = (c0 && q0) ? t00 : 0u, p01 = (c1 && q0) ? t01 : 0u, p10 = (c0 && q1) ? t10 : 0u, p11 = (c1 && q1) ? t11 : 0u;
-                    const uint32_t wa = 32u - fa, wb = 32u - fb;
-                    const uint32_t top = __umul24(p00, wa) + __umul24(p01, fa), bot = __umul24(p10, wa) + __umul24(p11, fa);
-                    B |= ((__umul24(top, wb) + __umul24(bot, fb) + 512u) >> 10) << (8 * k);
+                    B |= map4_blend(m, (c0 && q0) ? t00 : 0u, (c1 && q0) ? t01 : 0u, (c0 && q1) ? t10 : 0u, (c1 && q1) ? t11 : 0u) << (8 * k);
                 }
             }
             return (unsigned)row < (unsigned)H ? (B & lc.bytemask) : 0u; // rows and columns outside the image do not exist

@@ -81,6 +81,31 @@ __global__ void undistort_map_kernel(MapArgs m)
     if (flags) atomicOr(m.flags, flags);
 }
 
+// ---- per compact table: the boxes of source pixels that parts of the output read (TapBox, filter_dev.h) ----------------------
+// per 8x8 output cell (the box kernel sums them up over an item's exact region)
+__global__ void srcbox_kernel(const uint32_t* __restrict__ map4, ushort4* __restrict__ srcbox, int H, int W)
+{
+    const int ncx = (W + 7) >> 3, ncy = (H + 7) >> 3;
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= ncx * ncy) return;
+    const int cy = c / ncx, cx = c - cy * ncx;
+    TapBox b;
+    for (int y = 8 * cy; y < 8 * cy + 8 && y < H; y++)
+        for (int x = 8 * cx; x < 8 * cx + 8 && x < W; x++) b.add(map4[(size_t)y * W + x], x, y);
+    srcbox[c] = b.stored();
+}
+// per (row, strip): the row's pixels of the strip (columns 240 strip - 8 .. + 255), for the bands of the staged row pipeline
+__global__ void rowbox_kernel(const uint32_t* __restrict__ map4, ushort4* __restrict__ rowbox, int H, int W, int n_strips)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= H * n_strips) return;
+    const int row = i / n_strips, strip = i - row * n_strips;
+    const int xa = strip * 240 - 8 > 0 ? strip * 240 - 8 : 0, xb = strip * 240 + 247 < W - 1 ? strip * 240 + 247 : W - 1;
+    TapBox b;
+    for (int x = xa; x <= xb; x++) b.add(map4[(size_t)row * W + x], x, row);
+    rowbox[i] = b.stored();
+}
+
 // ---- stand-alone stages (drop-in surface of lib/CudaOperations.py and lib/ImageOperations.py) ---------------
 
 // fast_cuda_blur: floor(S/c) over the in-bounds taps of a ksize x ksize window
@@ -244,6 +269,16 @@ void launch_remap_stats(const StatArgs& a, hipStream_t s)
 void launch_undistort_map(const MapArgs& m, hipStream_t s)
 {
     hipLaunchKernelGGL(undistort_map_kernel, dim3((m.H + 63) / 64), dim3(64), 0, s, m);
+}
+void launch_srcbox(const uint32_t* map4, ushort4* srcbox, int H, int W, hipStream_t s)
+{
+    const int n = ((W + 7) >> 3) * ((H + 7) >> 3);
+    hipLaunchKernelGGL(srcbox_kernel, dim3((n + 63) / 64), dim3(64), 0, s, map4, srcbox, H, W);
+}
+void launch_rowbox(const uint32_t* map4, ushort4* rowbox, int H, int W, int n_strips, hipStream_t s)
+{
+    const int n = H * n_strips;
+    hipLaunchKernelGGL(rowbox_kernel, dim3((n + 63) / 64), dim3(64), 0, s, map4, rowbox, H, W, n_strips);
 }
 void launch_box_blur(const uint8_t* src, uint8_t* dst, int H, int W, int sp, int dp, int ksize, hipStream_t s)
 {

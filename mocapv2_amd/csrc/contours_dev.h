@@ -178,11 +178,11 @@ __device__ __forceinline__ void store_small_fields(int slot, const ContourRec& r
     rbox[slot][2] = (int16_t)bx1; rbox[slot][3] = (int16_t)by1;
 }
 
-// a tile's box (settle_tiles_kernel: .x = the recorded region's columns, .z = the scan box's) as the columns [x0, x1] that can hold
+// a tile's box (tile_box_pack, kernels.h: .x = the recorded region's columns, .z = the scan box's) as the columns [x0, x1] that can hold
 // set pixels or a hole start one column right of them; left as they are when the tile recorded nothing
 __device__ __forceinline__ void box_columns(uint4 box, int& x0, int& x1)
 {
-    const int r0 = (int)(box.x & 0xffffu), r1 = (int)(box.x >> 16), b0 = (int)(box.z & 0xffffu) & ~7, b1 = (int)(box.z >> 16) | 7;
+    const int r0 = span_first(box.x), r1 = span_last(box.x), b0 = span_first(box.z) & ~7, b1 = span_last(box.z) | 7;
     if (r0 <= r1) { x0 = r0 > b0 ? r0 : b0; x1 = (r1 < b1 ? r1 : b1) + 1; }
 }
 

@@ -1,5 +1,6 @@
 // filter_dev.h -- device helpers of the filter stage (undistort -> 5x5 in-bounds box sum -> threshold -> 5x5 majority) that
-// its kernel files share: blob_rows.hip, blob_rows_staged.hip, blob_boxes.hip, blob_setup.hip.
+// its kernel files share: blob_rows.hip, blob_rows_staged.hip, blob_boxes.hip, blob_setup.hip -- wave shifts and byte sums, the
+// general and the compact undistort table's words, the row pipeline's source fetch, the window-count table.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -46,6 +47,49 @@ __device__ __forceinline__ uint32_t remap_px(const uint8_t* __restrict__ img, in
     uint32_t top = p00 * wx0 + p01 * wx1, bot = p10 * wx0 + p11 * wx1;
     return (top * wy0 + bot * wy1 + 512u) >> 10; // == (sum of 32*w*p + 2^14) >> 15
 }
+
+// ---- the compact table's word (BoxArgs::map4), in one place -------------------------------------------------------------------
+// dx (11 bits, signed) | dy (11, signed) << 11 | x fraction (5) << 22 | y fraction (5) << 27: the 2x2 taps of pixel (x, y) start at
+// (x + dx, y + dy); taps outside the image read 0 (cv::remap's BORDER_CONSTANT).
+struct Map4 { int dx, dy; uint32_t fa, fb; };
+__device__ __forceinline__ Map4 map4_decode(uint32_t w)
+{
+    return {(int)(w << 21) >> 21, (int)(w << 10) >> 21, (w >> 22) & 31u, w >> 27};
+}
+// cv::remap's fixed-point blend of the four taps (p00 p01 / p10 p11)
+__device__ __forceinline__ uint32_t map4_blend(const Map4& m, uint32_t p00, uint32_t p01, uint32_t p10, uint32_t p11)
+{
+    const uint32_t wa = 32u - m.fa, wb = 32u - m.fb;
+    const uint32_t top = __umul24(p00, wa) + __umul24(p01, m.fa), bot = __umul24(p10, wa) + __umul24(p11, m.fa);
+    return (__umul24(top, wb) + __umul24(bot, m.fb) + 512u) >> 10; // == (sum of 32*w*p + 2^14) >> 15
+}
+// The pixel whose taps start at (sx, sy), the taps taken from memory: each is loaded from the nearest position inside the image
+// and zeroed by select where that is not its own (no branch around loads).  px(x, y) fetches one pixel of the image: a gray byte,
+// or a gray value formed from its Bayer neighbourhood.
+template <class Px>
+__device__ __forceinline__ uint32_t map4_blend_from_memory(const Map4& m, int sx, int sy, int W, int H, Px px)
+{
+    const int sx0 = sx < 0 ? 0 : (sx > W - 1 ? W - 1 : sx), sx1 = sx + 1 < 0 ? 0 : (sx + 1 > W - 1 ? W - 1 : sx + 1);
+    const int sy0 = sy < 0 ? 0 : (sy > H - 1 ? H - 1 : sy), sy1 = sy + 1 < 0 ? 0 : (sy + 1 > H - 1 ? H - 1 : sy + 1);
+    const uint32_t t00 = px(sx0, sy0), t01 = px(sx1, sy0), t10 = px(sx0, sy1), t11 = px(sx1, sy1);
+    const bool c0 = sx0 == sx, c1 = sx1 == sx + 1, r0 = sy0 == sy, r1 = sy1 == sy + 1;
+    return map4_blend(m, (c0 && r0) ? t00 : 0u, (c1 && r0) ? t01 : 0u, (c0 && r1) ? t10 : 0u, (c1 && r1) ? t11 : 0u);
+}
+// Box of the tap coordinates a set of table words reads (srcbox_kernel, rowbox_kernel): they lie in [-2, W + 1] x [-2, H + 1] and
+// are stored + 2.
+struct TapBox {
+    int x0 = 0x7fff, x1 = -0x8000, y0 = 0x7fff, y1 = -0x8000;
+    __device__ __forceinline__ void add(uint32_t w, int x, int y)
+    {
+        const Map4 m = map4_decode(w);
+        const int sx = x + m.dx, sy = y + m.dy;
+        x0 = sx < x0 ? sx : x0; x1 = sx + 1 > x1 ? sx + 1 : x1; y0 = sy < y0 ? sy : y0; y1 = sy + 1 > y1 ? sy + 1 : y1;
+    }
+    __device__ __forceinline__ ushort4 stored() const
+    {
+        return make_ushort4((unsigned short)(x0 + 2), (unsigned short)(x1 + 2), (unsigned short)(y0 + 2), (unsigned short)(y1 + 2));
+    }
+};
 
 // per-lane column constants of a 4-pixel group starting at column xl
 struct LaneCols {

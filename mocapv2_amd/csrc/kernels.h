@@ -1,4 +1,5 @@
-// kernels.h -- internal launch interface between the C-ABI (abi_*.hip) and the HIP kernels.
+// kernels.h -- internal launch interface between the C-ABI (abi_*.hip) and the HIP kernels, and the records the kernels of the
+// filter stage pass between them (mask layout, spans, work items, wide-tile entries, the tiles' regions).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -70,7 +71,7 @@ struct FilterArgs {
     const ushort4* rowbox = nullptr; // [cam_mod][H][n_strips]: per row and strip, the box of tap coordinates the strip's pixels read, + 2
     int stage_dw = 0;         // dwords of LDS a band's source rectangle may take (ROWS_STAGE_DW; smaller values are a test switch)
 };
-void launch_rowbox(const uint32_t* map4, ushort4* rowbox, int H, int W, int n_strips, hipStream_t s);
+void launch_rowbox(const uint32_t* map4, ushort4* rowbox, int H, int W, int n_strips, hipStream_t s); // (blob_setup.hip)
 int rows_stage_dwords();
 // (blob_rows_staged.hip; launch_filter_mask / launch_filter_tiles go through it when a.staged is set)
 void launch_filter_rows_staged(const FilterArgs& a, bool list, int blocks, hipStream_t s);
@@ -86,9 +87,10 @@ struct BayerArgs {
     int shift;
 };
 
-// The sparse half of the filter stage (blob_boxes.hip): tiles, boxes, work items.
+// The sparse half of the filter stage: tiles, boxes, work items.
 // A tile = 240 mask columns x rows_per_chunk rows.  The scan kernel leaves per tile the box of mask rows / columns that
-// hot cells can reach (tile_rows); settle_tiles_kernel turns the boxes into items; box_filter_kernel consumes them.
+// hot cells can reach (tile_rows); settle_tiles_kernel (blob_settle.hip) turns the boxes into items; box_filter_kernel
+// (blob_boxes.hip, its device helpers in boxes_dev.h) consumes them.
 #ifndef MOCAP_BOX_HCAP         // (build-time knobs for A/B builds, scratch/build_variant.sh)
 #define MOCAP_BOX_HCAP 1536
 #define MOCAP_BOX_SCAP 6656
@@ -97,8 +99,39 @@ struct BayerArgs {
 constexpr int BOX_HCAP = MOCAP_BOX_HCAP; // quad-rows (4 pixels x 1 row) of one item's patch (halving it for twice the waves per CU: 0.63 against 0.53 ms)
 constexpr int BOX_SCAP = MOCAP_BOX_SCAP; // bytes of source pixels staged in LDS per item (>= (BOX_HCAP + 64) * 4: the counts alias it)
 constexpr int BOX_MAX_PARTS = MOCAP_BOX_MAX_PARTS;  // items a tile is cut into at most (a whole 240 x 68 tile: 2 x 2)
-struct BoxItem { uint32_t image, tile, x01, y01, bx01, by01, pad0, pad1; }; // output region: columns x0 | x1 << 16, rows y0 | y1 << 16
-                                                                        //   (x0 > x1: skip); the scan's box of the tile (not clipped to it)
+// The span records settle writes and the box kernel, the row pipeline's list form and the contour stage read: a closed range
+// [a, b] of columns or rows in one word, a | b << 16 (a > b: empty).
+__host__ __device__ __forceinline__ uint32_t span_pack(int a, int b) { return (uint32_t)a | ((uint32_t)b << 16); }
+__host__ __device__ __forceinline__ int span_first(uint32_t s) { return (int)(s & 0xffffu); }
+__host__ __device__ __forceinline__ int span_last(uint32_t s) { return (int)(s >> 16); }
+// One work item of the box kernel, moved as its two 16-byte halves.  head: image, tile (chunk * n_strips + strip), the output region's
+// columns and rows as spans (an empty part of a split: columns 1 > 0, the consumer skips it); box: the columns and rows of the scan's
+// box the item takes its exact pixels from (not clipped to the tile), two words of padding.
+struct BoxItem {
+    uint4 head, box;
+    static __device__ __forceinline__ BoxItem make(int image, int tile, int x0, int x1, int y0, int y1, int bx0, int bx1, int by0, int by1)
+    {
+        const bool empty = x0 > x1 || y0 > y1;
+        return {make_uint4((uint32_t)image, (uint32_t)tile, empty ? 1u : span_pack(x0, x1), span_pack(y0, y1)),
+                make_uint4(span_pack(bx0, bx1), span_pack(by0, by1), 0u, 0u)};
+    }
+};
+static_assert(sizeof(BoxItem) == 32, "two 16-byte halves");
+// A tile's record in BoxArgs::cur_box: .x / .y the columns / rows of its output region of this batch (what the mask may hold
+// there; empty = none), .z / .w those of the scan's box (not clipped to the tile).
+__host__ __device__ __forceinline__ uint4 tile_box_pack(uint32_t out_x, uint32_t out_y, int bx0, int bx1, int by0, int by1)
+{
+    return make_uint4(out_x, out_y, span_pack(bx0, bx1), span_pack(by0, by1));
+}
+// An entry of the wide-tile list (BoxArgs::wide_tiles = FilterArgs::tiles): image, tile, rows [y0, y1]; a band without rows
+// (y0 > y1) is stored as [y0, y0 - 1] and skipped by the row pipeline.
+struct WideTile { int image, tile, y0, y1; };
+__host__ __device__ __forceinline__ uint4 wide_tile_pack(int image, int tile, int y0, int y1)
+{
+    return make_uint4((uint32_t)image, (uint32_t)tile, (uint32_t)y0, (uint32_t)(y0 <= y1 ? y1 : y0 - 1));
+}
+__host__ __device__ __forceinline__ WideTile wide_tile_unpack(uint4 e) { return {(int)e.x, (int)e.y, (int)e.z, (int)e.w}; }
+
 struct BoxArgs {
     const uint8_t* src; size_t image_stride; int pitch, H, W;
     uint32_t* mask; int words_per_row; // [n_images][mask_image_words(H, words_per_row)] in 32-row blocks (see mask_word_index)
@@ -134,10 +167,10 @@ struct BoxArgs {
     // every gray value it reads from their 3x3 neighbourhood (bayer.src / dst are not used; W % 16 == 0, H >= 8)
     BayerArgs bayer;
 };
-void launch_settle_tiles(const BoxArgs& a, hipStream_t s);
-void launch_box_filter(const BoxArgs& a, int grid, hipStream_t s, bool bayer = false);
+void launch_settle_tiles(const BoxArgs& a, hipStream_t s);                              // blob_settle.hip
+void launch_box_filter(const BoxArgs& a, int grid, hipStream_t s, bool bayer = false); // blob_boxes.hip
 int box_filter_blocks_per_cu();
-void launch_srcbox(const uint32_t* map4, ushort4* srcbox, int H, int W, hipStream_t s);
+void launch_srcbox(const uint32_t* map4, ushort4* srcbox, int H, int W, hipStream_t s); // blob_setup.hip
 
 struct MapArgs {
     double K[9], dist[5];

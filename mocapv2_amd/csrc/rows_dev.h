@@ -51,10 +51,10 @@ __device__ __forceinline__ bool rows_item(RowsItem& t, uint32_t it, const uint4*
     t.strip = (int)it;
     int r0e = 0, r1e = 0x7fffffff;
     if (LIST) {
-        const uint4 e = tiles[it];
-        t.image = __builtin_amdgcn_readfirstlane((int)e.x);
-        const int tile = __builtin_amdgcn_readfirstlane((int)e.y);
-        r0e = __builtin_amdgcn_readfirstlane((int)e.z); r1e = __builtin_amdgcn_readfirstlane((int)e.w) + 1;
+        const WideTile e = wide_tile_unpack(tiles[it]);
+        t.image = __builtin_amdgcn_readfirstlane(e.image);
+        const int tile = __builtin_amdgcn_readfirstlane(e.tile);
+        r0e = __builtin_amdgcn_readfirstlane(e.y0); r1e = __builtin_amdgcn_readfirstlane(e.y1) + 1;
         t.chunk = tile / n_strips; t.strip = tile - t.chunk * n_strips;
         t.slot = t.image % cam_mod;
     }
