@@ -177,6 +177,40 @@ MOCAP_API int mocap_blob_centroids_bayer(mocap_ctx_t ctx, const void* bayer_fram
                                int cam_mod, int slot_base, size_t image_stride, int pitch, int pattern, int gray_shift,
                                int32_t* out_xy_dev, long xy_stride, int32_t* out_count_dev, long count_stride,
                                int max_blobs, void* stream);
+/* Sub-pixel centroids: back to the frame bytes around every integer centroid of mocap_blob_centroids.  The reference has no
+ * counterpart (its centroid is int(M["m10"] / M["m00"]), which truncates): the contract is the definition of DESIGN.md section 2,
+ * restated by tests/subpixel_ref.py; integer sums and FP64 operations rounded one by one, so the device equals the restatement
+ * bit for bit.  New symbol, MOCAP_ABI_VERSION stays 7.
+ * Frames, cam_mod, slot_base, image_stride and pitch as in mocap_blob_centroids (no alignment demands); pattern -1 = gray
+ * frames, 0..3 = raw Bayer frames whose gray values are formed site by site as mocap_bayer_gray_u8 forms them (gray_shift 14
+ * or 15; it is not looked at for gray frames; H, W >= 3), no gray frame is written.  xy_dev, count_dev and their strides mean
+ * what they mean in mocap_blob_centroids: the records are read in place.  An image with count <= 0 writes nothing, a count above
+ * max_blobs (1..256) refines the first max_blobs points, rows at and beyond the count are not written.
+ * Per centroid (cx, cy): the start pixel is the centroid mapped into the raw frame by the slot's forward lens model (U, V),
+ * rounded and clamped into the image ((cx, cy) itself for an identity slot); over the window of `radius` (1..31) pixels around
+ * it, clipped to the image, with the weights w = max(0, p - floor) (floor 0..254): S = sum w and the weighted mean position; the
+ * window moves to the mean's pixel and the sums are formed again, `iters` (1..8) windows at most.  Flags of the last window:
+ *   MOCAP_SUBPIX_EMPTY      S == 0
+ *   MOCAP_SUBPIX_EDGE       a pixel of the unclipped window's outermost ring has w > 0: the blob is wider than the window, or a
+ *                           neighbour leaks in
+ *   MOCAP_SUBPIX_NEIGHBOUR  the start pixel of another centroid of the image lies inside the window
+ *   MOCAP_SUBPIX_MOVING     the last window still wants to move
+ *   MOCAP_SUBPIX_CUT        the image border clipped the window (informational)
+ * coords 0 (raw): the mean, a pixel of the distorted frame -- what mocap_correspond_visible(distorted = 1) takes; coords 1
+ * (ideal): the mean through cv.undistortPoints' five fixed-point rounds -- a drop-in for the integer centroid in mocap_correspond
+ * and mocap_correspond_visible(distorted = 0).  A point flagged EMPTY, EDGE, NEIGHBOUR or MOVING falls back to its integer
+ * centroid in the coordinates asked for: (cx, cy) for coords 1, (U, V) for coords 0 -- never worse than what the caller had, and
+ * never silently.  An identity slot skips both lens maps.
+ *   out_xy_dev   float64 [n_images][max_blobs][2], image n at out_xy_dev + n * out_xy_stride (in doubles)
+ *   out_info_dev int32 [n_images][max_blobs][2] = (S of the last window, flags), image n at + n * out_info_stride; or NULL
+ * Bad arguments are MOCAP_E_INVALID, a slot without mocap_set_undistort is MOCAP_E_STATE; neither launches anything. */
+enum { MOCAP_SUBPIX_EMPTY = 1, MOCAP_SUBPIX_EDGE = 2, MOCAP_SUBPIX_NEIGHBOUR = 4, MOCAP_SUBPIX_MOVING = 8, MOCAP_SUBPIX_CUT = 16 };
+MOCAP_API int mocap_refine_centroids(mocap_ctx_t ctx, const void* frames_dev, int n_images, int cam_mod, int slot_base,
+                                     size_t image_stride, int pitch, int pattern, int gray_shift, const int32_t* xy_dev,
+                                     long xy_stride, const int32_t* count_dev, long count_stride, int max_blobs, int radius,
+                                     int floor, int iters, int coords, double* out_xy_dev, long out_xy_stride,
+                                     int32_t* out_info_dev, long out_info_stride, void* stream);
+
 /* fast_cuda_demosaic(bayer) (lib/CudaOperations.py:84-100): uint8[H][W] -> uint8[H][W][3] (B,G,R) */
 MOCAP_API int mocap_demosaic_u8(mocap_ctx_t ctx, const void* bayer_dev, void* bgr_dev, int height, int width, int spitch,
                       void* stream);

@@ -49,6 +49,7 @@ SIGNATURES = {
     "mocap_set_fundamentals": [_vp, _i, _dp],
     "mocap_blob_centroids": [_vp, _vp, _i, _i, _i, _sz, _i, _vp, _l, _vp, _l, _i, _vp],
     "mocap_blob_centroids_bayer": [_vp, _vp, _vp, _i, _i, _i, _sz, _i, _i, _i, _vp, _l, _vp, _l, _i, _vp],
+    "mocap_refine_centroids": [_vp, _vp, _i, _i, _i, _sz, _i, _i, _i, _vp, _l, _vp, _l, _i, _i, _i, _i, _i, _vp, _l, _vp, _l, _vp],
     "mocap_filter_mask": [_vp, _vp, _i, _i, _i, _sz, _i, _vp, _vp],
     "mocap_contours_from_mask": [_vp, _vp, _i, _vp, _l, _vp, _l, _i, _vp, _vp, _i, _vp],
     "mocap_image_filter_u8": [_vp, _vp, _vp, _i, _i, _i, _i, _vp],

@@ -711,6 +711,41 @@ int mocap_blob_centroids_bayer(mocap_ctx_t c, const void* bayer_frames, void* gr
                         (hipStream_t)stream);
 }
 
+// ---- sub-pixel centroids (subpixel.hip) ---------------------------------------------------------------------------------
+int mocap_refine_centroids(mocap_ctx_t c, const void* frames, int n_images, int cam_mod, int slot_base, size_t image_stride, int pitch,
+                           int pattern, int gray_shift, const int32_t* xy, long xy_stride, const int32_t* count, long count_stride,
+                           int max_blobs, int radius, int floor_, int iters, int coords, double* out_xy, long out_xy_stride,
+                           int32_t* out_info, long out_info_stride, void* stream)
+{
+    if (!c || !frames || !xy || !count || !out_xy) return fail(MOCAP_E_INVALID, "null argument");
+    if (radius < 1 || radius > 31 || floor_ < 0 || floor_ > 254 || iters < 1 || iters > 8 || (coords != 0 && coords != 1))
+        return fail(MOCAP_E_INVALID, "radius %d (1..31), floor %d (0..254), iters %d (1..8), coords %d (0 raw, 1 ideal)", radius, floor_, iters, coords);
+    if (max_blobs < 1 || max_blobs > SUBPIX_MAX_BLOBS || xy_stride < 2L * max_blobs || count_stride < 1 || out_xy_stride < 2L * max_blobs ||
+        (out_info && out_info_stride < 2L * max_blobs))
+        return fail(MOCAP_E_INVALID, "max_blobs %d (1..%d), strides %ld %ld %ld %ld", max_blobs, SUBPIX_MAX_BLOBS, xy_stride, count_stride,
+                    out_xy_stride, out_info_stride);
+    if (pattern < -1 || pattern > 3 || (pattern >= 0 && gray_shift != 14 && gray_shift != 15))
+        return fail(MOCAP_E_INVALID, "pattern %d (-1 = gray frames, 0..3 = BG, GB, RG, GR) / gray_shift %d (14 or 15)", pattern, gray_shift);
+    if (pattern >= 0 && (c->H < 3 || c->W < 3)) return fail(MOCAP_E_INVALID, "Bayer frames need H, W >= 3");
+    TRY(check_frames(c, frames, n_images, cam_mod, slot_base, image_stride, pitch));
+    if (set_device(c)) return MOCAP_E_HIP;
+    RefineArgs a{};
+    a.src = (const uint8_t*)frames; a.image_stride = image_stride; a.pitch = pitch; a.H = c->H; a.W = c->W;
+    a.n_images = n_images; a.cam_mod = cam_mod;
+    if (pattern >= 0) { // (the frames are their own gray buffer: bayer_args wants one, nothing is written)
+        BayerArgs b;
+        TRY(bayer_args(b, frames, nullptr, n_images, c->H, c->W, pitch, pitch, image_stride, image_stride, pattern, gray_shift, true));
+        a.bayer = 1; a.ry = b.ry; a.rx = b.rx; a.cb = b.cb; a.cg = b.cg; a.cr = b.cr; a.shift = b.shift;
+    }
+    a.lens = c->lens + (size_t)SUBPIX_LENS * slot_base;
+    a.xy = xy; a.xy_stride = xy_stride; a.count = count; a.count_stride = count_stride; a.max_blobs = max_blobs;
+    a.radius = radius; a.floor = floor_; a.iters = iters; a.coords = coords;
+    a.out_xy = out_xy; a.out_xy_stride = out_xy_stride; a.out_info = out_info; a.out_info_stride = out_info_stride;
+    launch_refine_centroids(a, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return MOCAP_OK;
+}
+
 int mocap_undistort_u8(mocap_ctx_t c, int slot, const void* src, void* dst, int spitch, int dpitch, void* stream)
 {
     if (!c || !src || !dst) return fail(MOCAP_E_INVALID, "null argument");

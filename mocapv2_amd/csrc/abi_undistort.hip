@@ -32,6 +32,14 @@ int mocap_set_undistort(mocap_ctx_t c, int slot, const double K[9], const double
     c->slot_state[slot] = (flags & 1u) ? 2 : 1;
     c->slot_compact[slot] = (flags & 2u) ? 0 : 1;
     c->slot_wmax[slot] = c->slot_state[slot] == 1 ? 1024u : 0u; // identity: every source pixel feeds exactly one output pixel
+    {   // the lens itself stays on the device too: mocap_refine_centroids maps points through it in both directions
+        double lens[SUBPIX_LENS] = {0};
+        memcpy(lens, K, 9 * sizeof(double));
+        memcpy(lens + 9, dist, 5 * sizeof(double));
+        lens[14] = c->slot_state[slot] == 1 ? 1.0 : 0.0;
+        TRY(c->lens.reserve((size_t)SUBPIX_LENS * c->n_slots, true));
+        HIP_TRY(hipMemcpy(c->lens + (size_t)SUBPIX_LENS * slot, lens, sizeof(lens), hipMemcpyHostToDevice));
+    }
     launch_srcbox(m.map4, c->srcbox + (size_t)ncx_ * ncy_ * slot, c->H, c->W, 0);
     HIP_TRY(hipGetLastError());
     launch_rowbox(m.map4, c->rowbox + (size_t)c->H * n_strips_ * slot, c->H, c->W, n_strips_, 0);

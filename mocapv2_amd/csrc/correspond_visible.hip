@@ -102,22 +102,6 @@ __device__ __forceinline__ bool solve_members(const double* cam, const double* s
     return front;
 }
 
-// cv.undistortPoints(p, K, dist, P=K) by calibrate.undistort_points' five fixed-point rounds, the same operations
-__device__ __forceinline__ void undistort_pt(const double* cam, double& px, double& py)
-{
-    const double fx = cam[oK + 0], cx = cam[oK + 2], fy = cam[oK + 4], cy = cam[oK + 5];
-    const double k1 = cam[oD + 0], k2 = cam[oD + 1], p1 = cam[oD + 2], p2 = cam[oD + 3], k3 = cam[oD + 4];
-    const double x0 = (px - cx) / fx, y0 = (py - cy) / fy;
-    double x = x0, y = y0;
-    for (int it = 0; it < 5; it++) {
-        const double r2 = x * x + y * y;
-        const double icd = 1.0 / (1 + ((k3 * r2 + k2) * r2 + k1) * r2);
-        const double dx = 2 * p1 * x * y + p2 * (r2 + 2 * x * x), dy = p1 * (r2 + 2 * y * y) + 2 * p2 * x * y;
-        x = (x0 - dx) * icd; y = (y0 - dy) * icd;
-    }
-    px = fx * x + cx; py = fy * y + cy;
-}
-
 } // namespace
 
 template <typename PT>
@@ -183,7 +167,8 @@ __global__ __launch_bounds__(256) void correspond_visible_kernel(VisArgs a)
         Ki[6] = c20 / det; Ki[7] = c21 / det; Ki[8] = c22 / det;
     }
     if (a.distorted)
-        for (int w = tid; w < C * P; w += nth) undistort_pt(cam + (w / P) * CAMW, spts[2 * w], spts[2 * w + 1]);
+        for (int w = tid; w < C * P; w += nth) // (geom_dev.h: cv.undistortPoints' five fixed-point rounds)
+            undistort_pt(cam + (w / P) * CAMW + oK, cam + (w / P) * CAMW + oD, spts[2 * w], spts[2 * w + 1]);
     __syncthreads();
     if (s_err) {
         if (tid == 0) a.n[t] = s_err == 3 ? CORR_ERR_BLOB : CORR_ERR_TRUNCATED;

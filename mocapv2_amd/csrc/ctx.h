@@ -111,6 +111,7 @@ struct mocap_ctx {
     Buf<ushort4> srcbox;      // [n_slots][ceil(H/8)][ceil(W/8)]: source box per 8x8 output cell (box kernel)
     Buf<ushort4> rowbox;      // [n_slots][H][n_strips]: source box per row and strip (staged row pipeline)
     Buf<uint32_t> map_flags;  // [n_slots] device
+    Buf<double> lens;         // [n_slots][SUBPIX_LENS]: the slot's K, dist and "the table is the identity" (mocap_refine_centroids)
     std::vector<int> slot_state; // 0 unset, 1 identity, 2 remap
     std::vector<int> slot_compact; // 1 = the slot's displacements fit the compact table (identity: always)
     std::vector<uint32_t> slot_wmax; // largest total blend weight of a source pixel (1024 = identity); 0 = early-out not provable

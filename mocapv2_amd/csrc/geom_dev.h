@@ -1,5 +1,6 @@
 // geom_dev.h -- device helpers the geometry kernels share (geom.hip, correspond_visible.hip): the DLT system of a point seen by
-// several cameras, the Jacobi eigen-solver behind it, and the typed load of an image point.  Device code only; the files that
+// several cameras, the Jacobi eigen-solver behind it, the lens model of a point in both directions (also subpixel.hip's), and the
+// typed load of an image point.  Device code only; the files that
 // include it are built with -ffp-contract=off, so every operation here is rounded on its own.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -112,6 +113,37 @@ struct DltAcc {
         X[0] = v[0] / v[3]; X[1] = v[1] / v[3]; X[2] = v[2] / v[3];
     }
 };
+
+// cv.undistortPoints(p, K, dist, P=K) by calibrate.undistort_points' five fixed-point rounds, the same operations
+// (K row-major [9], dist = k1, k2, p1, p2, k3); used by correspond_visible.hip and subpixel.hip
+__device__ __forceinline__ void undistort_pt(const double* K, const double* dist, double& px, double& py)
+{
+    const double fx = K[0], cx = K[2], fy = K[4], cy = K[5];
+    const double k1 = dist[0], k2 = dist[1], p1 = dist[2], p2 = dist[3], k3 = dist[4];
+    const double x0 = (px - cx) / fx, y0 = (py - cy) / fy;
+    double x = x0, y = y0;
+    for (int it = 0; it < 5; it++) {
+        const double r2 = x * x + y * y;
+        const double icd = 1.0 / (1 + ((k3 * r2 + k2) * r2 + k1) * r2);
+        const double dx = 2 * p1 * x * y + p2 * (r2 + 2 * x * x), dy = p1 * (r2 + 2 * y * y) + 2 * p2 * x * y;
+        x = (x0 - dx) * icd; y = (y0 - dy) * icd;
+    }
+    px = fx * x + cx; py = fy * y + cy;
+}
+
+// The forward lens model of a pixel of the undistorted image: where it lies in the raw frame (the map undistort_pt inverts, with
+// the same tangential sums; DESIGN.md section 2, "sub-pixel centroids")
+__device__ __forceinline__ void distort_pt(const double* K, const double* dist, double& px, double& py)
+{
+    const double fx = K[0], cx = K[2], fy = K[4], cy = K[5];
+    const double k1 = dist[0], k2 = dist[1], p1 = dist[2], p2 = dist[3], k3 = dist[4];
+    const double x = (px - cx) / fx, y = (py - cy) / fy;
+    const double r2 = x * x + y * y;
+    const double cd = 1 + ((k3 * r2 + k2) * r2 + k1) * r2;
+    const double xd = x * cd + (2 * p1 * x * y + p2 * (r2 + 2 * x * x));
+    const double yd = y * cd + (p1 * (r2 + 2 * y * y) + 2 * p2 * x * y);
+    px = fx * xd + cx; py = fy * yd + cy;
+}
 
 template <typename PT>
 __device__ __forceinline__ void load_pt(const void* base, size_t idx, double& x, double& y)

@@ -541,6 +541,24 @@ struct TrackArgs {
 };
 void launch_track_markers(const TrackArgs& a, hipStream_t s);
 
+// sub-pixel centroids from the frames (subpixel.hip): the flag bits are include/mocap_hip.h's MOCAP_SUBPIX_*
+enum { SUBPIX_EMPTY = 1, SUBPIX_EDGE = 2, SUBPIX_NEIGHBOUR = 4, SUBPIX_MOVING = 8, SUBPIX_CUT = 16 };
+constexpr int SUBPIX_MAX_BLOBS = 256; // centroids of one image at most: one per thread of its workgroup
+constexpr int SUBPIX_LENS = 16;       // doubles per slot in `lens`: K (9), dist (5), 1.0 = the slot's table is the identity, padding
+struct RefineArgs {
+    const uint8_t* src; size_t image_stride; int pitch, H, W; // gray frames, or raw Bayer frames (bayer = 1: ry, rx, cb, cg, cr, shift as BayerArgs)
+    int n_images, cam_mod;
+    int bayer, ry, rx; uint32_t cb, cg, cr; int shift;
+    const double* lens;        // [cam_mod][SUBPIX_LENS] of the first slot used
+    const int32_t* xy; long xy_stride;       // integer centroids of image n: xy + n * xy_stride, (cx, cy) pairs
+    const int32_t* count; long count_stride; // their number: count[n * count_stride]
+    int max_blobs;             // 1..SUBPIX_MAX_BLOBS
+    int radius, floor, iters, coords;
+    double* out_xy; long out_xy_stride;      // [n_images][max_blobs][2] through the stride (in doubles)
+    int32_t* out_info; long out_info_stride; // (S of the last window, flags) per centroid, or null
+};
+void launch_refine_centroids(const RefineArgs& a, hipStream_t s);
+
 void launch_fundamental_ransac(const FundArgs& a, hipStream_t s);
 
 void launch_correspond(const CorrArgs& a, hipStream_t s);

@@ -23,6 +23,9 @@ MAX_BLOBS = 128       # centroid record capacity per camera image (SURVEY.md sec
 GRAY_SHIFT = 15
 REC_INTS = 2 + 2 * MAX_BLOBS  # int32 record: count, pad, xy[MAX_BLOBS][2]
 RIG_LOSSES = {"none": 0, "cauchy": 1}  # MOCAP_RIG_LOSS_*
+SUBPIX_COORDS = {"raw": 0, "ideal": 1}  # mocap_refine_centroids' coords
+SUBPIX_EMPTY, SUBPIX_EDGE, SUBPIX_NEIGHBOUR, SUBPIX_MOVING, SUBPIX_CUT = 1, 2, 4, 8, 16  # MOCAP_SUBPIX_*
+SUBPIX_FALLBACK = SUBPIX_EMPTY | SUBPIX_EDGE | SUBPIX_NEIGHBOUR | SUBPIX_MOVING  # the point holds its integer centroid
 
 
 def _ptr(t):
@@ -176,6 +179,40 @@ class MocapContext:
         n, rec_ints = records.shape
         return records[:, 2:].reshape(n, (rec_ints - 2) // 2, 2), records[:, 0]
 
+    def refine_centroids(self, frames, records, cam_mod=1, slot_base=0, max_blobs=None, *, radius, floor, iters=3, coords="ideal",
+                         bayer_pattern=None, gray_shift=GRAY_SHIFT, out=None):
+        """Sub-pixel centroids (mocap_refine_centroids; the definition is DESIGN.md section 2): for every integer centroid of
+        `records` (blob_centroids' records of the same frames, read in place) the intensity-weighted centroid, weights
+        max(0, p - floor), over a window of `radius` pixels (1..31) that follows the blob for at most `iters` windows (1..8).
+        radius and floor have no defaults: they depend on the markers' size in the image and on the background.
+        coords: "ideal" -- pixels of the undistorted image, a drop-in for the integer centroids (correspond_records and
+        correspond_visible_records take them as `points`); "raw" -- pixels of the distorted frame, what
+        correspond_visible(distorted=True) takes.  bayer_pattern: the frames are raw Bayer frames (no gray frame is written).
+        max_blobs (default: the records' capacity, at most 256): points refined per image.
+        Returns {"xy": float64 [n, max_blobs, 2], "weight": int32 [n, max_blobs] (the last window's sum of weights), "flags":
+        int32 [n, max_blobs] (SUBPIX_* bits)} as device tensors; weight and flags are views of out["info"].  A point flagged
+        EMPTY, EDGE, NEIGHBOUR or MOVING holds its integer centroid in the coordinates asked for.  Rows at and beyond an image's
+        count are not written (a fresh `out` holds zeros there)."""
+        flat, n, stride, pitch = self._frames(frames)
+        rec_ints = records.shape[-1]
+        assert records.is_cuda and records.is_contiguous() and records.dtype == torch.int32 and records.numel() == n * rec_ints
+        max_blobs = min(256, (rec_ints - 2) // 2) if max_blobs is None else int(max_blobs)
+        if coords not in SUBPIX_COORDS:
+            raise ValueError(f"coords {coords!r}: one of {sorted(SUBPIX_COORDS)}")
+        if out is None:
+            out = {"xy": torch.zeros((n, max_blobs, 2), dtype=torch.float64, device=self.device),
+                   "info": torch.zeros((n, max_blobs, 2), dtype=torch.int32, device=self.device)}
+        xy, info = out["xy"], out["info"]
+        assert xy.is_contiguous() and xy.dtype == torch.float64 and xy.shape[0] == n and xy.shape[1] >= max_blobs and xy.shape[2] == 2
+        assert info.is_contiguous() and info.dtype == torch.int32 and info.shape[0] == n and info.shape[1] >= max_blobs and info.shape[2] == 2
+        _abi.check(self.lib.mocap_refine_centroids(self._h, _ptr(flat), n, cam_mod, slot_base, stride, pitch,
+                                                   -1 if bayer_pattern is None else int(bayer_pattern), int(gray_shift),
+                                                   C.c_void_p(records.data_ptr() + 8), rec_ints, _ptr(records), rec_ints, max_blobs,
+                                                   int(radius), int(floor), int(iters), SUBPIX_COORDS[coords], _ptr(xy),
+                                                   2 * xy.shape[1], _ptr(info), 2 * info.shape[1], _stream()))
+        out["weight"], out["flags"] = info[:, :, 0], info[:, :, 1]
+        return out
+
     def filter_mask(self, frames, cam_mod=1, slot_base=0, mask=None):
         flat, n, stride, pitch = self._frames(frames)
         wpr = (self.width + 31) // 32
@@ -272,11 +309,22 @@ class MocapContext:
                                              _ptr(out["root"]), _ptr(out["order"]), _ptr(out["n"]), _stream()))
         return out
 
+    @staticmethod
+    def _record_points(points, records, P, stride_t, stride_c, t0):
+        """(pointer, stride_t, stride_c) of float64 points [images, rows >= P, 2] that stand beside the records, image for image
+        (refine_centroids' xy), read with pts_f64 = 1 through the records' own layout"""
+        assert points.is_cuda and points.is_contiguous() and points.dtype == torch.float64 and points.dim() == 3, points.shape
+        assert points.shape[0] == records.numel() // records.shape[-1] and points.shape[1] >= P and points.shape[2] == 2, (points.shape, P)
+        row = 2 * points.shape[1]
+        return C.c_void_p(points.data_ptr() + 8 * row * stride_t * t0), row * stride_t, row * stride_c
+
     def correspond_records(self, records, T, Cn, t0=0, stride_t=None, stride_c=None, P=None, cutoff=10.0, max_groups=4096,
-                           out=None):
+                           out=None, points=None):
         """Correspondence + triangulation straight from centroid records (int32 [..., 2 + 2*max_blobs]) laid out so
         that the record of (time step t0 + t, camera c) sits stride_t*t + stride_c*c records after records[t0 * ...].
-        Default layout: records [T_total, C, rec] (time-major).  P limits the points read per camera."""
+        Default layout: records [T_total, C, rec] (time-major).  P limits the points read per camera.
+        points: float64 [images, rows >= P, 2] on the GPU, one block per record in the records' order (refine_centroids' xy):
+        the points are read from there, the counts still from the records."""
         rec_ints = records.shape[-1]
         flat = records.reshape(-1, rec_ints)
         stride_t = Cn if stride_t is None else stride_t
@@ -284,8 +332,10 @@ class MocapContext:
         P = P or min(255, (rec_ints - 2) // 2)
         out = out or self._corr_out(T, P, Cn)
         base = flat.data_ptr() + 4 * rec_ints * stride_t * t0
-        _abi.check(self.lib.mocap_correspond(self._h, C.c_void_p(base + 8), rec_ints * stride_t, rec_ints * stride_c,
-                                             C.c_void_p(base), rec_ints * stride_t, rec_ints * stride_c, 0, T, Cn, P,
+        pts = (C.c_void_p(base + 8), rec_ints * stride_t, rec_ints * stride_c) if points is None else \
+            self._record_points(points, records, P, stride_t, stride_c, t0)
+        _abi.check(self.lib.mocap_correspond(self._h, *pts,
+                                             C.c_void_p(base), rec_ints * stride_t, rec_ints * stride_c, int(points is not None), T, Cn, P,
                                              cutoff, max_groups, _ptr(out["xyz"]), _ptr(out["err"]), _ptr(out["grp"]),
                                              _ptr(out["root"]), _ptr(out["order"]), _ptr(out["n"]), _stream()))
         return out
@@ -326,16 +376,19 @@ class MocapContext:
                               max_err, max_passes, max_hyp, Q, out)
 
     def correspond_visible_records(self, records, T, Cn, t0=0, stride_t=None, stride_c=None, P=None, distorted=False, cutoff=10.0,
-                                   gate=10.0, min_views=2, max_err=25.0, max_passes=3, max_hyp=8192, Q=None, out=None):
-        """correspond_visible straight from centroid records, laid out and read as correspond_records reads them."""
+                                   gate=10.0, min_views=2, max_err=25.0, max_passes=3, max_hyp=8192, Q=None, out=None, points=None):
+        """correspond_visible straight from centroid records, laid out and read as correspond_records reads them (`points`
+        included)."""
         rec_ints = records.shape[-1]
         flat = records.reshape(-1, rec_ints)
         stride_t = Cn if stride_t is None else stride_t
         stride_c = 1 if stride_c is None else stride_c
         P = P or min(255, (rec_ints - 2) // 2)
         base = flat.data_ptr() + 4 * rec_ints * stride_t * t0
-        return self._vis_call(C.c_void_p(base + 8), rec_ints * stride_t, rec_ints * stride_c, C.c_void_p(base), rec_ints * stride_t,
-                              rec_ints * stride_c, False, T, Cn, P, distorted, cutoff, gate, min_views, max_err, max_passes,
+        pts = (C.c_void_p(base + 8), rec_ints * stride_t, rec_ints * stride_c) if points is None else \
+            self._record_points(points, records, P, stride_t, stride_c, t0)
+        return self._vis_call(*pts, C.c_void_p(base), rec_ints * stride_t,
+                              rec_ints * stride_c, points is not None, T, Cn, P, distorted, cutoff, gate, min_views, max_err, max_passes,
                               max_hyp, Q, out)
 
     def track_state(self, max_tracks):

@@ -172,6 +172,7 @@ class _Lane:
 
     def __init__(self, ctx, records, stream):
         self.ctx, self.records, self.stream, self.out = ctx, records, stream, None
+        self.subpix = None   # refine_centroids' outputs beside the records (the tracker was built with `subpixel`)
         self.gathered = None # all ranks' records (collective == "rccl")
         self.staging = None  # device copy of a batch that arrived in host memory
 
@@ -186,7 +187,7 @@ class BatchTracker:
     def __init__(self, K, dist, R, t, F, width, height, steps_per_rank, world=1, rank=0, device=0, group=None,
                  max_points=32, max_groups=4096, depth=1, bayer_pattern=None, gray_shift=GRAY_SHIFT, collective="auto",
                  force_collective=False, visibility="all", min_views=2, gate=10.0, max_err=25.0, max_passes=3, cutoff=10.0,
-                 max_hyp=8192, track=None):
+                 max_hyp=8192, track=None, subpixel=None):
         """visibility: which markers stage B reports --
              "all"   the reference's find_point_correspondance_and_object_points (mocap_correspond): a marker every camera sees,
                      searched from camera 0's points; the outputs are MocapContext.correspond's;
@@ -206,7 +207,21 @@ class BatchTracker:
              status [T].  Their rows are the rows of xyz with visibility="any"; with "all" they are the positions in `order` (row
              k = the k-th reported root: xyz is gathered through `order` on the device first).  One state per tracker, shared
              by its batches in flight, whose track calls are chained by events.  Needs world == 1: time is sharded across
-             ranks, and a hand-off of the state between ranks is not implemented."""
+             ranks, and a hand-off of the state between ranks is not implemented.
+           subpixel: None, or {"radius": r, "floor": f, "iters": 3} -- sub-pixel image points (MocapContext.refine_centroids,
+             DESIGN.md section 2; radius and floor are required, there are no defaults for them): `extract` refines the integer
+             centroids from the frames right behind the blob stage, and stage B reads the refined points (ideal pixels) in
+             either visibility, also from raw Bayer frames.  The outputs gain subpix_flags [images, max_points] (SUBPIX_* bits per
+             image point; a flagged point is its integer centroid).  Needs world == 1: the all-gather carries the int32 records only.
+             None is the path as it was."""
+        self.subpixel = None
+        if subpixel is not None:
+            if world > 1:
+                raise ValueError("subpixel needs world == 1: the all-gather carries the int32 centroid records only")
+            unknown = set(subpixel) - {"radius", "floor", "iters"}
+            if unknown or "radius" not in subpixel or "floor" not in subpixel:
+                raise ValueError(f"subpixel: a dict with radius and floor (both required) and iters; got {sorted(subpixel)}")
+            self.subpixel = {"radius": int(subpixel["radius"]), "floor": int(subpixel["floor"]), "iters": int(subpixel.get("iters", 3))}
         self.track = None
         if track is not None:
             if world > 1:
@@ -255,6 +270,9 @@ class BatchTracker:
             records = torch.zeros((self.per, self.rec_ints), dtype=torch.int32, device=ctx.device)
             stream = torch.cuda.Stream(device=ctx.device) if depth > 1 else None
             self.lanes.append(_Lane(ctx, records, stream))
+            if self.subpixel:
+                self.lanes[-1].subpix = {"xy": torch.zeros((self.per, max_points, 2), dtype=torch.float64, device=ctx.device),
+                                         "info": torch.zeros((self.per, max_points, 2), dtype=torch.int32, device=ctx.device)}
         self._k = 0
         self._cur = self.lanes[0]
         self.track_state = self.lanes[0].ctx.track_state(self.max_tracks) if self.track else None
@@ -334,6 +352,9 @@ class BatchTracker:
             kw = {"bayer_pattern": self.bayer_pattern, "gray_shift": self.gray_shift}
         if self.world == 1:
             ctx.blob_centroids(frames, cam_mod=self.n_cam, max_blobs=self.max_points, records=self.records, **kw)
+            if self.subpixel:  # same stream, right behind the contour stage, from the same frames and records
+                ctx.refine_centroids(frames, self.records, cam_mod=self.n_cam, max_blobs=self.max_points, coords="ideal",
+                                     out=self._cur.subpix, **self.subpixel, **kw)
             return self.records
         o = 0
         for c, t0, t1 in self.segs:
@@ -347,17 +368,20 @@ class BatchTracker:
         """Stage B for this rank's time steps [rank * T, (rank + 1) * T) from the records of all cameras
         (world == 1: self.records, time-major; else the all-gathered records, camera-major)."""
         ctx = self.ctx
+        points = self._cur.subpix["xy"] if self.subpixel else None  # (world == 1: `gathered` is this lane's records)
         if self.visibility == "any":
             t0, st, sc = (0, self.n_cam, 1) if self.world == 1 else (self.rank * self.T, 1, self.t_total)
             self.out = ctx.correspond_visible_records(gathered, self.T, self.n_cam, t0=t0, stride_t=st, stride_c=sc,
-                                                      P=self.max_points, out=self.out, **self.vis_params)
+                                                      P=self.max_points, out=self.out, points=points, **self.vis_params)
         elif self.world == 1:
             self.out = ctx.correspond_records(gathered, self.T, self.n_cam, t0=0, stride_t=self.n_cam, stride_c=1,
-                                              P=self.max_points, max_groups=self.max_groups, out=self.out)
+                                              P=self.max_points, max_groups=self.max_groups, out=self.out, points=points)
         else:
             self.out = ctx.correspond_records(gathered, self.T, self.n_cam, t0=self.rank * self.T, stride_t=1,
                                               stride_c=self.t_total, P=self.max_points, max_groups=self.max_groups,
                                               out=self.out)
+        if self.subpixel:
+            self.out["subpix_flags"] = self._cur.subpix["flags"]
         return self.out
 
     def track_ids(self, out, steps=None):

@@ -38,7 +38,7 @@ class ReplayTracker:
 
     def __init__(self, K, dist, R, t, F, width, height, batch=64, obj_count=OBJ_COUNT, device=0, max_points=32,
                  max_groups=4096, bayer_pattern=None, gray_shift=GRAY_SHIFT, depth=1, visibility="all", min_views=2, gate=10.0,
-                 max_err=25.0, max_passes=3, cutoff=10.0, max_hyp=8192, track=None):
+                 max_err=25.0, max_passes=3, cutoff=10.0, max_hyp=8192, track=None, subpixel=None):
         """visibility="any" (BatchTracker's): a time step yields the markers at least min_views cameras see, found from any
         camera pair, in acceptance order (more views first, then smaller error) -- the first obj_count + 1 of them as
         object_points, image_points [markers, C, 2] float64 with NaN where a camera does not see the marker; F may be None.
@@ -47,7 +47,9 @@ class ReplayTracker:
         come out in order either way.
         track (BatchTracker's): marker identities across time steps and batches; the dicts of run_batches and run gain `ids` and
         `ages`, row for row beside object_points (-1 = the row's marker got no track).  The black frames that pad the last batch
-        are not walked: they do not age the tracks.  The messages stay as they are."""
+        are not walked: they do not age the tracks.  The messages stay as they are.
+        subpixel (BatchTracker's): {"radius": r, "floor": f, "iters": 3} -- the object points are triangulated from sub-pixel image
+        points; image_points keep their integer form (visibility="any": the records' centroids; "all": the refined points, truncated)."""
         self.n_cam = len(K)
         self.batch = int(batch)
         self.obj_count = obj_count
@@ -56,7 +58,7 @@ class ReplayTracker:
         self.tracker = BatchTracker(K, dist, R, t, F, width, height, self.batch, device=device, max_points=max_points,
                                     max_groups=max_groups, bayer_pattern=bayer_pattern, gray_shift=gray_shift, depth=self.depth,
                                     visibility=visibility, min_views=min_views, gate=gate, max_err=max_err, max_passes=max_passes,
-                                    cutoff=cutoff, max_hyp=max_hyp, track=track)
+                                    cutoff=cutoff, max_hyp=max_hyp, track=track, subpixel=subpixel)
         self.visibility = visibility
         self.tracked = track is not None
         self.point = [0, 0, 0, 0, 0, 0, 0, 0]  # RealtimeTracking_FLIR.py:171 (eight zeros until the first detection)

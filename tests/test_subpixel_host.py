@@ -1,0 +1,191 @@
+"""Sub-pixel centroids without a GPU: the restatement's own properties on hand-made images (tests/subpixel_ref.py is what the
+device is held to, so it has to be right by itself), the new symbol in header and binding, the kernel's code object, the
+tracker's argument checks, and how close the refined points come to the true projected centres of rendered markers."""
+import os
+import re
+import sys
+
+import numpy as np
+import pytest
+
+import oracle
+import lens_cases
+import subpixel_ref as ref
+from mocapv2_amd import _abi, synth
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LENS_K = lens_cases._off_centre(640, 480, 1.0, 1.0, 0.04, -0.03)  # barrel_k123's recipe on the 480-row frame
+LENS_D = lens_cases.case("barrel_k123").dist
+
+
+def blob(H, W, cx, cy, half=2, peak=255, base=0):
+    """a (2 half + 1)^2 pyramid, symmetric about (cx, cy)"""
+    img = np.full((H, W), base, np.uint8)
+    for y in range(cy - half, cy + half + 1):
+        for x in range(cx - half, cx + half + 1):
+            img[y, x] = max(base, peak - 40 * max(abs(x - cx), abs(y - cy)))
+    return img
+
+
+# ---- the restatement on hand-made images ------------------------------------------------------------------------------
+def test_symmetric_blobs_give_exact_centres():
+    img = blob(40, 50, 20, 15)
+    for start in ((20, 15), (22, 14), (18, 17)):
+        xy, S, fl = ref.refine_image(img, [start], radius=6, floor=10)
+        assert xy.tolist() == [[20.0, 15.0]] and fl.tolist() == [0] and S[0] == int(np.maximum(img.astype(int) - 10, 0).sum())
+    S0 = int(S[0])
+    img[15, 20 + 3] = 255  # one more pixel, 3 to the right of the centre: x0 = 14, Sx = 6 S0 + 9 w, the row stays
+    xy, S, fl = ref.refine_image(img, [(20, 15)], radius=6, floor=10)
+    assert S[0] == S0 + 245 and fl[0] == 0 and xy[0, 1] == 15.0
+    assert xy[0, 0] == np.float64(14) + np.float64(6 * S0 + 9 * 245) / np.float64(S0 + 245) and 20.0 < xy[0, 0] < 20.5
+
+
+def test_every_flag_from_the_smallest_image_that_raises_it():
+    one = np.full((1, 1), 64, np.uint8)
+    xy, S, fl = ref.refine_image(one, [(0, 0)], radius=1, floor=64)
+    assert fl[0] == ref.EMPTY | ref.CUT and S[0] == 0 and xy.tolist() == [[0.0, 0.0]]  # p - floor = 0 everywhere
+    xy, S, fl = ref.refine_image(one, [(0, 0)], radius=1, floor=63)
+    assert fl[0] == ref.CUT and S[0] == 1 and xy.tolist() == [[0.0, 0.0]]              # CUT alone does not fall back
+    three = np.zeros((3, 3), np.uint8)
+    three[1, 1] = 200
+    assert ref.refine_image(three, [(1, 1)], radius=1, floor=0)[2].tolist() == [0]   # the window is the image: not cut
+    three[0, 1] = three[2, 1] = 1                                                      # ring pixels, balanced: the centre stays
+    xy, S, fl = ref.refine_image(three, [(1, 1)], radius=1, floor=0)
+    assert fl[0] == ref.EDGE and S[0] == 202 and xy.tolist() == [[1.0, 1.0]]
+    assert ref.refine_image(three, [(1, 1)], radius=1, floor=1)[2].tolist() == [0]   # ... and invisible under the floor
+    two = np.zeros((5, 5), np.uint8)  # (at radius 1 every pixel but the centre is ring: MOVING alone needs radius 2)
+    two[2, 2] = two[2, 3] = 9
+    xy, S, fl = ref.refine_image(two, [(2, 2)], radius=2, floor=0, iters=1)            # mean 2.5 -> pixel 3: wants to move
+    assert fl[0] == ref.MOVING and S[0] == 18 and xy.tolist() == [[2.0, 2.0]]
+    xy, S, fl = ref.refine_image(two, [(2, 2)], radius=2, floor=0, iters=2)            # the second window stays at 3, cut by the border
+    assert fl[0] == ref.CUT and xy.tolist() == [[2.5, 2.0]]
+    pair = np.zeros((3, 5), np.uint8)
+    pair[1, 1] = 50
+    xy, S, fl = ref.refine_image(pair, [(1, 1), (2, 1), (3, 1)], radius=1, floor=0)
+    assert fl.tolist() == [ref.NEIGHBOUR, ref.NEIGHBOUR, ref.EMPTY | ref.NEIGHBOUR]    # (2,1) recentres on (1,1); (3,1) sees nothing
+    assert S.tolist() == [50, 50, 0] and xy.tolist() == [[1.0, 1.0], [2.0, 1.0], [3.0, 1.0]]
+    xy, S, fl = ref.refine_image(pair, [(1, 1), (3, 1)], radius=1, floor=0)           # start pixels 2 apart: outside each other's window
+    assert fl.tolist() == [0, ref.EMPTY]
+
+
+def test_recentring_and_the_iteration_limit():
+    img = blob(60, 60, 30, 30, half=3)
+    for iters, flags in ((1, ref.MOVING), (2, 0), (8, 0)):  # 5 px off: the first window sees the whole blob, the second is centred
+        xy, _, fl = ref.refine_image(img, [(35, 27)], radius=9, floor=0, iters=iters)
+        assert fl[0] == flags and xy.tolist() == ([[30.0, 30.0]] if not flags else [[35.0, 27.0]])
+
+
+def test_fallback_values_are_exact_in_both_coordinates():
+    img = np.zeros((480, 640), np.uint8)
+    pts = [(100, 90), (500, 400)]
+    U = [ref.distort_pt(LENS_K, LENS_D, *p) for p in pts]
+    xy1, _, fl = ref.refine_image(img, pts, 5, 0, K=LENS_K, dist=LENS_D, identity=False, coords=1)
+    xy0, _, _ = ref.refine_image(img, pts, 5, 0, K=LENS_K, dist=LENS_D, identity=False, coords=0)
+    assert fl.tolist() == [ref.EMPTY] * 2
+    assert xy1.tolist() == [[100.0, 90.0], [500.0, 400.0]] and xy0.tolist() == [list(map(float, u)) for u in U]
+    assert max(abs(u[0] - p[0]) + abs(u[1] - p[1]) for u, p in zip(U, pts)) > 2  # the lens does move these points
+    # near the principal point the five rounds invert the forward model to far below a pixel's thousandth (at (100, 90), where
+    # this lens moves a point by 30 px, they leave 0.012 px: that is cv.undistortPoints' own accuracy, and the definition's)
+    back = ref.undistort_pt(LENS_K, LENS_D, *ref.distort_pt(LENS_K, LENS_D, 400, 260))
+    assert abs(back[0] - 400) < 1e-6 and abs(back[1] - 260) < 1e-6
+    # an identity slot: coords makes no difference to the bits
+    img = blob(40, 40, 20, 20)
+    img[20, 22] += 3
+    a = ref.refine_image(img, [(20, 20)], 6, 0, coords=0)
+    b = ref.refine_image(img, [(20, 20)], 6, 0, coords=1)
+    assert a[0].tobytes() == b[0].tobytes() and a[2].tolist() == [0]
+
+
+# ---- the symbol, the kernel, the tracker's arguments -------------------------------------------------------------------
+def test_header_and_binding_arity():
+    text = open(os.path.join(ROOT, "include", "mocap_hip.h")).read()
+    m = re.search(r"MOCAP_API\s+int\s+mocap_refine_centroids\s*\(([^;]*)\)\s*;", text)
+    assert m, "mocap_refine_centroids is not declared"
+    assert len(m.group(1).split(",")) == len(_abi.SIGNATURES["mocap_refine_centroids"]) == 23
+    assert re.search(r"#define\s+MOCAP_ABI_VERSION\s+7\b", text) and _abi.ABI_VERSION == 7
+    bits = dict(re.findall(r"MOCAP_SUBPIX_(\w+)\s*=\s*(\d+)", text))
+    assert {k: int(v) for k, v in bits.items()} == {"EMPTY": ref.EMPTY, "EDGE": ref.EDGE, "NEIGHBOUR": ref.NEIGHBOUR,
+                                                    "MOVING": ref.MOVING, "CUT": ref.CUT}
+    from mocapv2_amd import engine
+    assert (engine.SUBPIX_EMPTY, engine.SUBPIX_EDGE, engine.SUBPIX_NEIGHBOUR, engine.SUBPIX_MOVING, engine.SUBPIX_CUT) == \
+        (ref.EMPTY, ref.EDGE, ref.NEIGHBOUR, ref.MOVING, ref.CUT) and engine.SUBPIX_FALLBACK == ref.FALLBACK
+
+
+def test_kernel_uses_no_scratch_memory():
+    """The compiler's own metadata for subpixel.hip (scratch/kernel_meta.py, no GPU needed): exactly one kernel, 0 bytes of scratch,
+    0 spilled VGPRs."""
+    sys.path.insert(0, os.path.join(ROOT, "scratch"))
+    import kernel_meta as km
+    ks = km.kernels_of(os.path.join(km.CSRC, "subpixel.hip"))
+    assert len(ks) == 1 and "refine_centroids_kernel" in ks[0]["name"], ks
+    assert ks[0]["scratch"] == 0 and ks[0]["spill"] == 0 and ks[0]["wg"] == 256, ks[0]
+    assert "subpixel.hip" in open(os.path.join(km.CSRC, "Makefile")).read()
+
+
+def test_batch_tracker_refuses_bad_subpixel_arguments():
+    from mocapv2_amd.pipeline import BatchTracker, scene_arrays
+    from mocapv2_amd.replay import ReplayTracker
+    K, dist, R, t, F = scene_arrays(synth.Scene(2, 64, 48))
+    for bad in ({"radius": 5}, {"floor": 64}, {"radius": 5, "floor": 64, "sigma": 1.0}, {}):
+        with pytest.raises(ValueError, match="subpixel"):
+            BatchTracker(K, dist, R, t, F, 64, 48, 1, subpixel=bad)
+        with pytest.raises(ValueError, match="subpixel"):
+            ReplayTracker(K, dist, R, t, F, 64, 48, batch=1, subpixel=bad)
+    with pytest.raises(ValueError, match="world == 1"):
+        BatchTracker(K, dist, R, t, F, 64, 48, 1, world=2, rank=0, subpixel={"radius": 5, "floor": 64})
+
+
+# ---- accuracy ----------------------------------------------------------------------------------------------------------
+RADIUS, FLOOR = 22, 64
+# The blob oracle with its defaults but min_area 400: at the default 500 it drops the discs of radius 14 .. 14.x (measured: a disc
+# of radius 14 is dropped, one of 15 is kept), and the accuracy of a refined point does not depend on that gate.
+BLOB_PARAMS = oracle.default_params(undistort=True)
+BLOB_PARAMS.min_area = 400.0
+BOUND = 0.0295  # px: twice the largest error measured, see test_refined_points_lie_near_the_true_centres
+
+
+def accuracy_errors(dist, K=None):
+    """(errors of the refined points in ideal pixels, in raw pixels, errors of the integer centroids, flags) over 3 seeds x 3
+    cameras x 6 markers"""
+    scene = synth.Scene(3, 640, 480, dist=dist)
+    if K is not None:
+        scene.K = np.array(K, float)
+    identity = not np.any(np.asarray(dist))
+    e_ideal, e_raw, e_int, flags = [], [], [], []
+    for seed in (11, 12, 13):
+        rng = np.random.default_rng(seed)
+        markers = ref.place_markers(scene, rng, 6, margin=RADIUS + 20, apart=2 * RADIUS + 2)
+        for cam in range(3):
+            truth = {d: scene.pixels(markers, cam, distorted=d) for d in (True, False)}
+            for d in (True, False):  # the placement the issue asks for, checked here: no two projections within 2 r
+                diff = np.abs(truth[d][:, None] - truth[d][None]).max(axis=2) + 1e9 * np.eye(len(markers))
+                assert diff.min() > 2 * RADIUS
+            frame = scene.render(rng, markers, cam, radius_range=(14.0, 16.0))
+            pts = np.array(oracle.find_dot(frame, scene.K, scene.dist, params=BLOB_PARAMS))
+            assert len(pts) == len(markers)
+            order = [int(np.abs(pts - t).sum(axis=1).argmin()) for t in truth[False]]
+            assert sorted(order) == list(range(len(markers)))
+            pts = pts[order]
+            for coords, err in ((1, e_ideal), (0, e_raw)):
+                xy, _, fl = ref.refine_image(frame, pts, RADIUS, FLOOR, 3, scene.K, scene.dist, identity, coords)
+                err.extend(np.hypot(*(xy - truth[coords == 0]).T))
+                flags.extend(fl)
+            e_int.extend(np.hypot(*(pts - truth[False]).T))
+    return np.array(e_ideal), np.array(e_raw), np.array(e_int), np.array(flags)
+
+
+@pytest.mark.parametrize("lens", ["identity", "barrel_k123"])
+def test_refined_points_lie_near_the_true_centres(lens):
+    """Rendered discs (synth.Scene.render: radii 14..16, noise 0..60) at 640 x 480, integer centroids from the blob oracle, refined
+    by the restatement with radius 22, floor 64: no point is flagged, every refined point lies within BOUND of Scene.pixels -- in
+    ideal pixels and, for the lens model, in raw pixels too -- and the integer centroids' mean error is at least five times the
+    refined points' largest.
+    Measured once (54 points per lens): largest refined error 0.01470 px (identity), 0.01252 px ideal / 0.01228 px raw
+    (barrel_k123); BOUND = 0.0295 is twice the largest, for the sub-pixel placements three seeds do not sample.  Integer
+    centroids: mean error 0.743 px (identity), 0.723 px (barrel_k123), largest 1.32 px."""
+    e_ideal, e_raw, e_int, flags = accuracy_errors(synth.ZERO_DIST) if lens == "identity" else accuracy_errors(LENS_D, LENS_K)
+    print(f"{lens}: refined max {e_ideal.max():.5f} (ideal) {e_raw.max():.5f} (raw) px, integer mean {e_int.mean():.4f} max {e_int.max():.4f} px")
+    assert BOUND < 0.1
+    assert not flags.any()
+    assert e_ideal.max() < BOUND and e_raw.max() < BOUND
+    assert e_int.mean() >= 5 * max(e_ideal.max(), e_raw.max())
