@@ -17,7 +17,7 @@ int mocap_correspond(mocap_ctx_t c, const void* pts, long pt_st, long pt_sc, con
     if (c->n_cam < C) return fail(MOCAP_E_STATE, "mocap_set_cameras: %d cameras set, %d needed", c->n_cam, C);
     if (c->n_F < C - 1) return fail(MOCAP_E_STATE, "mocap_set_fundamentals: %d matrices set, %d needed", c->n_F, C - 1);
     if (set_device(c)) return MOCAP_E_HIP;
-    if (!correspond_fits(P, C)) // the plan is adaptive (geom.hip: corr_lds_plan); what is left are the candidate lists, P * C * 16 bytes
+    if (!correspond_fits(P, C)) // the plan is adaptive (correspond.hip: corr_lds_plan); what is left are the candidate lists, P * C * 16 bytes
         return fail(MOCAP_E_UNSUPPORTED, "P=%d points x C=%d cameras needs %zu bytes of LDS per time step", P, C, correspond_smem_bytes(P, C));
     // error scratch: the groups of one time step lie back to back, so a step needs room for its total, not P x max_groups;
     // a step with more than max(2 * max_groups, 8192) groups in all reports MOCAP_CORR_E_GROUPS

@@ -9,7 +9,7 @@ namespace mocap {
 __device__ __forceinline__ constexpr int sym9(int i, int j) { return i <= j ? i * 9 - i * (i - 1) / 2 + (j - i) : j * 9 - j * (j - 1) / 2 + (i - j); }
 
 // B: the 45 unique entries of the matrix (sym9's order); overwritten.  f: the eigenvector.
-// Cyclic Jacobi with the eigenvector matrix, the rotations of smallest_eigvec4 in geom.hip.  Every loop over matrix indices is
+// Cyclic Jacobi with the eigenvector matrix, the rotations of smallest_eigvec4 in geom_dev.h.  Every loop over matrix indices is
 // unrolled, so every index is a constant: B stays in registers, and with it everything a rotation's angle depends on.  The
 // eigenvector matrix V (81 doubles) is only ever updated, never looked at before the end: it lives in LDS at V[(9 i + j) * st],
 // st = 64 with one problem per lane ([element][lane]: the lanes of a wave never share a bank), st = 1 for a single solve; its

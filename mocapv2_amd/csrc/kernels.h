@@ -561,6 +561,8 @@ void launch_refine_centroids(const RefineArgs& a, hipStream_t s);
 
 void launch_fundamental_ransac(const FundArgs& a, hipStream_t s);
 
+enum { LDS_USER_CORRESPOND, LDS_USER_VISIBLE, LDS_USERS };
+int workgroup_lds_limit(int user, const void* kernel_f64, const void* kernel_i32); // correspond.hip: bytes of dynamic LDS per workgroup
 void launch_correspond(const CorrArgs& a, hipStream_t s);
 size_t correspond_smem_bytes(int P, int C);
 bool correspond_fits(int P, int C); // the kernel's LDS plan for P points x C cameras fits a workgroup

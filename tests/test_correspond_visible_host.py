@@ -4,6 +4,8 @@ the code-object table of the new kernel."""
 import ctypes
 import importlib.util
 import os
+import re
+import subprocess
 
 import numpy as np
 import pytest
@@ -138,12 +140,18 @@ def test_abi_declares_the_entry_point_and_its_status_code():
 
 def test_new_kernel_uses_no_scratch_memory_and_spills_nothing():
     """The compiler's own metadata for correspond_visible.hip (scratch/kernel_meta.py, no GPU needed): 0 bytes of scratch and 0
-    spilled VGPRs, as for every geometry kernel -- and geom.hip's kernels keep theirs after the helpers moved to geom_dev.h."""
+    spilled VGPRs, as for every geometry kernel -- and the seven kernels that were geom.hip's (correspond.hip, geom_batch.hip,
+    ba_residuals.hip: exactly those seven) keep theirs with the helpers in geom_dev.h."""
     spec = importlib.util.spec_from_file_location("kernel_meta", os.path.join(ROOT, "scratch", "kernel_meta.py"))
     km = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(km)
     ks = km.kernels_of(os.path.join(km.CSRC, "correspond_visible.hip"))
     assert len(ks) == 2 and all("correspond_visible_kernel" in k["name"] for k in ks)  # the float64 and the int32 points
-    for k in ks + km.kernels_of(os.path.join(km.CSRC, "geom.hip")):
+    geom = [k for f in ("correspond.hip", "geom_batch.hip", "ba_residuals.hip") for k in km.kernels_of(os.path.join(km.CSRC, f))]
+    plain = subprocess.run([km.FILT], input="\n".join(k["name"] for k in geom), capture_output=True, text=True, check=True).stdout.split("\n")
+    short = sorted(re.sub(r"^void |mocap::|\(.*\)$", "", nm) for nm in plain if nm)
+    assert short == ["ba_residuals_kernel", "correspond_kernel<double>", "correspond_kernel<int>", "epipolar_scores_kernel<double>",
+                     "epipolar_scores_kernel<int>", "reproject_kernel", "triangulate_kernel"], short
+    for k in ks + geom:
         print(k)
         assert k["scratch"] == 0 and k["spill"] == 0, k

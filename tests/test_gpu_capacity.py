@@ -293,9 +293,9 @@ def perm(seq, seed):
     return [seq[i] for i in np.random.default_rng(seed).permutation(len(seq))]
 
 
-@pytest.mark.parametrize("threads", [64, 256])
+@pytest.mark.parametrize("threads", [64, 128, 256])
 def test_sixteen_candidates_per_root_and_camera_fit_and_the_seventeenth_does_not(threads):
-    """MAXM = 16 (csrc/geom.hip): a root with 16 candidates within the cutoff in camera 1 is answered like the oracle; a 17th
+    """MAXM = 16 (csrc/correspond.hip): a root with 16 candidates within the cutoff in camera 1 is answered like the oracle; a 17th
     within the cutoff gives MOCAP_CORR_E_GROUPS; a 17th at distance == cutoff (not < cutoff), first or last in the camera's
     list, is no candidate and changes nothing but the indices."""
     rig = rectified_rig(2)
@@ -318,7 +318,7 @@ def three_camera_step():
             .root(800.0, [perm(DYS[:10], 6), perm(DYS[:13], 7)]))
 
 
-@pytest.mark.parametrize("threads", [64, 256])
+@pytest.mark.parametrize("threads", [64, 128, 256])
 def test_max_groups_is_reached_exactly_and_exceeded_by_one(threads):
     rig = rectified_rig(3)
     pts, cnt = pack_steps([three_camera_step()], 48)
@@ -333,7 +333,7 @@ def test_max_groups_is_reached_exactly_and_exceeded_by_one(threads):
     assert correspond(ctx, pts2, cnt2, max_groups=129)["n"].tolist() == [-2]
 
 
-@pytest.mark.parametrize("threads", [64, 256])
+@pytest.mark.parametrize("threads", [64, 128, 256])
 def test_the_step_budget_is_reached_exactly_and_exceeded_by_one(threads):
     """corr_step_groups = n: a time step of exactly n groups is answered, n - 1 gives MOCAP_CORR_E_GROUPS -- with 1024 groups
     (the per-group errors' last size in LDS) and with 1025 (their first in the context's scratch array; the second time step, so
@@ -355,3 +355,47 @@ def test_the_step_budget_is_reached_exactly_and_exceeded_by_one(threads):
         for s, n in enumerate(n_exp):
             if n > 0:
                 assert_step_equals_oracle(out, s, pts, cnt, rig, n)
+
+
+def dead_root_steps():
+    """C = 3, P = 8, T = 2.  Step 0: three roots, the middle one with two candidates in camera 1 and none within the cutoff in
+    camera 2 (no group: a dead root between two roots of 2 x 1 and 1 x 2 groups, which shares its offset in the flat group index
+    with the root behind it).  Step 1: camera 0 has no points at all, cameras 1 and 2 have.  Every coordinate is an integer, so the
+    same lists go in as int32 and as float64."""
+    first = Step(3).root(200.0, [[0.0, 2.0], [-2.0]]).root(500.0, [[2.0, 0.0], []]).root(800.0, [[4.0], [0.0, -2.0]])
+    second = Step(3).root(300.0, [[0.0, 2.0], [2.0]]).root(700.0, [[-2.0], [0.0]])
+    pts, cnt = pack_steps([first, second], 8)
+    cnt[1, 0] = 0
+    assert cnt.tolist() == [[3, 5, 3], [0, 3, 2]] and np.array_equal(pts, np.round(pts))
+    return pts, cnt
+
+
+@pytest.mark.parametrize("dtype", [np.int32, np.float64], ids=["int32", "float64"])
+@pytest.mark.parametrize("threads", [64, 128, 256])
+def test_a_dead_root_between_live_roots_and_a_step_without_roots(threads, dtype):
+    """The oracle answers roots 0 and 2 for the first step (on the CPU, before anything runs on the GPU) and nothing for the second;
+    the kernel equals it as test_batched_correspond_matches_oracle asks (integers equal, xyz to 1e-7), from the dense array and --
+    the int32 points -- from camera-major records [C, 3, rec] whose time steps 1 and 2 are these two (t0 = 1; time step 0 of the
+    records holds a negative count, which would fail a step that read it)."""
+    import torch
+    rig = rectified_rig(3)
+    pts, cnt = dead_root_steps()
+    refs = [oracle.correspond(pts[s], cnt[s], *rig) for s in range(2)]
+    assert refs[0]["root"].tolist() == [0, 2] and len(refs[1]["root"]) == 0
+    ctx = rig_context(rig, threads)
+    outs = [correspond(ctx, pts.astype(dtype), cnt)]
+    if dtype is np.int32:
+        T, C, P = pts.shape[:3]
+        records = np.zeros((C, T + 1, 2 + 2 * P), np.int32)
+        records[:, 0, 0] = -1
+        records[:, 1:, 0] = cnt.T
+        records[:, 1:, 2:] = pts.transpose(1, 0, 2, 3).reshape(C, T, 2 * P)
+        out = ctx.correspond_records(torch.from_numpy(records).cuda(), T, C, t0=1, stride_t=1, stride_c=T + 1, P=P)
+        outs.append({k: v.cpu().numpy() for k, v in out.items()})
+    for out in outs:
+        assert out["n"].tolist() == [2, 0]
+        ref = refs[0]
+        assert np.array_equal(out["root"][0, :2], ref["root"]) and np.array_equal(out["grp"][0, :2], ref["groups"])
+        assert np.array_equal(out["order"][0, :2], ref["order"])
+        assert np.abs(out["xyz"][0, :2] - ref["xyz"]).max() < 1e-7
+        assert np.allclose(out["err"][0, :2], ref["err"], rtol=1e-9, atol=1e-12)

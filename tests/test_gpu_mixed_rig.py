@@ -1,6 +1,6 @@
 """The geometry and solver kernels on rigs whose cameras all differ in K and lens (mocapv2_amd.synth.MixedScene,
 tests/mixed_rig.py).  Everywhere else in the suite the cameras of a rig share one K and one lens, so a read of the wrong
-camera's row -- csrc/geom.hip's 38-double LDS row per camera, its `ki = compact_k ? m : c`, csrc/rig_ba.hip's Lens per
+camera's row -- csrc/correspond_dev.h's 38-double LDS row per camera, csrc/geom_batch.hip's `ki = compact_k ? m : c`, csrc/rig_ba.hip's Lens per
 observation, calibrate.py's K[a] / K[b] over tree edges, BatchTracker's slot_of[c] -- changes nothing there.  Here it does, and
 the correspondence test measures by how much (CPU oracle) before it compares.  Yardsticks: the reference's own outputs
 (tests/golden/*_mixed*.npz, oracle/gen_golden.py mixed), the CPU oracle, NumPy restatements.  Tolerances are the ones the
