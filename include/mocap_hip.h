@@ -47,6 +47,12 @@ enum {
     MOCAP_TRACK_E_IDS = -3,       /* the identity counter stands at INT32_MAX: no new marker gets an identity (the counter never wraps) */
     MOCAP_TRACK_E_INPUT = -4,     /* a blind step: its count n[t] is negative (the correspondence's own failure code) */
     MOCAP_TRACK_E_COUNT = -5,     /* a blind step: its count n[t] exceeds 256 or the Q rows of a step */
+    MOCAP_RIGID_LOST = 1,         /* mocap_rigid_poses, status[t][b]: no candidate reached min_markers inliers (not an error) */
+    MOCAP_RIGID_E_BLIND = -2,     /* a blind step: its count n[t] is negative (the correspondence's own failure code) */
+    MOCAP_RIGID_E_CAPACITY = -3,  /* a blind step: its count n[t] exceeds 64 or the Q rows of a step */
+    MOCAP_RIGID_E_MODEL = -4,     /* the body's tables are not a model: n_markers outside 3..8, n_tri outside 1..56, or a triple
+                                     that is not 0 <= a < b < c < n_markers */
+    MOCAP_RIGID_E_HYP = -5,       /* more than max_hyp candidates for the body in the step: it has no result there */
     MOCAP_FUND_E_SAMPLE = -2,     /* mocap_fundamental_ransac: a sample index outside its pair's point list */
     MOCAP_FUND_E_DEGENERATE = -3  /* no valid hypothesis (e.g. coincident points), a winner with fewer than 8 inliers, or
                                      inliers that do not span a model in the refit */
@@ -317,6 +323,45 @@ MOCAP_API int mocap_track_markers(mocap_ctx_t ctx, const double* xyz_dev /*[T][Q
                                   int T, int Q, void* state_dev, int max_tracks, double gate, double beta, int max_miss,
                                   int32_t* id_dev, int32_t* slot_dev, int32_t* age_dev /*[T][Q] each*/, int32_t* status_dev /*[T]*/,
                                   void* stream);
+
+/* Rigid-body poses (6-DoF) per time step.  Each of B bodies -- 3 to 8 model points in the body's own frame -- is searched among the
+ * unlabelled 3-D detections of every one of T time steps; every (time step, body) is independent (one workgroup each), the call is
+ * stateless and neither needs nor changes the tracker.  The reference has no counterpart (nothing optical ever fills the four
+ * orientation slots of its {"tracker1": [0, 0, 0, 0, x, y, z]} message): the contract is the definition of DESIGN.md section 2,
+ * restated by tests/rigid_ref.py -- FP64 throughout, + - * / and sqrt only, every operation rounded on its own, so the device
+ * equals the restatement bit for bit.  New symbol, MOCAP_ABI_VERSION stays 7.
+ * Per (step, body): a model triple h = (a, b, c) with an ordered triple (i, j, k) of distinct detections is a candidate when
+ * |d_ij - L_ab|, |d_jk - L_bc| and |d_ik - L_ac| are all below tol; each candidate is posed by Horn's closed-form quaternion from
+ * its three pairs; the model points, in ascending order, take the nearest unclaimed detection within gate of where the pose puts
+ * them (ties: the lower row); with at least min_markers such inliers the pose is refitted once over all of them (no re-labelling)
+ * and rms^2 is the mean squared distance after the refit; the result is the candidate smallest in the total order (more inliers,
+ * smaller rms^2, h, i, j, k).  Bodies do not know of each other: two bodies may claim the same detection.
+ *   xyz_dev       float64 [T][Q][3]  detections (mocap_correspond_visible's xyz_dev as it is); rows at and beyond n_dev[t] take no
+ *                                    part and may hold any bytes; the rows below it must be finite
+ *   n_dev         int32 [T]          detections of the step.  Negative (MOCAP_CORR_E_*): MOCAP_RIGID_E_BLIND for every body; above
+ *                                    min(Q, 64): MOCAP_RIGID_E_CAPACITY for every body
+ *   model_dev     float64 [B][8][3]  model points, the first n_markers_dev[b] (3..8) of each body
+ *   tri_dev       int32 [B][56][3]   model triples a < b < c, the first n_tri_dev[b] (1..56) of each body: the caller lists those
+ *                                    whose triangle is not degenerate
+ *   tol, gate     finite and > 0 (world units);  min_markers 3..8;  max_hyp 1..4096: more candidates are MOCAP_RIGID_E_HYP for
+ *                 that body in that step -- the list is never shortened -- and leave the other bodies and steps as they are
+ *   R_dev [T][B][9] (row-major, D = R m + t), t_dev [T][B][3], q_dev [T][B][4] (w, x, y, z; unit, first non-zero component
+ *   positive), rms_dev [T][B], n_in_dev int32 [T][B], label_dev int32 [T][B][8] (the detection row of each model point or -1; -1
+ *   from n_markers on), status_dev int32 [T][B]: 0, MOCAP_RIGID_LOST or MOCAP_RIGID_E_*.  On any status other than 0, n_in is 0,
+ *   the labels are -1, and the floats are unspecified and must not be read.
+ * T = 0 or B = 0 is a no-op.  Bad arguments (B above 16 among them) are MOCAP_E_INVALID and launch nothing.  Asynchronous on
+ * `stream`.  No floating-point atomics, and the winner does not depend on the order the lanes found the candidates in: the same
+ * call gives the same bits. */
+#define MOCAP_RIGID_MAX_DETECTIONS 64
+#define MOCAP_RIGID_MAX_MARKERS 8
+#define MOCAP_RIGID_MAX_TRIPLES 56
+#define MOCAP_RIGID_MAX_BODIES 16
+#define MOCAP_RIGID_MAX_HYP 4096
+MOCAP_API int mocap_rigid_poses(mocap_ctx_t ctx, const double* xyz_dev /*[T][Q][3]*/, const int32_t* n_dev /*[T]*/, int T, int Q,
+                                int B, const double* model_dev /*[B][8][3]*/, const int32_t* n_markers_dev /*[B]*/,
+                                const int32_t* tri_dev /*[B][56][3]*/, const int32_t* n_tri_dev /*[B]*/, double tol, double gate,
+                                int min_markers, int max_hyp, double* R_dev, double* t_dev, double* q_dev, double* rms_dev,
+                                int32_t* n_in_dev, int32_t* label_dev, int32_t* status_dev, void* stream);
 
 /* The scoring step of find_point_correspondance_and_object_points on its own (lib/Helpers.py:205-220), for one camera
  * pair: the epipolar line of every root point under Fs[f_index] (cv.computeCorrespondEpilines on the float32 point, :207;

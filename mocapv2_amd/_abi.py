@@ -61,6 +61,7 @@ SIGNATURES = {
     "mocap_correspond_visible": [_vp, _vp, _l, _l, _vp, _l, _l, _i, _i, _i, _i, _i, _d, _d, _i, _d, _i, _i, _i, _vp, _vp, _vp, _vp,
                                  _vp, _vp],
     "mocap_track_markers": [_vp, _vp, _vp, _i, _i, _vp, _i, _d, _d, _i, _vp, _vp, _vp, _vp, _vp],
+    "mocap_rigid_poses": [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _d, _d, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "mocap_epipolar_scores": [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp],
     "mocap_ba_residuals": [_vp, _dp, _i, _vp, _vp, _i, _i, C.POINTER(C.c_float), _ip, _vp],
     "mocap_fundamental_ransac": [_vp, _i, _vp, _vp, _ip, _vp, _i, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp],

@@ -541,6 +541,33 @@ struct TrackArgs {
 };
 void launch_track_markers(const TrackArgs& a, hipStream_t s);
 
+// rigid-body poses per time step (rigid.hip).  The codes and caps are include/mocap_hip.h's MOCAP_RIGID_*.
+enum { RIGID_LOST = 1, RIGID_ERR_BLIND = -2, RIGID_ERR_CAPACITY = -3, RIGID_ERR_MODEL = -4, RIGID_ERR_HYP = -5 };
+constexpr int RIGID_MAX_DET = 64;      // detections of a time step
+constexpr int RIGID_MAX_MARKERS = 8;   // model points of a body
+constexpr int RIGID_MAX_TRIPLES = 56;  // model triples of a body: C(8, 3)
+constexpr int RIGID_MAX_BODIES = 16;
+constexpr int RIGID_MAX_HYP = 4096;    // candidates of one (time step, body): the LDS list's entries
+struct RigidArgs {
+    const double* xyz;         // [T][Q][3] detections; rows at and beyond n[t] take no part
+    const int32_t* n;          // [T] detections of the step; < 0 or > min(Q, 64): a blind step
+    int T, Q, B;
+    const double* model;       // [B][8][3]
+    const int32_t* n_markers;  // [B] 3..8
+    const int32_t* tri;        // [B][56][3] model triples a < b < c
+    const int32_t* n_tri;      // [B] 1..56
+    double tol, gate;
+    int min_markers, max_hyp;
+    double* R;                 // [T][B][9]
+    double* t;                 // [T][B][3]
+    double* q;                 // [T][B][4] (w, x, y, z)
+    double* rms;               // [T][B]
+    int32_t* n_in;             // [T][B]
+    int32_t* label;            // [T][B][8] detection row or -1
+    int32_t* status;           // [T][B] 0, RIGID_LOST or RIGID_ERR_*
+};
+void launch_rigid_poses(const RigidArgs& a, hipStream_t s);
+
 // sub-pixel centroids from the frames (subpixel.hip): the flag bits are include/mocap_hip.h's MOCAP_SUBPIX_*
 enum { SUBPIX_EMPTY = 1, SUBPIX_EDGE = 2, SUBPIX_NEIGHBOUR = 4, SUBPIX_MOVING = 8, SUBPIX_CUT = 16 };
 constexpr int SUBPIX_MAX_BLOBS = 256; // centroids of one image at most: one per thread of its workgroup

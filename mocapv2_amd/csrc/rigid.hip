@@ -1,0 +1,293 @@
+// rigid.hip -- rigid-body poses per time step: each of B bodies (3 to 8 model points) is searched among a step's unlabelled 3-D
+// detections by distance-matched triples, posed by Horn's closed-form quaternion, labelled, refitted once and scored (FP64).
+//
+// The reference has no counterpart (the four orientation slots of its {"tracker1": [0, 0, 0, 0, x, y, z]} message are never
+// filled by anything optical): the contract is the definition of DESIGN.md section 2, restated by tests/rigid_ref.py.  The library
+// is built with -ffp-contract=off: every sum and product below is a separately rounded FP64 operation, in the order the definition
+// gives, so the device and the restatement agree bit for bit.
+//
+// Work decomposition: every (time step, body) is independent, so the grid is T x B workgroups of 256 threads.  A workgroup keeps in
+// LDS the step's detections with their 64 x 64 distance table (32 KB), the body's model with its table and triples, and the
+// candidate list (32-bit entries: 6 bits each for h, i, j, k).  Phases: (a) load and build the tables; (b) lanes stride over
+// (h, i, j), test the first distance and scan k, appending matches through an LDS integer counter -- the list's order is whatever
+// the lanes made it, and nothing below depends on it; (c) lanes stride over the candidates and solve, label, refit and score each,
+// keeping their best key; (d) a tree reduction of the key (more inliers, smaller rms^2, smaller (h, i, j, k)) -- a total order, so
+// the winner is the same whatever the list's order; (e) lane 0 solves the winner once more (the same operations, the same bits:
+// nothing but a key travels through the reduction) and writes it.  No floating-point atomics: the same call gives the same bits.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "kernels.h"
+#include "geom_dev.h"
+
+namespace mocap {
+
+namespace {
+
+constexpr int THREADS = 256;
+constexpr int DS = RIGID_MAX_DET;        // row stride of the detections' distance table
+constexpr unsigned NO_LABEL = 0xffu;     // a model point without a detection, in the packed labels (one byte per model point)
+static_assert(RIGID_MAX_DET <= 64 && RIGID_MAX_TRIPLES <= 64, "a candidate packs h, i, j, k into 6 bits each");
+static_assert(RIGID_MAX_MARKERS == 8, "the labels of a body are the eight bytes of one 64-bit word");
+
+struct Pose { double R[9], t[3], q[4]; };
+struct Fit { Pose pose; unsigned long long lab; int n_in; double rms2; };
+
+__device__ __forceinline__ unsigned label_of(unsigned long long lab, int p) { return (unsigned)(lab >> (8 * p)) & 0xffu; }
+__device__ __forceinline__ unsigned long long with_label(unsigned long long lab, int p, unsigned l)
+{
+    return (lab & ~(0xffull << (8 * p))) | ((unsigned long long)l << (8 * p));
+}
+
+__device__ __forceinline__ double dist3(const double* a, const double* b)
+{
+    const double dx = a[0] - b[0], dy = a[1] - b[1], dz = a[2] - b[2];
+    return sqrt((dx * dx + dy * dy) + dz * dz);
+}
+
+// R m + t, each row ((R0 m0 + R1 m1) + R2 m2) + t
+__device__ __forceinline__ void transform(const Pose& o, const double* m, double out[3])
+{
+#pragma unroll
+    for (int u = 0; u < 3; u++) out[u] = ((o.R[3 * u] * m[0] + o.R[3 * u + 1] * m[1]) + o.R[3 * u + 2] * m[2]) + o.t[u];
+}
+
+// Horn's closed-form pose of the pairs (m_p, D_lab[p]) that have a label, in ascending p
+__device__ __forceinline__ void horn(const double* model, const double* det, unsigned long long lab, Pose& o)
+{
+    double cnt = 0., sm[3] = {0., 0., 0.}, sd[3] = {0., 0., 0.};
+#pragma unroll
+    for (int p = 0; p < RIGID_MAX_MARKERS; p++) {
+        const unsigned l = label_of(lab, p);
+        if (l == NO_LABEL) continue;
+        cnt += 1.;
+#pragma unroll
+        for (int u = 0; u < 3; u++) { sm[u] += model[3 * p + u]; sd[u] += det[3 * l + u]; }
+    }
+    double mb[3], db[3];
+#pragma unroll
+    for (int u = 0; u < 3; u++) { mb[u] = sm[u] / cnt; db[u] = sd[u] / cnt; }
+    double S[3][3] = {{0., 0., 0.}, {0., 0., 0.}, {0., 0., 0.}};
+#pragma unroll
+    for (int p = 0; p < RIGID_MAX_MARKERS; p++) {
+        const unsigned l = label_of(lab, p);
+        if (l == NO_LABEL) continue;
+#pragma unroll
+        for (int u = 0; u < 3; u++)
+#pragma unroll
+            for (int v = 0; v < 3; v++) S[u][v] += (model[3 * p + u] - mb[u]) * (det[3 * l + v] - db[v]);
+    }
+    double N[4][4];
+    N[0][0] = (S[0][0] + S[1][1]) + S[2][2];
+    N[1][1] = (S[0][0] - S[1][1]) - S[2][2];
+    N[2][2] = (S[1][1] - S[0][0]) - S[2][2];
+    N[3][3] = (S[2][2] - S[0][0]) - S[1][1];
+    N[0][1] = N[1][0] = S[1][2] - S[2][1];
+    N[0][2] = N[2][0] = S[2][0] - S[0][2];
+    N[0][3] = N[3][0] = S[0][1] - S[1][0];
+    N[1][2] = N[2][1] = S[0][1] + S[1][0];
+    N[1][3] = N[3][1] = S[2][0] + S[0][2];
+    N[2][3] = N[3][2] = S[1][2] + S[2][1];
+#pragma unroll
+    for (int r = 0; r < 4; r++)
+#pragma unroll
+        for (int c = 0; c < 4; c++) N[r][c] = -N[r][c]; // the largest eigenvalue of N is the smallest of -N
+    double q[4];
+    smallest_eigvec4(N, q);
+    const double nrm = sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
+#pragma unroll
+    for (int k = 0; k < 4; k++) q[k] = q[k] / nrm;
+    const bool z0 = q[0] == 0., z1 = q[1] == 0., z2 = q[2] == 0.;
+    const bool neg = q[0] < 0. || (z0 && q[1] < 0.) || (z0 && z1 && q[2] < 0.) || (z0 && z1 && z2 && q[3] < 0.);
+#pragma unroll
+    for (int k = 0; k < 4; k++) o.q[k] = neg ? -q[k] : q[k];
+    const double w = o.q[0], x = o.q[1], y = o.q[2], z = o.q[3];
+    const double ww = w * w, xx = x * x, yy = y * y, zz = z * z;
+    const double wx = w * x, wy = w * y, wz = w * z, xy = x * y, xz = x * z, yz = y * z;
+    o.R[0] = ((ww + xx) - yy) - zz; o.R[1] = 2.0 * (xy - wz);       o.R[2] = 2.0 * (xz + wy);
+    o.R[3] = 2.0 * (xy + wz);       o.R[4] = ((ww - xx) + yy) - zz; o.R[5] = 2.0 * (yz - wx);
+    o.R[6] = 2.0 * (xz - wy);       o.R[7] = 2.0 * (yz + wx);       o.R[8] = ((ww - xx) - yy) + zz;
+#pragma unroll
+    for (int u = 0; u < 3; u++) o.t[u] = db[u] - ((o.R[3 * u] * mb[0] + o.R[3 * u + 1] * mb[1]) + o.R[3 * u + 2] * mb[2]);
+}
+
+// steps 4 to 6 for one candidate: pose from its three pairs, labels, one refit, rms^2.  n_in < min_markers: no refit, no result.
+__device__ __forceinline__ void evaluate(unsigned e, const int* tri, const double* model, const double* det, int M, int n, double g2,
+                                         int min_markers, Fit& f)
+{
+    const int h = e >> 18, i = (e >> 12) & 63, j = (e >> 6) & 63, k = e & 63;
+    unsigned long long seed = ~0ull;
+    seed = with_label(seed, tri[3 * h], (unsigned)i);
+    seed = with_label(seed, tri[3 * h + 1], (unsigned)j);
+    seed = with_label(seed, tri[3 * h + 2], (unsigned)k);
+    horn(model, det, seed, f.pose);
+    unsigned long long claimed = 0ull, lab = ~0ull;
+    int n_in = 0;
+#pragma unroll
+    for (int p = 0; p < RIGID_MAX_MARKERS; p++) {
+        if (p >= M) continue;
+        double pr[3];
+        transform(f.pose, model + 3 * p, pr);
+        int best = -1;
+        double bd = 0.;
+        for (int l = 0; l < n; l++) { // the nearest unclaimed detection below gate^2; ties go to the lower row
+            const double e0 = det[3 * l] - pr[0], e1 = det[3 * l + 1] - pr[1], e2 = det[3 * l + 2] - pr[2];
+            const double d2 = (e0 * e0 + e1 * e1) + e2 * e2;
+            if (!(claimed >> l & 1ull) && d2 < g2 && (best < 0 || d2 < bd)) { bd = d2; best = l; }
+        }
+        if (best >= 0) { claimed |= 1ull << best; lab = with_label(lab, p, (unsigned)best); n_in++; }
+    }
+    f.lab = lab; f.n_in = n_in; f.rms2 = 0.;
+    if (n_in < min_markers) return;
+    horn(model, det, lab, f.pose);
+    double ssq = 0.;
+#pragma unroll
+    for (int p = 0; p < RIGID_MAX_MARKERS; p++) {
+        const unsigned l = label_of(lab, p);
+        if (l == NO_LABEL) continue;
+        double pr[3];
+        transform(f.pose, model + 3 * p, pr);
+        const double e0 = det[3 * l] - pr[0], e1 = det[3 * l + 1] - pr[1], e2 = det[3 * l + 2] - pr[2];
+        ssq += (e0 * e0 + e1 * e1) + e2 * e2;
+    }
+    f.rms2 = ssq / (double)n_in;
+}
+
+// the total order of step 7: more inliers, smaller rms^2, smaller (h, i, j, k); n < 0 = no result, which nothing is worse than
+__device__ __forceinline__ bool better(int an, double ar, unsigned ap, int bn, double br, unsigned bp)
+{
+    return an > bn || (an == bn && (ar < br || (ar == br && ap < bp)));
+}
+
+} // namespace
+
+__global__ __launch_bounds__(THREADS) void rigid_poses_kernel(RigidArgs a)
+{
+    __shared__ double s_dd[RIGID_MAX_DET * DS];           // the detections' distance table
+    __shared__ double s_det[RIGID_MAX_DET * 3];
+    __shared__ double s_model[RIGID_MAX_MARKERS * 3];
+    __shared__ double s_dm[RIGID_MAX_MARKERS * RIGID_MAX_MARKERS];
+    __shared__ int s_tri[RIGID_MAX_TRIPLES * 3];
+    __shared__ unsigned s_cand[RIGID_MAX_HYP];            // h << 18 | i << 12 | j << 6 | k, in no particular order
+    __shared__ double s_kr[THREADS];                      // the reduction's keys: rms^2, inliers, candidate
+    __shared__ int s_kn[THREADS];
+    __shared__ unsigned s_kp[THREADS];
+    __shared__ int s_count, s_bad;
+
+    const int tid = threadIdx.x;
+    const int t = blockIdx.x / a.B, b = blockIdx.x - t * a.B;
+    const size_t o = (size_t)t * a.B + b;
+    const int n = a.n[t], M = a.n_markers[b], H = a.n_tri[b];
+    const int rows = a.Q < RIGID_MAX_DET ? a.Q : RIGID_MAX_DET;
+    const int cap = a.max_hyp < RIGID_MAX_HYP ? a.max_hyp : RIGID_MAX_HYP;
+
+    // every exit below is taken by the whole workgroup: `code` is formed from values all lanes share
+    int code = 0;
+    if (n < 0) code = RIGID_ERR_BLIND;
+    else if (n > rows) code = RIGID_ERR_CAPACITY;
+    else if (M < 3 || M > RIGID_MAX_MARKERS || H < 1 || H > RIGID_MAX_TRIPLES) code = RIGID_ERR_MODEL;
+
+    if (code == 0) {
+        // ---- (a) inputs and tables ---------------------------------------------------------------------------------------------
+        if (tid == 0) { s_count = 0; s_bad = 0; }
+        for (int x = tid; x < 3 * H; x += THREADS) s_tri[x] = a.tri[(size_t)b * RIGID_MAX_TRIPLES * 3 + x];
+        if (tid < 3 * M) s_model[tid] = a.model[(size_t)b * RIGID_MAX_MARKERS * 3 + tid];
+        for (int x = tid; x < 3 * n; x += THREADS) s_det[x] = a.xyz[(size_t)t * a.Q * 3 + x];
+        __syncthreads();
+        if (tid < H) {
+            const int ta = s_tri[3 * tid], tb = s_tri[3 * tid + 1], tc = s_tri[3 * tid + 2];
+            if (!(0 <= ta && ta < tb && tb < tc && tc < M)) s_bad = 1;
+        }
+        for (int x = tid; x < n * n; x += THREADS) {
+            const int i = x / n, j = x - i * n;
+            s_dd[i * DS + j] = dist3(s_det + 3 * i, s_det + 3 * j);
+        }
+        if (tid < RIGID_MAX_MARKERS * RIGID_MAX_MARKERS) {
+            const int i = tid >> 3, j = tid & 7;
+            s_dm[tid] = i < M && j < M ? dist3(s_model + 3 * i, s_model + 3 * j) : 0.;
+        }
+        __syncthreads();
+        if (s_bad) code = RIGID_ERR_MODEL;
+    }
+
+    int count = 0;
+    if (code == 0) {
+        // ---- (b) candidates: |d_ij - L_ab|, |d_jk - L_bc|, |d_ik - L_ac| all below tol, i, j, k distinct -------------------------
+        const int nn = n * n, items = H * nn;
+        for (int x = tid; x < items; x += THREADS) {
+            const int h = x / nn, r = x - h * nn, i = r / n, j = r - i * n;
+            if (i == j) continue;
+            const int ta = s_tri[3 * h], tb = s_tri[3 * h + 1], tc = s_tri[3 * h + 2];
+            if (!(fabs(s_dd[i * DS + j] - s_dm[ta * 8 + tb]) < a.tol)) continue;
+            const double Lbc = s_dm[tb * 8 + tc], Lac = s_dm[ta * 8 + tc];
+            for (int k = 0; k < n; k++) {
+                if (k == i || k == j) continue;
+                if (fabs(s_dd[j * DS + k] - Lbc) < a.tol && fabs(s_dd[i * DS + k] - Lac) < a.tol) {
+                    const int pos = atomicAdd(&s_count, 1);
+                    if (pos < cap) s_cand[pos] = (unsigned)h << 18 | (unsigned)i << 12 | (unsigned)j << 6 | (unsigned)k;
+                }
+            }
+        }
+        __syncthreads();
+        count = s_count;
+        if (count > cap) code = RIGID_ERR_HYP; // never a shortened list
+    }
+
+    if (code == 0) {
+        const double g2 = a.gate * a.gate;
+        int bn = -1;
+        double br = 0.;
+        unsigned bp = 0xffffffffu;
+        unsigned winner = 0u;
+        for (int pass = 0; pass < 2; pass++) {
+            // ---- (c) pass 0: every candidate, the lane's best key;  (e) pass 1: lane 0 solves the winner again and writes it ----
+            const bool last = pass == 1;
+            const int lo = last ? (tid == 0 ? 0 : 1) : tid, hi = last ? 1 : count;
+            for (int x = lo; x < hi; x += THREADS) {
+                const unsigned e = last ? winner : s_cand[x];
+                Fit f;
+                evaluate(e, s_tri, s_model, s_det, M, n, g2, a.min_markers, f);
+                if (!last) {
+                    if (f.n_in >= a.min_markers && better(f.n_in, f.rms2, e, bn, br, bp)) { bn = f.n_in; br = f.rms2; bp = e; }
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 9; k++) a.R[o * 9 + k] = f.pose.R[k];
+#pragma unroll
+                    for (int k = 0; k < 3; k++) a.t[o * 3 + k] = f.pose.t[k];
+#pragma unroll
+                    for (int k = 0; k < 4; k++) a.q[o * 4 + k] = f.pose.q[k];
+                    a.rms[o] = sqrt(f.rms2);
+                    a.n_in[o] = f.n_in;
+#pragma unroll
+                    for (int p = 0; p < RIGID_MAX_MARKERS; p++) {
+                        const unsigned l = label_of(f.lab, p);
+                        a.label[o * RIGID_MAX_MARKERS + p] = l == NO_LABEL ? -1 : (int)l;
+                    }
+                    a.status[o] = 0;
+                }
+            }
+            if (last) return;
+            // ---- (d) the smallest key of the workgroup -------------------------------------------------------------------------
+            s_kn[tid] = bn; s_kr[tid] = br; s_kp[tid] = bp;
+            __syncthreads();
+            for (int s = THREADS / 2; s > 0; s >>= 1) {
+                if (tid < s && better(s_kn[tid + s], s_kr[tid + s], s_kp[tid + s], s_kn[tid], s_kr[tid], s_kp[tid])) {
+                    s_kn[tid] = s_kn[tid + s]; s_kr[tid] = s_kr[tid + s]; s_kp[tid] = s_kp[tid + s];
+                }
+                __syncthreads();
+            }
+            if (s_kn[0] < 0) { code = RIGID_LOST; break; }
+            winner = s_kp[0];
+        }
+    }
+
+    // no result: the status says why, no inliers, no labels; the floats stay as they were
+    if (tid == 0) { a.status[o] = code; a.n_in[o] = 0; }
+    if (tid < RIGID_MAX_MARKERS) a.label[o * RIGID_MAX_MARKERS + tid] = -1;
+}
+
+void launch_rigid_poses(const RigidArgs& a, hipStream_t s)
+{
+    hipLaunchKernelGGL(rigid_poses_kernel, dim3((unsigned)(a.T * a.B)), dim3(THREADS), 0, s, a);
+}
+
+} // namespace mocap

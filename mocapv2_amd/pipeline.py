@@ -10,7 +10,7 @@ With one rank the block is the whole grid and no collective runs.
 import numpy as np
 import torch
 
-from .engine import GRAY_SHIFT, MocapContext
+from .engine import GRAY_SHIFT, MocapContext, rigid_tables
 
 
 def shard_plan(n_cams, steps_per_rank, world, rank):
@@ -187,7 +187,7 @@ class BatchTracker:
     def __init__(self, K, dist, R, t, F, width, height, steps_per_rank, world=1, rank=0, device=0, group=None,
                  max_points=32, max_groups=4096, depth=1, bayer_pattern=None, gray_shift=GRAY_SHIFT, collective="auto",
                  force_collective=False, visibility="all", min_views=2, gate=10.0, max_err=25.0, max_passes=3, cutoff=10.0,
-                 max_hyp=8192, track=None, subpixel=None):
+                 max_hyp=8192, track=None, subpixel=None, bodies=None):
         """visibility: which markers stage B reports --
              "all"   the reference's find_point_correspondance_and_object_points (mocap_correspond): a marker every camera sees,
                      searched from camera 0's points; the outputs are MocapContext.correspond's;
@@ -213,7 +213,23 @@ class BatchTracker:
              centroids from the frames right behind the blob stage, and stage B reads the refined points (ideal pixels) in
              either visibility, also from raw Bayer frames.  The outputs gain subpix_flags [images, max_points] (SUBPIX_* bits per
              image point; a flagged point is its integer centroid).  Needs world == 1: the all-gather carries the int32 records only.
-             None is the path as it was."""
+             None is the path as it was.
+           bodies: None, or {"models": [...], "tol": world units, "gate": world units, "min_markers": 3, "max_hyp": 1024,
+             "min_area": 1e-4, "names": [...]} -- rigid-body poses per time step (MocapContext.rigid_bodies / rigid_poses, DESIGN.md
+             section 2; tol and gate are required, there are no defaults for them: they are the capture's noise).  The outputs
+             gain body_R [T, B, 9], body_t [T, B, 3], body_q [T, B, 4] (w, x, y, z), body_rms [T, B], body_n [T, B], body_label
+             [T, B, 8] and body_status [T, B].  The labels are rows of xyz with visibility="any"; with "all" they are positions in
+             `order`, as `track`'s rows are.  Stateless per time step: works with world > 1 and any depth, next to `track` or
+             without it.  None is the path as it was: no launch, no key."""
+        self.bodies = None
+        if bodies is not None:
+            known = {"models", "tol", "gate", "min_markers", "max_hyp", "min_area", "names"}
+            if set(bodies) - known or not {"models", "tol", "gate"} <= set(bodies):
+                raise ValueError(f"bodies: a dict with models, tol and gate (all required), min_markers, max_hyp, min_area, names; "
+                                 f"got {sorted(bodies)}")
+            rigid_tables(bodies["models"], float(bodies.get("min_area", 1e-4)))  # refuses bad models before anything is allocated
+            self.bodies = {"tol": float(bodies["tol"]), "gate": float(bodies["gate"]), "min_markers": int(bodies.get("min_markers", 3)),
+                           "max_hyp": int(bodies.get("max_hyp", 1024))}
         self.subpixel = None
         if subpixel is not None:
             if world > 1:
@@ -276,6 +292,9 @@ class BatchTracker:
         self._k = 0
         self._cur = self.lanes[0]
         self.track_state = self.lanes[0].ctx.track_state(self.max_tracks) if self.track else None
+        self.body_tables = None
+        if self.bodies:
+            self.body_tables = self.lanes[0].ctx.rigid_bodies(bodies["models"], float(bodies.get("min_area", 1e-4)), bodies.get("names"))
         self._track_done = None  # event behind the most recent track call (depth > 1): the next batch's call waits for it
         self.force_collective = bool(force_collective)
         self.collective = None
@@ -384,15 +403,31 @@ class BatchTracker:
             self.out["subpix_flags"] = self._cur.subpix["flags"]
         return self.out
 
+    def _marker_rows(self, out):
+        """The 3-D markers of a batch in the rows `track` and `bodies` speak of: xyz as it is with visibility="any"; with "all" the
+        reported roots in their order (rows beyond n: whatever `order` holds, clamped)"""
+        xyz = out["xyz"]
+        if self.visibility == "all":
+            pick = out["order"].clamp(0, xyz.shape[1] - 1).to(torch.int64)[:, :, None].expand(-1, -1, 3)
+            xyz = torch.gather(xyz, 1, pick)
+        return xyz
+
+    BODY_KEYS = {"R": "body_R", "t": "body_t", "q": "body_q", "rms": "body_rms", "n_in": "body_n", "label": "body_label",
+                 "status": "body_status"}
+
+    def body_poses(self, out):
+        """Rigid-body poses for the markers of a batch (the tracker was built with `bodies`): adds the body_* tensors to `out`."""
+        prev = {k: out[v] for k, v in self.BODY_KEYS.items()} if "body_R" in out else None
+        res = self._cur.ctx.rigid_poses(self._marker_rows(out), out["n"], self.body_tables, out=prev, **self.bodies)
+        out.update({v: res[k] for k, v in self.BODY_KEYS.items()})
+        return out
+
     def track_ids(self, out, steps=None):
         """Identities for the markers of a batch, in the order the batches are submitted (the tracker was built with `track`):
         adds id, slot, age and status to `out`.  Batches in flight on several streams share the one state, so every call waits
         for the event recorded behind the call before it."""
         lane = self._cur
-        xyz = out["xyz"]
-        if self.visibility == "all":  # the reported roots, in their order (rows beyond n: whatever `order` holds, clamped)
-            pick = out["order"].clamp(0, xyz.shape[1] - 1).to(torch.int64)[:, :, None].expand(-1, -1, 3)
-            xyz = torch.gather(xyz, 1, pick)
+        xyz = self._marker_rows(out)
         if lane.stream is not None and self._track_done is not None:
             torch.cuda.current_stream().wait_event(self._track_done)
         ids = {k: out[k] for k in ("id", "slot", "age", "status")} if "id" in out else None
@@ -435,7 +470,9 @@ class BatchTracker:
         else:
             gathered = allgather_records(records, self.world, self.group, force=self.force_collective)
         out = self.triangulate(gathered)
-        return self.track_ids(out, steps) if self.track else out
+        if self.track:
+            out = self.track_ids(out, steps)
+        return self.body_poses(out) if self.bodies else out
 
     def synchronize(self):
         """Wait for every batch submitted so far."""

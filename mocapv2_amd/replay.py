@@ -38,7 +38,7 @@ class ReplayTracker:
 
     def __init__(self, K, dist, R, t, F, width, height, batch=64, obj_count=OBJ_COUNT, device=0, max_points=32,
                  max_groups=4096, bayer_pattern=None, gray_shift=GRAY_SHIFT, depth=1, visibility="all", min_views=2, gate=10.0,
-                 max_err=25.0, max_passes=3, cutoff=10.0, max_hyp=8192, track=None, subpixel=None):
+                 max_err=25.0, max_passes=3, cutoff=10.0, max_hyp=8192, track=None, subpixel=None, bodies=None):
         """visibility="any" (BatchTracker's): a time step yields the markers at least min_views cameras see, found from any
         camera pair, in acceptance order (more views first, then smaller error) -- the first obj_count + 1 of them as
         object_points, image_points [markers, C, 2] float64 with NaN where a camera does not see the marker; F may be None.
@@ -49,7 +49,12 @@ class ReplayTracker:
         `ages`, row for row beside object_points (-1 = the row's marker got no track).  The black frames that pad the last batch
         are not walked: they do not age the tracks.  The messages stay as they are.
         subpixel (BatchTracker's): {"radius": r, "floor": f, "iters": 3} -- the object points are triangulated from sub-pixel image
-        points; image_points keep their integer form (visibility="any": the records' centroids; "all": the refined points, truncated)."""
+        points; image_points keep their integer form (visibility="any": the records' centroids; "all": the refined points, truncated).
+        bodies (BatchTracker's): {"models": [...], "tol": ..., "gate": ..., "min_markers": 3, "names": [...]} -- rigid-body poses
+        per time step; the dicts of run_batches gain body_R, body_t, body_q, body_rms, body_n, body_label, body_status (host
+        arrays [n_steps, B, ...]) and body_messages: per time step one rigid_message per body, {"<name>": [w, x, y, z, tx, ty, tz]};
+        a body without a pose in a step repeats its previous message (seven zeros until its first pose).  run() yields the same per
+        time step.  The labels are rows of the step's markers before the obj_count selection.  `messages` stay as they are."""
         self.n_cam = len(K)
         self.batch = int(batch)
         self.obj_count = obj_count
@@ -58,9 +63,12 @@ class ReplayTracker:
         self.tracker = BatchTracker(K, dist, R, t, F, width, height, self.batch, device=device, max_points=max_points,
                                     max_groups=max_groups, bayer_pattern=bayer_pattern, gray_shift=gray_shift, depth=self.depth,
                                     visibility=visibility, min_views=min_views, gate=gate, max_err=max_err, max_passes=max_passes,
-                                    cutoff=cutoff, max_hyp=max_hyp, track=track, subpixel=subpixel)
+                                    cutoff=cutoff, max_hyp=max_hyp, track=track, subpixel=subpixel, bodies=bodies)
         self.visibility = visibility
         self.tracked = track is not None
+        self.body_names = self.tracker.body_tables["names"] if bodies is not None else None
+        if self.body_names is not None:  # the message in force per body: zeros until its first pose
+            self.body_carry = [rigid_message(name, [0.0] * 4, [0.0] * 3) for name in self.body_names]
         self.point = [0, 0, 0, 0, 0, 0, 0, 0]  # RealtimeTracking_FLIR.py:171 (eight zeros until the first detection)
         # raw sensor frames: the camera loop's cvtColor(BAYER_GR2BGR) + cvtColor(BGR2GRAY) (:103-104) run on the GPU first, with
         # no gray frame in memory (BatchTracker.extract); bayer_pattern 0..3 = BG, GB, RG, GR (the reference: 3), None = the
@@ -122,7 +130,26 @@ class ReplayTracker:
         if has.any():
             self.point = [0, 0, 0, 0] + list(obj[np.flatnonzero(has)[-1], 0])  # :184-185
         res = {"first_step": b0, "n_steps": nb, "n_roots": n, "kept": kept, "object_points": obj, "image_points": grp, "messages": msgs}
-        return self._with_ids(res, out, n, width)
+        return self._with_bodies(self._with_ids(res, out, n, width), out)
+
+    def _with_bodies(self, res, out):
+        """body_* [n_steps, B, ...] and body_messages: one device-to-host copy per output, the messages built in bulk per body"""
+        if self.body_names is None:
+            return res
+        nb = res["n_steps"]
+        for key in BatchTracker.BODY_KEYS.values():
+            res[key] = out[key].cpu().numpy()[:nb]
+        has = res["body_status"] == 0
+        per_body = []
+        for b, name in enumerate(self.body_names):
+            q = np.where(has[:, b, None], res["body_q"][:, b], 0.0)  # (the floats of a step without a pose are not read)
+            t = np.where(has[:, b, None], res["body_t"][:, b], 0.0)
+            msgs = batch_rigid_messages(name, q, t, has[:, b], self.body_carry[b])
+            if nb:
+                self.body_carry[b] = msgs[-1]
+            per_body.append(msgs)
+        res["body_messages"] = [[per_body[b][s] for b in range(len(self.body_names))] for s in range(nb)]
+        return res
 
     def _with_ids(self, res, out, n, width):
         """ids / ages [n_steps, width] beside object_points (the tracker's rows are object_points' rows in both visibilities)"""
@@ -156,7 +183,7 @@ class ReplayTracker:
         if has.any():
             self.point = [0, 0, 0, 0] + list(obj[np.flatnonzero(has)[-1], 0])
         res = {"first_step": b0, "n_steps": nb, "n_roots": n, "kept": kept, "object_points": obj, "image_points": img, "messages": msgs}
-        return self._with_ids(res, out, n, width)
+        return self._with_bodies(self._with_ids(res, out, n, width), out)
 
     def run_batches(self, frames, send_many=None):
         """Generator over BATCHES of time steps: dicts with first_step, n_steps, n_roots [n], kept [n] (object points per time
@@ -185,7 +212,52 @@ class ReplayTracker:
                 one = {"object_points": obj[s, :kept[s]] if k else empty, "image_points": img[s, :k] if k else empty, "message": msgs[s]}
                 if self.tracked:
                     one["ids"], one["ages"] = (res[f][s, :kept[s]] if k else none for f in ("ids", "ages"))
+                if self.body_names is not None:
+                    for key in list(BatchTracker.BODY_KEYS.values()) + ["body_messages"]:
+                        one[key] = res[key][s]
                 yield one
+
+
+def rigid_message(name, q, t):
+    """Wire format of one rigid-body update: msgpack map {"<name>": [w, x, y, z, tx, ty, tz]}, seven float64 -- the reference's
+    tracker message with its four orientation slots (scalar first, as its IMU code has them) filled."""
+    import msgpack
+    return msgpack.packb({str(name): [float(v) for v in list(q) + list(t)]}, use_bin_type=True)
+
+
+def unpack_rigid_message(data):
+    """-> (name, q [4], t [3])"""
+    import msgpack
+    (name, v), = msgpack.unpackb(data, raw=False).items()
+    return name, v[:4], v[4:]
+
+
+def _rigid_head(name):
+    raw = str(name).encode("utf-8")
+    if len(raw) < 32:
+        key = bytes([0xa0 | len(raw)])            # fixstr
+    elif len(raw) < 256:
+        key = bytes([0xd9, len(raw)])             # str 8
+    else:
+        raise ValueError(f"a body name of {len(raw)} bytes: at most 255")
+    return bytes([0x81]) + key + raw + bytes([0x97])  # map of 1, the key, array of 7
+
+
+def batch_rigid_messages(name, q, t, has, carry):
+    """The rigid_message bytes of one body over a run of time steps, built without a Python loop over them (batch_messages' way):
+    q [n, 4], t [n, 3] float64, has [n] bool (the step has a pose), carry: the message in force before the run."""
+    n = len(has)
+    head = _rigid_head(name)
+    L = len(head) + 63
+    buf = np.empty((n, L), np.uint8)
+    buf[:, :len(head)] = np.frombuffer(head, np.uint8)
+    body = buf[:, len(head):].reshape(n, 7, 9)
+    body[:, :, 0] = 0xcb
+    vals = np.concatenate([np.asarray(q, np.float64).reshape(n, 4), np.asarray(t, np.float64).reshape(n, 3)], axis=1)
+    body[:, :, 1:] = np.ascontiguousarray(vals).astype(">f8").view(np.uint8).reshape(n, 7, 8)
+    src = np.maximum.accumulate(np.where(has, np.arange(n), -1)) if n else np.zeros(0, np.int64)
+    raw = buf[np.maximum(src, 0)].tobytes()
+    return [raw[i * L:(i + 1) * L] if src[i] >= 0 else carry for i in range(n)]
 
 
 _MSG_HEAD = bytes([0x81, 0xa8]) + b"tracker1" + bytes([0x97, 0, 0, 0, 0])  # map of 1, fixstr(8), array of 7, four zero ints
@@ -209,4 +281,5 @@ def batch_messages(first_points, has, carry):
     return [raw[i * L:(i + 1) * L] if src[i] >= 0 else carry for i in range(n)]
 
 
-__all__ = ["ReplayTracker", "batch_messages", "tracker_message", "unpack_tracker_message", "OBJ_COUNT", "MocapContext"]
+__all__ = ["ReplayTracker", "batch_messages", "tracker_message", "unpack_tracker_message", "rigid_message", "unpack_rigid_message",
+           "batch_rigid_messages", "OBJ_COUNT", "MocapContext"]
