@@ -14,9 +14,10 @@
 // Candidates are found with word-parallel bit tests on the mask, guided by the occupancy words the filter kernels leave
 // per tile and by the tiles' boxes (settle_tiles_kernel); a group of 8 lanes holds consecutive words of a mask row.  Every
 // candidate becomes one entry of a batch-wide walk list and is followed by a PAIR OF LANES of contour_follow_kernel: one lane
-// forwards, one backwards from the same start, until they meet (see there); a lane keeps the three 64-column mask rows around
-// its current pixel in registers (a vertical move takes one new row from a 64 x 64 window staged in LDS), the walker state and
-// the integer Green's-theorem sums are per-lane registers.  The step itself is literally the reference border-following step
+// forwards, one backwards from the same start, until they meet (see there); a lane reads the 3 x 3 neighbourhood of its
+// current pixel from a 64 x 64 window of the mask staged in LDS (three 16-bit loads per step, one per row; a lane that reaches the
+// window's rim pauses until the window is staged anew around it), the walker state and the integer Green's-theorem sums are
+// per-lane registers.  The step itself is literally the reference border-following step
 // (same neighbour order, same CHAIN_APPROX_SIMPLE vertex rule); a candidate is dropped as soon as one of its lanes meets an
 // earlier pixel of its own border.  The polygon sums are exact integers (int64), the perimeter is a sum of correctly rounded
 // float32 square roots held exactly in a double.
@@ -39,8 +40,6 @@ constexpr int MAXK = 256;   // kept contours per image
 constexpr int MAXD = 8;     // nesting depth of a kept contour
 constexpr int MAXCELL = 4096; // occupancy cells (strip x 8 rows) listed per image; with more, every cell is scanned
 constexpr int MAXA = 64;    // links per image whose owner has to be found by a walk that are handed to the packed second pass
-
-__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
 struct Mask {
     const uint32_t* w;

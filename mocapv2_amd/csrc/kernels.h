@@ -23,6 +23,14 @@ __host__ __device__ __forceinline__ uint32_t mask_byte_index(int y, int b, int w
 }
 __host__ __device__ __forceinline__ size_t mask_image_words(int H, int wpr) { return (size_t)((H + 31) >> 5) * 32 * (size_t)wpr; }
 
+// a value every lane of the wave holds, moved to scalar registers: addresses formed from it are scalar, loops over it uniform
+__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ unsigned long long uni64(unsigned long long v)
+{
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+    return (unsigned long long)hi << 32 | lo;
+}
+
 // Sums with a fixed order, for results that must have the same bits on every run (no floating-point atomics): the lanes of a
 // wave by shuffles (offsets 32 .. 1; lane 0 holds the sum) ...
 __device__ __forceinline__ double wave_sum(double v)

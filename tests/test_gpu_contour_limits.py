@@ -143,6 +143,29 @@ def test_more_kept_contours_than_max_blobs_are_counted_not_written(form):
     check_image(small, case_s, table_s, case["gates"], xy[1], cnt[1], recs[1], 128)
 
 
+@pytest.mark.parametrize("form", ["links_in_place", "links_deferred"])
+def test_more_walk_entries_than_the_waves_first_fill(form):
+    """A wave of the follow kernel takes its first 32 entries from 32 x its number; only a batch with more than 32 entries per
+    wave (4 waves per CU: 128 x CUs) has the counter hand out the rest.  ceil(128 CUs / 1024) + 4 images: combs_1024 (1024
+    entries each) with three squares_256_128 (384 each) in between, in one frame size.  Every image is the oracle's."""
+    import torch
+    assert torch.cuda.is_available(), "these tests need the MI355X"
+    first_fill = 128 * torch.cuda.get_device_properties(0).multi_processor_count
+    n = -(-first_fill // 1024) + 4
+    H, W = BUILDERS["squares_256_128"]()[0].shape
+    comb, square = built("combs_1024", H, W), built("squares_256_128", H, W)
+    gates = comb[1]["gates"]
+    assert square[1]["gates"] == gates
+    images = [square if i in (n // 4, n // 2, 3 * n // 4) else comb for i in range(n)]
+    entries = sum(local_candidates(m) for m, _, _ in images)
+    assert local_candidates(comb[0]) == 1024 and entries > first_fill + 1024, (entries, first_fill)
+    xy, cnt, recs = run([m for m, _, _ in images], gates, form)
+    print("images", n, "walk entries", entries, "first fill", first_fill)
+    for i, (mask, case, table) in enumerate(images):
+        assert cnt[i] >= 0, (i, cnt[i])
+        check_image(mask, case, table, gates, xy[i], cnt[i], recs[i], 256)
+
+
 # ---- the list of occupancy cells (MAXCELL = 4096), through mocap_blob_centroids ----------------------------------------
 def bar_frame(H, W):
     """full-width bars 9 rows thick every 16 rows, 255 on black: blur, threshold and median leave 5 rows of each"""

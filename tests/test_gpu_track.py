@@ -179,6 +179,39 @@ def test_the_largest_shape(ctx):
     assert (out["id"][3] >= 0).all() and sorted(out["slot"][3].tolist()) == list(range(256))
 
 
+@pytest.mark.parametrize("M", [192, 130])
+def test_three_waves(ctx, M):
+    """max_tracks in 129 .. 192: 192 threads, so the detections' lanes wrap at 96 and the fourth word of a step's 256
+    detections is served by wave 0.  The lattice of test_the_largest_shape, the first count[t] points of it per step in
+    permuted rows: more detections than slots from the third step (second: M = 130) on.  Births never come from rows at and
+    beyond M, so what the fourth word carries is matched rows and rows that stay -1: both must exist there."""
+    rng = np.random.default_rng(9)
+    g = np.arange(256)
+    base = np.stack([0.1 * (g % 16), 0.1 * (g // 16), 0.03 * (g % 3)], axis=1)
+    counts = (120, 180, 256, 256, 230, 256, 256)
+    T = len(counts)
+    xyz = np.zeros((T, 256, 3))
+    for t, c in enumerate(counts):
+        pts = (base + 0.004 * t + 0.002 * rng.standard_normal(base.shape))[:c]
+        xyz[t, :c] = pts[rng.permutation(c)]
+    n = np.array(counts, np.int32)
+    out, _ = check(ctx, xyz, n, M, 0.03, max_miss=2, what=f"three waves, M = {M}")
+    full = [0, 0] + [tr.E_FULL] * 5 if M == 192 else [0] + [tr.E_FULL] * 6
+    assert out["status"].tolist() == full
+    for t in np.flatnonzero(n == 256):
+        word3 = out["id"][t, 192:256]
+        assert (word3 == -1).sum() >= 6 and (word3 >= 0).sum() >= 6, (t, word3.tolist())
+
+
+@pytest.mark.parametrize("T", [48, 96, 97])
+def test_the_chunk_edges(ctx, T):
+    """Q = 16: a chunk is 48 steps.  T = 48 is one full chunk with nothing to prefetch, 96 two full chunks (the last step's
+    count prefetch has no step beyond T to read), 97 leaves a last chunk of one step."""
+    xyz, n, _, _, _ = tr.scene(7, 0.8, T=T)
+    out, state = check(ctx, xyz, n, 16, GATE, what=f"T = {T}")
+    assert (out["id"] >= 0).sum() == n.sum() and tr.split_state(state)[0]["steps"][0] == T
+
+
 def test_two_calls_give_the_same_bits(ctx):
     xyz, n, gate = tr.crowd_case()
     a = run_gpu(ctx, xyz, n, 16, gate)
