@@ -95,7 +95,7 @@ MOCAP_API int mocap_set_blob_params(mocap_ctx_t ctx, const mocap_blob_params* p)
  * them changes a result; they select between equivalent code paths (A/B measurements, tests of the alternative paths) or
  * size a scratch buffer.  mocap_ctx_create reads each of them ONCE from the environment (MOCAP_<NAME> in capitals; the hot
  * path never calls getenv), this call changes one for the context afterwards.  Names: skip_dark,
- * general_filter, dense_boxes, remap_pipeline, cluster, wide_quads_remap, wide_quads_identity, wide_bands, wide_fork,
+ * general_filter, dense_boxes, remap_pipeline, cluster, wide_quads_remap, wide_quads_identity, wide_bands, wide_split, wide_fork,
  * box_prio, scan_prio, contour_prio, corr_prio, box_stage_bytes, box_timing, contour_timing, follow_timing, scan_wide, scan_hotmap, scan_serial, rows_staged, rows_stage_dw, wide_blocks_per_cu, contour_blocks_per_cu, mark_blocks_per_cu, contour_defer,
  * scan_blocks_per_cu, scan_slices, excess_base, probe_debug, contour_boxes, contours_split, corr_threads, corr_step_groups.  (rows, box_blocks_per_cu and base_sel
  * shape the context at creation: environment only.)  Must not race with a batch call on the same context. */
@@ -582,6 +582,11 @@ MOCAP_API int mocap_allgather_centroids(mocap_ctx_t ctx, const int32_t* local_re
  * disables it.  mocap_tile_stats: number of (strip, chunk) tiles of the most recent batch and how many of them were
  * resolved that way.  Synchronises the device. */
 MOCAP_API int mocap_tile_stats(mocap_ctx_t ctx, uint64_t* tiles, uint64_t* skipped);
+/* The work lists the sparse path made of the most recent batch (any entry point that filters): items of the box kernel,
+ * entries of the wide-tile list, and wide tiles that were cut at their empty columns into items instead (wide_split: 0 = never,
+ * 2 = always, 1 = unless the context's last probe found the scene crowded; the default).  All 0
+ * when the batch took the dense path.  Any pointer may be null.  Synchronises the device. */
+MOCAP_API int mocap_list_stats(mocap_ctx_t ctx, uint32_t* items, uint32_t* wide, uint32_t* split);
 /* HIP-event timing of the kernels launched by mocap_blob_centroids / mocap_filter_mask / mocap_correspond / mocap_correspond_visible, recorded
  * on their stream.  mocap_profile_read synchronises, returns accumulated milliseconds and launch counts and resets:
  * index 0 = box_filter_kernel (or the general filter_mask_kernel), 1 = contours_kernel, 2 = correspond_kernel and

@@ -129,7 +129,7 @@ static ScanBounds scan_bounds(const mocap_ctx* c, int slot_base, int cam_mod, in
     auto t5 = [](int n) { return (n - 1 < 2 ? n - 1 : 2) + 1; }; // taps of a window at the border, per axis
     auto t5full = [](int n) { return n < 5 ? n : 5; };
     const long long per_tap = 1024LL * (2LL * thr_mul - 2LL * b.base - 1), per_tap_alt = 1024LL * (2LL * thr_mul - 2LL * b.base_alt - 1);
-    if (!c->tile_rows || !c->reach || !c->cflags) ok = false;
+    if (!c->tile_rows || !c->tile_cols || !c->reach || !c->cflags) ok = false;
     if (ok && wmax > 0 && per_tap > 0) {
         b.allow = (int)((per_tap * t5full(c->W) * t5full(c->H) - 1) / wmax); // windows with all their taps
         const long long taps1 = t5(c->W) * t5full(c->H) < t5full(c->W) * t5(c->H) ? t5(c->W) * t5full(c->H) : t5full(c->W) * t5(c->H);
@@ -222,6 +222,9 @@ static BoxArgs box_args(const mocap_ctx* c, const Batch& bt, const FilterPath& p
     a.tile_rows = c->tile_rows + (c->tile_rows_flip ? tr_words : 0);
     a.tile_rows_next = c->tile_rows + (c->tile_rows_flip ? 0 : tr_words);
     a.n_clear = c->tile_rows_hold[c->tile_rows_flip ^ 1];
+    a.tile_cols = c->tile_cols + (c->tile_rows_flip ? tr_words / 4 : 0);
+    a.tile_cols_next = c->tile_cols + (c->tile_rows_flip ? 0 : tr_words / 4);
+    a.wide_split = c->tune.wide_split == 2 || (c->tune.wide_split == 1 && !c->hot_dense); // (1: sparse scenes only, as scan_hotmap and contour_defer)
     a.cluster = c->tune.cluster;
     a.cur_box = bt.own_mask ? c->cur_box : c->cur_box_ext;
     a.items = c->items; a.n_items = c->n_items; a.cap_items = (uint32_t)c->items.n;
@@ -242,7 +245,8 @@ static BoxArgs box_args(const mocap_ctx* c, const Batch& bt, const FilterPath& p
 }
 
 // the scan's arguments, without probe and hot map
-static BrightArgs bright_args(const mocap_ctx* c, const Batch& bt, const FilterPath& p, const ScanBounds& sb, uint32_t* tile_rows, bool scan_zeroes)
+static BrightArgs bright_args(const mocap_ctx* c, const Batch& bt, const FilterPath& p, const ScanBounds& sb, uint32_t* tile_rows, uint32_t* tile_cols,
+                              bool scan_zeroes)
 {
     const Tiling tl = tiling(c);
     // floor(i / ncx) = umulhi(i, ceil(2^32 / ncx)) is exact while i * ncx < 2^32
@@ -262,16 +266,17 @@ static BrightArgs bright_args(const mocap_ctx* c, const Batch& bt, const FilterP
     b.zero_counters = scan_zeroes ? c->n_items.p : nullptr;
     b.block_ctr = c->n_items + 160; // (words 160..223 of the counter block zeroed above: one per slice)
     b.slices = c->tune.scan_slices; b.image0 = 0; b.slice_images = bt.n_images;
+    b.tile_cols = tile_cols;
     return b;
 }
 
 // One streaming pass over the frames marks the tiles (and their boxes) that can hold set pixels.  `b` keeps what it ran with,
 // for mark_tiles_kernel when that one has to follow (`mark_after_scan`).
-static int scan_tiles(mocap_ctx* c, const Batch& bt, const FilterPath& p, const ScanBounds& sb, uint32_t* tile_rows, bool scan_zeroes,
-                      BrightArgs& b, bool& mark_after_scan)
+static int scan_tiles(mocap_ctx* c, const Batch& bt, const FilterPath& p, const ScanBounds& sb, uint32_t* tile_rows, uint32_t* tile_cols,
+                      bool scan_zeroes, BrightArgs& b, bool& mark_after_scan)
 {
     const hipStream_t s = bt.s;
-    b = bright_args(c, bt, p, sb, tile_rows, scan_zeroes);
+    b = bright_args(c, bt, p, sb, tile_rows, tile_cols, scan_zeroes);
     const bool probe = sb.fixed_base < 0 && !c->probe_pending && sb.allow_alt >= 0 && sb.base_alt != sb.base && !p.bayer &&
                        (c->probe_age == 0 || c->probe_age >= 32);
     if (probe) {
@@ -350,7 +355,7 @@ static int report_box_timing(mocap_ctx* c, const uint64_t* timing, hipStream_t s
     const double n = sum[5] > 0 ? sum[5] : 1;
     uint32_t cnt[16];
     HIP_TRY(hipMemcpy(cnt, c->n_items, sizeof(cnt), hipMemcpyDeviceToHost));
-    fprintf(stderr, "[box] list: %u items, %u wide-tile entries\n", cnt[0], cnt[8]);
+    fprintf(stderr, "[box] list: %u items, %u wide-tile entries, %u split tiles\n", cnt[0], cnt[8], cnt[SPLIT_COUNTER]);
     fprintf(stderr, "[box] items %.0f (%.1f per wave) | cycles per item: header+wait %.0f, stage %.0f, patch %.0f, threshold %.0f, majority+next %.0f | busiest wave %.0f cycles\n",
             sum[5], sum[5] / c->box_grid, sum[0] / n, sum[1] / n, sum[2] / n, sum[3] / n, sum[4] / n, mx);
     return 0;
@@ -428,7 +433,7 @@ static int run_filter(mocap_ctx* c, const void* frames, int n_images, int cam_mo
     a.zero8 = bt.own_mask ? c->walk_count.p : nullptr; // (the contour stage of this batch follows on the same stream; null before its first batch)
     c->walk_count_zeroed = a.zero8 != nullptr;
     BrightArgs mark_args{}; bool mark_after_scan = false;
-    if (!a.dense) TRY(scan_tiles(c, bt, p, sb, a.tile_rows, scan_zeroes, mark_args, mark_after_scan));
+    if (!a.dense) TRY(scan_tiles(c, bt, p, sb, a.tile_rows, const_cast<uint32_t*>(a.tile_cols), scan_zeroes, mark_args, mark_after_scan));
     else if (p.bayer) { // no early-out (not provable for this table, or MOCAP_SKIP_DARK=0): the plain gray pass
         launch_bayer_gray(p.bl, s);
         HIP_TRY(hipGetLastError());
@@ -578,6 +583,8 @@ static int grow_mask_group(mocap_ctx* c, size_t n_images)
     TRY(c->tile_rows.reserve(2 * init.size()));
     HIP_TRY(hipMemcpy(c->tile_rows, init.data(), sizeof(uint32_t) * init.size(), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(c->tile_rows + init.size(), init.data(), sizeof(uint32_t) * init.size(), hipMemcpyHostToDevice));
+    TRY(c->tile_cols.reserve(2 * tiles)); // the column words beside them: no column marked
+    HIP_TRY(hipMemset(c->tile_cols, 0, sizeof(uint32_t) * 2 * tiles));
     // the hot map, sized for either scan form
     const int hw0 = hot_map_words(c->H, c->W, 0), hw1 = hot_map_words(c->H, c->W, 1);
     TRY(c->hotmap.reserve(n_images * (hw0 > hw1 ? hw0 : hw1), true)); // all zeros between batches: the scan stores hot words only, mark_tiles_kernel clears them
@@ -596,7 +603,7 @@ static int ensure_mask(mocap_ctx* c, int n_images)
     if ((size_t)n_images <= c->mask_images) return 0;
     c->mask_images = 0; c->last_images = 0;
     if (int rc = grow_mask_group(c, n_images)) { // not half a group: the error is returned once, the next call starts over
-        c->mask.release(); c->cells.release(); c->tile_rows.release(); c->hotmap.release(); c->cur_box.release();
+        c->mask.release(); c->cells.release(); c->tile_rows.release(); c->tile_cols.release(); c->hotmap.release(); c->cur_box.release();
         c->items.release(); c->wide_tiles.release();
         return rc;
     }
@@ -836,6 +843,22 @@ int mocap_tile_stats(mocap_ctx_t c, uint64_t* tiles, uint64_t* skipped)
     }
     if (tiles) *tiles = total;
     if (skipped) *skipped = total - full;
+    return MOCAP_OK;
+}
+
+int mocap_list_stats(mocap_ctx_t c, uint32_t* items, uint32_t* wide, uint32_t* split)
+{
+    if (!c) return fail(MOCAP_E_INVALID, "null context");
+    if (set_device(c)) return MOCAP_E_HIP;
+    uint32_t cnt[16] = {0};
+    static_assert(SPLIT_COUNTER != 0 && SPLIT_COUNTER != 8 && SPLIT_COUNTER < 16, "a word of its own in the first line of the counter block");
+    if (c->n_items) {
+        HIP_TRY(hipDeviceSynchronize());
+        HIP_TRY(hipMemcpy(cnt, c->n_items, sizeof(cnt), hipMemcpyDeviceToHost));
+    }
+    if (items) *items = cnt[0];
+    if (wide) *wide = cnt[8];
+    if (split) *split = cnt[SPLIT_COUNTER];
     return MOCAP_OK;
 }
 

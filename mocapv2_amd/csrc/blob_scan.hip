@@ -107,8 +107,9 @@ __device__ __forceinline__ void bright_cells_block(const BrightArgs& a, const in
     const uint2* __restrict__ reach = a.reach + (size_t)slot * n;
     const uint8_t* __restrict__ cflags = a.cflags + (size_t)slot * n;
     uint32_t* __restrict__ rows = a.tile_rows + (size_t)image * a.n_chunks * a.n_strips * 4;
+    uint32_t* __restrict__ cols = a.tile_cols + (size_t)image * a.n_chunks * a.n_strips;
     const uint32_t base4 = (uint32_t)a.base * 0x01010101u, c8 = 8u * (uint32_t)a.base;
-    uint32_t level[2] = {0u, 0u};
+    uint32_t level[2] = {0u, 0u}, sum[2];
 #pragma unroll
     for (int u = 0; u < 2; u++) {
         uint32_t acc = 0;
@@ -124,7 +125,7 @@ __device__ __forceinline__ void bright_cells_block(const BrightArgs& a, const in
             }
         }
         if (MAP) level[u] = in_range[u] ? hot_level(a, acc) : 0u;
-        else mark_hot_cell(a, reach, cflags, rows, ci[u], acc);
+        sum[u] = acc;
         if (a.probe && (image & 15) == 0) { // wave-uniform, rare: which base would leave fewer hot cells?
             const uint32_t alt4 = (uint32_t)a.base_alt * 0x01010101u, alt8 = 8u * (uint32_t)a.base_alt;
             uint32_t acc2 = 0;
@@ -140,6 +141,11 @@ __device__ __forceinline__ void bright_cells_block(const BrightArgs& a, const in
                 atomicAdd(&a.probe[PROBE_STRIDE * (bx & 127) + 1], (uint32_t)n_alt);
             }
         }
+    }
+    // (the hot cells mark their tiles once both sums stand: the frame bytes need no registers beside that rare path's)
+    if (!MAP) {
+        mark_hot_cell(a, reach, cflags, rows, cols, ci[0], sum[0]);
+        mark_hot_cell(a, reach, cflags, rows, cols, ci[1], sum[1]);
     }
     if (MAP) {
         // The hot map: two bits per cell in cell order, so the 128 cells of a wave are 8 whole words (WIDE: consecutive lanes hold
@@ -176,12 +182,12 @@ __device__ __forceinline__ void bright_cells_block(const BrightArgs& a, const in
 // at 8 markers per frame, 1.133 at 32: most scan waves carry a hot cell then).
 // The hot cells of a marker lie in the same few waves and reach the same one or two tiles, and a memory atomic costs what
 // it costs whether it changes anything or not (the first version issued four per hot cell and tile: 4 M of them per batch
-// at 8 markers, 0.29 ms; 0.89 ms at 32): the wave first merges its cells' rectangles per tile in a 32-entry table in LDS (tag
-// = tile; a collision goes to memory directly) and then widens each tile it touched once.
+// at 8 markers, 0.29 ms; 0.89 ms at 32): the wave first merges its cells' rectangles, and the byte columns they overlap, per tile in
+// a 32-entry table in LDS (tag = tile; a collision goes to memory directly) and then widens each tile it touched once.
 __global__ __launch_bounds__(256) void mark_tiles_kernel(BrightArgs a)
 {
     __shared__ uint16_t s_list[4][1024];
-    __shared__ uint32_t s_tab[4][32][5]; // tile | first row | last row | first column | last column
+    __shared__ uint32_t s_tab[4][32][6]; // tile | first row | last row | first column | last column | column bits
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     // a wave takes 256 consecutive words (4 per lane) of one image at a time; with a fixed grid (a few workgroups per CU) the
     // waves go on to further pieces: few workgroups to place beside another batch's scan, which holds every wave slot of the chip
@@ -200,20 +206,25 @@ __global__ __launch_bounds__(256) void mark_tiles_kernel(BrightArgs a)
 #pragma unroll
     for (int k = 0; k < 4; k++)
         if (wk[k] != 0u) hm[wave_word0 + 64 * k + lane] = 0u; // the map is all zeros again for the next batch's scan
-    uint32_t (*tab)[5] = s_tab[wv];
-    if (lane < 32) { tab[lane][0] = 0xffffffffu; tab[lane][1] = 0xffffffffu; tab[lane][2] = 0u; tab[lane][3] = 0xffffffffu; tab[lane][4] = 0u; }
+    uint32_t (*tab)[6] = s_tab[wv];
+    if (lane < 32) { tab[lane][0] = 0xffffffffu; tab[lane][1] = 0xffffffffu; tab[lane][2] = 0u; tab[lane][3] = 0xffffffffu; tab[lane][4] = 0u; tab[lane][5] = 0u; }
     const int slot = image % a.cam_mod;
     const uint2* __restrict__ reach = a.reach + (size_t)slot * n_cells;
     const uint8_t* __restrict__ cflags = a.cflags + (size_t)slot * n_cells;
     uint32_t* __restrict__ rows = a.tile_rows + (size_t)image * a.n_chunks * a.n_strips * 4;
-    // widen one tile's box in memory (a box that already holds the rectangle needs no atomics)
-    auto widen = [&](int t, uint32_t ya, uint32_t yb, uint32_t xa, uint32_t xb) __attribute__((always_inline)) {
+    uint32_t* __restrict__ cols = a.tile_cols + (size_t)image * a.n_chunks * a.n_strips;
+    // widen one tile's box in memory and mark its columns (a box that already holds the rectangle, and a column word that holds
+    // its columns, need no atomics)
+    auto widen = [&](int t, uint32_t ya, uint32_t yb, uint32_t xa, uint32_t xb, uint32_t m) __attribute__((always_inline)) {
         const uint4 cur = *(const uint4*)(rows + 4 * t);
-        if (cur.x <= ya && cur.y >= yb && cur.z <= xa && cur.w >= xb) return;
-        atomicMin(&rows[4 * t], ya);
-        atomicMax(&rows[4 * t + 1], yb);
-        atomicMin(&rows[4 * t + 2], xa);
-        atomicMax(&rows[4 * t + 3], xb);
+        const uint32_t have = cols[t];
+        if (!(cur.x <= ya && cur.y >= yb && cur.z <= xa && cur.w >= xb)) {
+            atomicMin(&rows[4 * t], ya);
+            atomicMax(&rows[4 * t + 1], yb);
+            atomicMin(&rows[4 * t + 2], xa);
+            atomicMax(&rows[4 * t + 3], xb);
+        }
+        if ((have & m) != m) atomicOr(&cols[t], m);
     };
 #pragma unroll 1
     for (int k = 0; k < 4; k++) {
@@ -253,12 +264,14 @@ __global__ __launch_bounds__(256) void mark_tiles_kernel(BrightArgs a)
                         for (int ch = ch0; ch <= ch1; ch++)
                             for (int st = st0; st <= st1; st++) {
                                 const int t = ch * a.n_strips + st, q = t & 31;
+                                const uint32_t m = tile_col_bits(st, xa, xb);
                                 const uint32_t old = atomicCAS(&tab[q][0], 0xffffffffu, (uint32_t)t);
                                 if (old == 0xffffffffu || old == (uint32_t)t) {
                                     atomicMin(&tab[q][1], (uint32_t)ya); atomicMax(&tab[q][2], (uint32_t)yb);
                                     atomicMin(&tab[q][3], (uint32_t)xa); atomicMax(&tab[q][4], (uint32_t)xb);
+                                    atomicOr(&tab[q][5], m);
                                 } else
-                                    widen(t, (uint32_t)ya, (uint32_t)yb, (uint32_t)xa, (uint32_t)xb);
+                                    widen(t, (uint32_t)ya, (uint32_t)yb, (uint32_t)xa, (uint32_t)xb, m);
                             }
                     }
                 }
@@ -267,7 +280,7 @@ __global__ __launch_bounds__(256) void mark_tiles_kernel(BrightArgs a)
         __builtin_amdgcn_s_waitcnt(0xc07f);
         __builtin_amdgcn_wave_barrier(); // (the list is rewritten by the next k)
     }
-    if (lane < 32 && tab[lane][0] != 0xffffffffu) widen((int)tab[lane][0], tab[lane][1], tab[lane][2], tab[lane][3], tab[lane][4]);
+    if (lane < 32 && tab[lane][0] != 0xffffffffu) widen((int)tab[lane][0], tab[lane][1], tab[lane][2], tab[lane][3], tab[lane][4], tab[lane][5]);
     __builtin_amdgcn_s_waitcnt(0xc07f);
     __builtin_amdgcn_wave_barrier(); // (the table is initialised anew for the wave's next piece)
     }

@@ -1,8 +1,9 @@
 // blob_settle.hip -- between the streaming scan and the two filter kernels of the sparse path: settle_tiles_kernel, one thread per
 // (tile, image), turns the box the scan left on the tile (reachable mask rows and columns) into work items of a bounded size in ONE
 // global list (box_filter_kernel, blob_boxes.hip) -- or, a wide box, into entries of the wide-tile list that the sliding row pipeline
-// works through (blob_rows.hip) --, clears what the previous batch left in the mask where this batch will not write, and empties the
-// next batch's boxes.  The records it writes (items, wide-tile entries, the tiles' regions) are defined in kernels.h.
+// works through (blob_rows.hip); a wide box with empty columns between its markers is cut at them into items after all --, clears
+// what the previous batch left in the mask where this batch will not write, and empties the next batch's boxes and column words.
+// The records it writes (items, wide-tile entries, the tiles' regions) are defined in kernels.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "kernels.h"
@@ -168,11 +169,60 @@ __device__ __forceinline__ void emit_wide(const BoxArgs& a, bool wide, int image
     }
 }
 
-// ---- items ------------------------------------------------------------------------------------------------------------------
-// This thread's nx x ny parts of `cover` (none: nx = 0), at consecutive places of the list: one atomic per wave.
-__device__ __forceinline__ void emit_items(const BoxArgs& a, int nx, int ny, int nb, int h, int image, int tile, const Rect& cover, const Rect& exact)
+// the split tiles of this wave, counted for the read-back of the list counts (one atomic per wave that has any)
+__device__ __forceinline__ void count_split(const BoxArgs& a, bool split)
 {
-    const int lane = threadIdx.x & 63, cnt = nx * ny;
+    const uint64_t sb = __ballot(split);
+    if (sb && (threadIdx.x & 63) == 0) atomicAdd(a.n_items + SPLIT_COUNTER, (uint32_t)__popcll(sb));
+}
+
+// ---- a gapped wide tile, cut at its empty columns ------------------------------------------------------------------------------
+// The pieces a thread emits items for, 16 bits each: first and last mask byte column of the piece within its tile (5 bits each),
+// then nx and ny of its parts (3 bits each).  A tile that is not split has one piece, of which only nx and ny are used.
+__device__ __forceinline__ uint64_t piece_pack(int b0, int b1, int nx, int ny) { return (uint64_t)(b0 | b1 << 5 | nx << 10 | ny << 13); }
+
+// A tile on its way to the wide list whose column word (the byte columns some hot cell's rectangle overlaps, scan_mark.h) has empty
+// columns inside the region: the maximal runs of set columns become one piece each, IF there are at least two, every run alone
+// (its bytes x the region's h rows) would be routed to the box kernel, and the parts of all of them together are at most
+// BOX_MAX_PARTS -- what the item list's capacity rests on.  Else the tile stays a wide entry (0 is returned).
+// Why a run's items are exact by themselves (exact pixels are needed only within reach + 4, which is what
+// the rectangles are): a rectangle marks every byte column it overlaps, so it lies within ONE run; two runs have an empty byte
+// column between them, so a rectangle of another run begins at least 8 pixels beyond this run's bytes, while the patch of this
+// run's items ends 4 pixels beyond them.  No patch meets another run's rectangles: the run's byte extent (towards the tile's
+// edges the box's own extent, which reaches into the neighbour's halo) holds every exact pixel its items need.
+// In: cols = the column word, [b0, b1] = the region's byte columns within the tile.  Out: the pieces, their number.
+__device__ __forceinline__ int split_at_gaps(uint32_t cols, int b0, int b1, int h, int limit, uint64_t& pieces)
+{
+    uint32_t w = cols & ((2u << b1) - (1u << b0));
+    int n = 0, parts = 0;
+    pieces = 0;
+    while (w) {
+        const int r0 = __ffs((int)w) - 1;
+        const uint32_t up = w + (1u << r0);           // the carry runs through the run's bits
+        const int r1 = (up ? __ffs((int)up) - 1 : 32) - 1;
+        w &= up;                                       // the run is gone
+        int nx, ny;
+        choose_split(r1 - r0 + 1, h, nx, ny);
+        if (n == BOX_MAX_PARTS || 2 * (r1 - r0 + 1) + 2 * nx >= limit) return 0;
+        pieces |= piece_pack(r0, r1, nx, ny) << (16 * n);
+        n++; parts += nx * ny;
+    }
+    return (n >= 2 && parts <= BOX_MAX_PARTS) ? n : 0;
+}
+
+// ---- items ------------------------------------------------------------------------------------------------------------------
+// This thread's pieces (none: n_pieces = 0), each as its nx x ny parts, at consecutive places of the list: one atomic per wave.
+// A tile that is not split has one piece: `cover`, with its exact pixels from `exact`.  The pieces of a split tile (split_at_gaps)
+// are runs of byte columns of the tile [tile_x0, tile_x1]: a run covers its columns x the rows of `cover` and takes its exact pixels from
+// the rows of `exact` and its own byte extent -- where it holds the tile's first / last byte, from the extent of `exact` on that
+// side, which is not clipped to the tile: a marker that straddles the tile's edge needs its halo pixels exact.
+__device__ __forceinline__ void emit_items(const BoxArgs& a, int n_pieces, uint64_t pieces, bool split, int image, int tile, const Rect& cover,
+                                           const Rect& exact, int tile_x0, int tile_x1)
+{
+    static_assert(BOX_MAX_PARTS <= 4, "a thread's pieces are packed into one 64-bit word");
+    const int lane = threadIdx.x & 63;
+    int cnt = 0;
+    for (int k = 0; k < n_pieces; k++) cnt += (int)((pieces >> (16 * k + 10)) & 7u) * (int)((pieces >> (16 * k + 13)) & 7u);
     int incl = cnt; // inclusive prefix sum over the wave
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
@@ -186,21 +236,32 @@ __device__ __forceinline__ void emit_items(const BoxArgs& a, int nx, int ny, int
     base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
     uint32_t o = base + (uint32_t)(incl - cnt);
     if (!cnt) return;
-    const int pb = (nb + nx - 1) / nx, ph = (h + ny - 1) / ny;
-    for (int jy = 0; jy < ny; jy++)
-        for (int jx = 0; jx < nx; jx++, o++) {
-            const int x0 = cover.x0 + 8 * pb * jx, x1 = imin(x0 + 8 * pb - 1, cover.x1);
-            const int y0 = cover.y0 + ph * jy, y1 = imin(y0 + ph - 1, cover.y1);
-            if (o >= a.cap_items) continue; // cannot happen: the list holds BOX_MAX_PARTS items per tile
-            // (a part may come out empty by the rounding of the split: stored as such, the consumer skips it)
-            a.items[o] = BoxItem::make(image, tile, x0, x1, y0, y1, exact.x0, exact.x1, exact.y0, exact.y1);
+    for (int k = 0; k < n_pieces; k++) {
+        const uint32_t p = (uint32_t)(pieces >> (16 * k)) & 0xffffu;
+        const int nx = (int)((p >> 10) & 7u), ny = (int)((p >> 13) & 7u);
+        Rect c = cover, e = exact;
+        if (split) {
+            const int r0 = (int)(p & 31u), r1 = (int)((p >> 5) & 31u);
+            c.x0 = tile_x0 + 8 * r0; c.x1 = imin(tile_x0 + 8 * r1 + 7, tile_x1);
+            e.x0 = r0 == 0 ? exact.x0 : c.x0; e.x1 = r1 == ((tile_x1 - tile_x0) >> 3) ? exact.x1 : c.x1;
         }
+        const int nb = (c.x1 - c.x0 + 8) >> 3, h = c.y1 - c.y0 + 1;
+        const int pb = (nb + nx - 1) / nx, ph = (h + ny - 1) / ny;
+        for (int jy = 0; jy < ny; jy++)
+            for (int jx = 0; jx < nx; jx++, o++) {
+                const int x0 = c.x0 + 8 * pb * jx, x1 = imin(x0 + 8 * pb - 1, c.x1);
+                const int y0 = c.y0 + ph * jy, y1 = imin(y0 + ph - 1, c.y1);
+                if (o >= a.cap_items) continue; // cannot happen: the list holds BOX_MAX_PARTS items per tile
+                // (a part may come out empty by the rounding of the split: stored as such, the consumer skips it)
+                a.items[o] = BoxItem::make(image, tile, x0, x1, y0, y1, e.x0, e.x1, e.y0, e.y1);
+            }
+    }
 }
 
 } // namespace
 
-// A driver over the steps above: thread -> tile, the scan's box, the cluster decision, the routing (here), the record and the
-// clearing of the previous region, the wide entries, the items.
+// A driver over the steps above: thread -> tile, the scan's box, the cluster decision, the routing (here; the cut of a gapped wide
+// tile: split_at_gaps), the record and the clearing of the previous region, the wide entries, the items.
 __global__ __launch_bounds__(256) void settle_tiles_kernel(BoxArgs a)
 {
     if (a.zero8 && blockIdx.x == 0 && threadIdx.x < 8) a.zero8[threadIdx.x] = 0u; // the contour stage's walk counters
@@ -208,7 +269,7 @@ __global__ __launch_bounds__(256) void settle_tiles_kernel(BoxArgs a)
     const TileOfThread t = tile_of_thread(a, n_all);
     if (t.valid && !a.dense && t.image < n_all) { // the buffer the NEXT batch's scan will widen -- read by the previous batch's settle -- is emptied
         const uint4 nxt = *(const uint4*)(a.tile_rows_next + 4 * t.idx);
-        if (nxt.x <= nxt.y) *(uint4*)(a.tile_rows_next + 4 * t.idx) = NO_BOX;
+        if (nxt.x <= nxt.y) { *(uint4*)(a.tile_rows_next + 4 * t.idx) = NO_BOX; a.tile_cols_next[t.idx] = 0u; }
     }
     const bool valid = t.valid && t.image < a.n_images; // (images beyond the batch: nothing else happens for them)
     const int tile = t.chunk * a.n_strips + t.strip;
@@ -223,23 +284,42 @@ __global__ __launch_bounds__(256) void settle_tiles_kernel(BoxArgs a)
     Rect cover = out, exact = box; // region the emitted items cover; box they take their exact pixels from
     const bool emits = marked && ((!a.dense && a.cluster) ? cluster_decision(a, t, cover, exact) : true);
     // routing: cut into items for the box kernel, or -- a wide box -- as the tile's rows through the sliding row pipeline, which
-    // then writes the whole width of the tile
-    int nx = 0, ny = 0, nb = 0, h = 0;
-    bool wide = false;
+    // then writes the whole width of the tile; or, a wide box with empty columns in it, cut at them into items after all
+    // (split_at_gaps): the region stays the box's, first run to last, and nobody writes the gaps
+    int n_pieces = 0;
+    uint64_t pieces = 0;
+    bool wide = false, split = false;
     if (marked) {
-        nb = (cover.x1 - cover.x0 + 8) >> 3; h = cover.y1 - cover.y0 + 1;
+        int nx, ny;
+        const int nb = (cover.x1 - cover.x0 + 8) >> 3, h = cover.y1 - cover.y0 + 1;
         choose_split(nb, h, nx, ny);
         const int limit = ((a.remap_bits >> (t.image % a.cam_mod)) & 1ull) ? a.wide_quads_remap : a.wide_quads_identity;
         const bool own = cover.x0 == out.x0 && cover.x1 == out.x1 && cover.y0 == out.y0 && cover.y1 == out.y1; // no cluster item
         wide = emits && own && a.wide_tiles != nullptr && 2 * nb + 2 * nx >= limit;
+        if (wide && a.wide_split && a.wide_bands == 1 && !a.dense) {
+            n_pieces = split_at_gaps(a.tile_cols[t.idx], (out.x0 - tile_x0) >> 3, (out.x1 - tile_x0) >> 3, h, limit, pieces);
+            split = n_pieces != 0;
+            wide = !split;
+        }
         if (wide) { out.x0 = tile_x0; out.x1 = tile_x1; cover.x0 = out.x0; cover.x1 = out.x1; }
+        else if (emits && !split) { n_pieces = 1; pieces = piece_pack(0, 0, nx, ny); }
     }
     uint32_t prev_x = 1u, prev_y = 1u; // empty
-    const bool need_clear = valid && record_region(a, t, marked, out, box, prev_x, prev_y);
+    bool need_clear = valid && record_region(a, t, marked, out, box, prev_x, prev_y);
+    // a split tile writes its runs only: what the previous batch left is cleared unless it lies inside ONE run's cover (the items
+    // write later on this stream, so clearing the whole previous region is safe)
+    if (split && span_first(prev_x) <= span_last(prev_x)) {
+        need_clear = true;
+        for (int k = 0; k < n_pieces; k++) {
+            const uint32_t p = (uint32_t)(pieces >> (16 * k));
+            const int x0 = tile_x0 + 8 * (int)(p & 31u), x1 = imin(tile_x0 + 8 * (int)((p >> 5) & 31u) + 7, tile_x1);
+            if (x0 <= span_first(prev_x) && span_last(prev_x) <= x1 && out.y0 <= span_first(prev_y) && span_last(prev_y) <= out.y1) need_clear = false;
+        }
+    }
     clear_previous(a, need_clear, prev_x, prev_y, t.image);
     emit_wide(a, wide, t.image, tile, out.y0, out.y1);
-    const bool items = emits && !wide;
-    emit_items(a, items ? nx : 0, items ? ny : 0, nb, h, t.image, tile, cover, exact);
+    count_split(a, split);
+    emit_items(a, n_pieces, pieces, split, t.image, tile, cover, exact, tile_x0, tile_x1);
 }
 
 void launch_settle_tiles(const BoxArgs& a, hipStream_t s)

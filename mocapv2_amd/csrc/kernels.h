@@ -107,6 +107,7 @@ struct BayerArgs {
 constexpr int BOX_HCAP = MOCAP_BOX_HCAP; // quad-rows (4 pixels x 1 row) of one item's patch (halving it for twice the waves per CU: 0.63 against 0.53 ms)
 constexpr int BOX_SCAP = MOCAP_BOX_SCAP; // bytes of source pixels staged in LDS per item (>= (BOX_HCAP + 64) * 4: the counts alias it)
 constexpr int BOX_MAX_PARTS = MOCAP_BOX_MAX_PARTS;  // items a tile is cut into at most (a whole 240 x 68 tile: 2 x 2)
+constexpr int SPLIT_COUNTER = 12;                   // word of the counter block (BoxArgs::n_items) that counts the split tiles of a batch
 // The span records settle writes and the box kernel, the row pipeline's list form and the contour stage read: a closed range
 // [a, b] of columns or rows in one word, a | b << 16 (a > b: empty).
 __host__ __device__ __forceinline__ uint32_t span_pack(int a, int b) { return (uint32_t)a | ((uint32_t)b << 16); }
@@ -155,12 +156,17 @@ struct BoxArgs {
     uint32_t* tile_rows;        // [n_images][n_chunks][n_strips][4]: the scan's boxes of this batch (first / last row, first / last
                                 //   column; (0xffffffff, 0) = none), read-only for settle
     uint32_t* tile_rows_next;   // the same array for the next batch (the two alternate): emptied by settle
+    const uint32_t* tile_cols;  // [n_images][n_chunks][n_strips]: the scan's column word of each tile of this batch (bit b, 0..29: a hot cell's
+                                //   rectangle overlaps mask byte column b of the tile, clipped to it; 0 = not marked), read-only for settle
+    uint32_t* tile_cols_next;   // the same array for the next batch: emptied by settle wherever it empties tile_rows_next
+    int wide_split;             // 1 = a wide tile whose column word has gaps is cut into one set of items per run of columns (the host decides: tuning.def)
     int n_clear;                // images whose boxes tile_rows_next may still hold (an earlier, larger batch): emptied too
     int cluster;                // 1 = a box spanning tiles that all hold it becomes one item (A/B switch)
     uint32_t* cur_box;          // [n_images][n_chunks][n_strips][4]: words 0-1 the tile's output region of this batch
                                 //   (x0 | x1 << 16, y0 | y1 << 16; x0 > x1 = none) = what the mask may hold there; words 2-3 the
                                 //   scan's box (not clipped to the tile)
-    BoxItem* items; uint32_t* n_items; uint32_t cap_items; // n_items[0] = items in the list; n_items[16 + 16 x] = head of run x (box kernel)
+    BoxItem* items; uint32_t* n_items; uint32_t cap_items; // n_items[0] = items in the list; n_items[16 + 16 x] = head of run x (box kernel);
+                                //   n_items[SPLIT_COUNTER] = wide tiles cut at their column gaps
     uint64_t* timing;           // optional [grid][6] phase clock of the box kernel (MOCAP_BOX_TIMING=1, a debugging aid), else null
     int prio;                   // 1 = raise the wave priority of the box kernel (A/B switch)
     int stage_bytes;            // LDS bytes the source staging may use (BOX_SCAP; smaller values are a test switch)
@@ -273,6 +279,7 @@ struct BrightArgs {
     int hot_words;                // words per image: hot_map_words(H, W, wide)
     uint32_t* zero_counters;      // not null: 256 words (the context's counter block) that workgroup 0 of the scan zeroes -- in place of a fill launch
     int mark_grid;                // > 0: workgroups of mark_tiles_kernel (its waves loop over the map); 0 = one piece per wave
+    uint32_t* tile_cols;          // [n_images][n_chunks][n_strips] beside tile_rows: bit b = some hot cell's rectangle overlaps mask byte column b of the tile
 };
 int hot_map_words(int H, int W, int wide);
 void launch_mark_tiles(const BrightArgs& a, hipStream_t s); // hot map -> tile boxes (tile_rows), behind launch_bright_cells

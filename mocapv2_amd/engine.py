@@ -828,6 +828,12 @@ class MocapContext:
         _abi.check(self.lib.mocap_tile_stats(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def list_stats(self):
+        """(box items, wide-tile entries, wide tiles split at their empty columns) of the most recent batch's sparse path"""
+        a, b, s = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        _abi.check(self.lib.mocap_list_stats(self._h, C.byref(a), C.byref(b), C.byref(s)))
+        return a.value, b.value, s.value
+
     def profile(self, on=True):
         _abi.check(self.lib.mocap_profile_enable(self._h, int(on)))
 

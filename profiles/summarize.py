@@ -33,7 +33,7 @@ def pmc(path, counter, dst):
     return {k: sum(v) / len(v) for k, v in acc.items()}, {k: len(v) for k, v in acc.items()}
 
 
-ROUND = "r05"
+ROUND = "r22"
 SHORT = ("bright_cells_kernel", "mark_tiles_kernel", "settle_tiles_kernel", "box_filter_kernel", "filter_rows_staged_kernel", "filter_mask_kernel")
 CONTOUR = ("contours_kernel<1", "contour_follow_kernel", "contours_kernel<2") # (candidates, follow: both passes, tree: both passes)
 
