@@ -494,6 +494,36 @@ MOCAP_API int mocap_rig_linearize_robust(mocap_ctx_t ctx, int C, int N, int n_ob
                                          double* S_dev, double* rhs_dev, int32_t* status_dev, int loss, double loss_scale,
                                          void* stream);
 
+/* mocap_rig_bundle_adjust_robust with the cameras' lenses among the unknowns: a wand capture, thousands of points through the
+ * whole volume seen by many cameras, constrains them far better than the board views mocap_intrinsics_calibrate had (new
+ * symbols, MOCAP_ABI_VERSION stays 7; definition in DESIGN.md section 2, restated by tests/rig_selfcal_ref.py).  Every camera,
+ * camera 0 included, gains kd = (fx, fy, cx, cy, k1, k2, p1, p2, k3), in mocap_intrinsics_calibrate's order; a camera's block
+ * is 15 wide, kd's 9 then the pose's 6, and the reduced system 15 C square.  K and dist of mocap_set_cameras are neither read
+ * nor changed, and no cameras need to be set.
+ *   kd_dev                float64 [C][9] in / out
+ *   refine_mask_host      int32 [C], HOST, copied before the call returns: bit i set = parameter i of kd is free for that
+ *                         camera.  A fixed parameter comes back with the bits it had.  Mask 0 for every camera is
+ *                         mocap_rig_bundle_adjust_robust's problem at the lenses kd_dev holds
+ * A mask with bits above 8, or a kd entry that is not finite or an fx, fy <= 0, is MOCAP_E_INVALID and nothing is launched
+ * (kd_dev is read back for the check: the call waits for `stream` once, before it enqueues anything).  A camera whose mask is
+ * not 0 needs at least twice as many observations as its mask has bits, else the status is MOCAP_RIG_E_LAYOUT.  A negative
+ * status leaves kd_dev, poses_dev and points_dev as they were.  Every other argument, the history, the result, the gauge on
+ * return and the rules on streams and scratch are mocap_rig_bundle_adjust_robust's.
+ * mocap_rig_linearize_intrinsics, for tests: the pieces of one iteration as mocap_rig_linearize_robust's, with gradient_dev
+ * [15 C + 3 N] (the cameras' 15 each, camera 0 first; then the points), S_dev [15 C][15 C] and rhs_dev [15 C].  A fixed
+ * parameter's row and column of S are zero but for a 1 on the diagonal, its gradient and rhs entries are 0. */
+MOCAP_API int mocap_rig_bundle_adjust_intrinsics(mocap_ctx_t ctx, int C, int N, int n_obs, const int32_t* obs_offset_dev,
+                                                 const int32_t* obs_cam_dev, const double* obs_uv_dev, double* kd_dev,
+                                                 const int32_t* refine_mask_host, double* poses_dev, double* points_dev,
+                                                 int max_iters, double ftol, double lambda0, double* history_dev,
+                                                 double* result_dev, int loss, double loss_scale, double* obs_err_dev,
+                                                 double* obs_weight_dev, void* stream);
+MOCAP_API int mocap_rig_linearize_intrinsics(mocap_ctx_t ctx, int C, int N, int n_obs, const int32_t* obs_offset_dev,
+                                             const int32_t* obs_cam_dev, const double* obs_uv_dev, const double* kd_dev,
+                                             const int32_t* refine_mask_host, const double* poses_dev, const double* points_dev,
+                                             double lambda, double* cost_dev, double* gradient_dev, double* S_dev, double* rhs_dev,
+                                             int32_t* status_dev, int loss, double loss_scale, void* stream);
+
 /* Intrinsic calibration of every camera of a rig from planar-board corner lists: per camera fx, fy, cx, cy, k1, k2, p1, p2, k3
  * and one board -> camera pose per view, by Levenberg-Marquardt on the device (Schur complement on the views, analytic
  * Jacobian, Marquardt scaling, Nielsen's damping rule; FP64 throughout; definition in DESIGN.md section 2, restated by

@@ -69,6 +69,8 @@ SIGNATURES = {
     "mocap_rig_linearize": [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp, _vp, _vp],
     "mocap_rig_bundle_adjust_robust": [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _d, _d, _vp, _vp, _i, _d, _vp, _vp, _vp],
     "mocap_rig_linearize_robust": [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp, _vp, _i, _d, _vp],
+    "mocap_rig_bundle_adjust_intrinsics": [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _ip, _vp, _vp, _i, _d, _d, _vp, _vp, _i, _d, _vp, _vp, _vp],
+    "mocap_rig_linearize_intrinsics": [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _ip, _vp, _vp, _d, _vp, _vp, _vp, _vp, _vp, _i, _d, _vp],
     "mocap_intrinsics_calibrate": [_vp, _i, _ip, _ip, _vp, _vp, _ip, _i, _i, _d, _d, _vp, _vp, _vp, _vp, _vp, _vp],
     "mocap_intrinsics_linearize": [_vp, _i, _ip, _ip, _vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp, _vp, _vp],
     "mocap_triangulate_batch": [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp],

@@ -17,7 +17,9 @@ What is batched that the reference loops over:
 Beyond the reference (whose calibration is two-camera at heart): `calibrate_rig` = `rig_initial_poses` (all camera pairs'
 fundamental matrices in one RANSAC call, a spanning tree with a common scale) + `bundle_adjust_rig` (all poses and all points
 on the GPU over exactly the observations that exist, csrc/rig_ba.hip; definition in DESIGN.md section 2; with
-loss="cauchy" robust against the outliers of a real capture, which it reports per observation and refits without).
+loss="cauchy" robust against the outliers of a real capture, which it reports per observation and refits without; with
+`bundle_adjust_rig_intrinsics` / `calibrate_rig_intrinsics` the cameras' K and distortion are unknowns of the same adjustment,
+csrc/rig_selfcal.hip).
 `calibrate_intrinsics` supplies the camera_params all of these take: K and distortion of every camera from board views
 (the reference's CalculateCameraIntrinsic.py:58, cv2.calibrateCamera, batched over the rig; csrc/intrinsics.hip).
 Image capture and the plotting / JSON writing of that script are outside the path.  `calculate_extrinsics` is the
@@ -447,6 +449,35 @@ def _check_loss(loss, loss_scale, inlier_weight):
     return True
 
 
+# what refine_intrinsics names: bit i frees parameter i of (fx, fy, cx, cy, k1, k2, p1, p2, k3)
+REFINE_MASKS = {"focal": 0x003, "focal+center": 0x00F, "focal+center+radial2": 0x03F, "all": 0x1FF}
+
+
+def _refine_masks(refine_intrinsics, Cn):
+    """int32 [C] lens masks of bundle_adjust_rig_intrinsics' refine_intrinsics (None: None), after the checks that need no GPU"""
+    if refine_intrinsics is None:
+        return None
+    if isinstance(refine_intrinsics, str):
+        if refine_intrinsics not in REFINE_MASKS:
+            raise ValueError(f"refine_intrinsics {refine_intrinsics!r}: None, one of {sorted(REFINE_MASKS)}, or an int mask per camera")
+        refine_intrinsics = REFINE_MASKS[refine_intrinsics]
+    masks = np.asarray(refine_intrinsics)
+    if masks.dtype.kind not in "iu" or masks.ndim > 1 or (masks.ndim == 1 and len(masks) != Cn):
+        raise ValueError(f"refine_intrinsics: one int mask, or one per camera ({Cn})")
+    masks = np.ascontiguousarray(np.broadcast_to(masks, (Cn,)), np.int64)
+    if ((masks < 0) | (masks > 0x1FF)).any():
+        raise ValueError("refine_intrinsics: a mask has bits 0..8 (fx, fy, cx, cy, k1, k2, p1, p2, k3)")
+    if Cn == 2 and (masks & ~REFINE_MASKS["focal"]).any():
+        raise ValueError("refine_intrinsics: two views determine no more than the focal lengths ('focal', mask 0x003)")
+    return masks.astype(np.int32)
+
+
+def _camera_entries(kd):
+    """camera_params entries, as calibrate_intrinsics returns and save_intrinsics writes them, from kd [C][9]"""
+    return [{"intrinsic_matrix": np.array([[k[0], 0.0, k[2]], [0.0, k[1], k[3]], [0.0, 0.0, 1.0]]), "distortion_coef": k[4:].copy()}
+            for k in np.asarray(kd, float)]
+
+
 def bundle_adjust_rig(image_points, valid, poses, camera_params, points=None, max_iters=50, ftol=1e-12, ctx=None, loss=None,
                       loss_scale=None, inlier_weight=0.25, refit=True):
     """Bundle adjustment of ALL cameras of a rig and all 3-D points on the GPU, over exactly the observations that exist
@@ -473,9 +504,35 @@ def bundle_adjust_rig(image_points, valid, poses, camera_params, points=None, ma
     points still used (the rejected ones included), obs_weight and outliers stay the robust stage's.  refit=False: cost is
     1/2 sum rho and rms_px is taken over the observations that are not outliers.  cost_initial is the robust stage's, the 1/2
     sum rho of the start.  The defaults (loss=None) are the plain adjustment with the keys above and nothing else."""
+    return _bundle_adjust_rig(image_points, valid, poses, camera_params, points, max_iters, ftol, ctx, loss, loss_scale, inlier_weight, refit)
+
+
+def bundle_adjust_rig_intrinsics(image_points, valid, poses, camera_params, points=None, max_iters=50, ftol=1e-12, ctx=None, loss=None,
+                                 loss_scale=None, inlier_weight=0.25, refit=True, refine_intrinsics="focal+center+radial2"):
+    """`bundle_adjust_rig` with the cameras' lenses among the unknowns (engine.MocapContext.rig_bundle_adjust_intrinsics ->
+    mocap_rig_bundle_adjust_intrinsics; definition in DESIGN.md section 2).  Thousands of wand points through the whole volume
+    hold the lenses better than the board views camera_params came from.  Every argument but the last as `bundle_adjust_rig`'s.
+    refine_intrinsics: which lens parameters of every camera, camera 0 included, join the unknowns: "focal" (fx, fy),
+    "focal+center" (+ cx, cy), "focal+center+radial2" (+ k1, k2), "all" (+ p1, p2, k3), or an int mask (bit i frees parameter
+    i of fx, fy, cx, cy, k1, k2, p1, p2, k3) for all cameras or one per camera.  Two cameras determine no more than "focal": a
+    wider mask raises ValueError.  Returns `bundle_adjust_rig`'s dict plus camera_params (entries as `calibrate_intrinsics`
+    returns and `save_intrinsics` writes them: the refined lenses; a parameter that was not free has the bits it came with)
+    and intrinsics_start (the same form: what camera_params held, so that the caller sees what moved).  With loss="cauchy" both
+    stages move the lenses, the refit under the same mask from the robust stage's result."""
+    if refine_intrinsics is None:
+        raise ValueError("refine_intrinsics: a name of REFINE_MASKS or int masks (bundle_adjust_rig leaves the lenses alone)")
+    return _bundle_adjust_rig(image_points, valid, poses, camera_params, points, max_iters, ftol, ctx, loss, loss_scale, inlier_weight, refit,
+                              refine_intrinsics)
+
+
+def _bundle_adjust_rig(image_points, valid, poses, camera_params, points, max_iters, ftol, ctx, loss, loss_scale, inlier_weight, refit,
+                       refine_intrinsics=None):
+    """The one body of bundle_adjust_rig and bundle_adjust_rig_intrinsics (refine_intrinsics=None: the lenses stay)"""
     robust = _check_loss(loss, loss_scale, inlier_weight)
     ip, vis, K, d = _rig_inputs(image_points, valid, camera_params)
     Cn, N = vis.shape
+    masks = _refine_masks(refine_intrinsics, Cn)
+    lens = {} if masks is None else {"intrinsics": np.c_[K[:, 0, 0], K[:, 1, 1], K[:, 0, 2], K[:, 1, 2], d], "refine": masks}
     if len(poses) != Cn:
         raise ValueError(f"{len(poses)} poses for {Cn} cameras")
     ctx = ctx or default_context()
@@ -511,11 +568,17 @@ def bundle_adjust_rig(image_points, valid, poses, camera_params, points=None, ma
     ctx.set_cameras(K, d, R, t)
     start = np.c_[R.reshape(Cn, 9), t]
     extra = {}
+
+    def adjust(offset, c_idx, uv, poses, pts, **loss_kw):
+        if lens:
+            return ctx.rig_bundle_adjust_intrinsics(offset, c_idx, uv, lens["intrinsics"], lens["refine"], poses, pts, max_iters, ftol, **loss_kw)
+        return ctx.rig_bundle_adjust(offset, c_idx, uv, poses, pts, max_iters, ftol, **loss_kw)
+
     if not robust:
-        out = ctx.rig_bundle_adjust(offset, c_idx, uv, start, X[sel], max_iters, ftol)
+        out = adjust(offset, c_idx, uv, start, X[sel])
         rms = float(np.sqrt(out["cost"] / len(uv)))
     else:
-        out = ctx.rig_bundle_adjust(offset, c_idx, uv, start, X[sel], max_iters, ftol, loss=loss, loss_scale=loss_scale)
+        out = adjust(offset, c_idx, uv, start, X[sel], loss=loss, loss_scale=loss_scale)
         err, weight = np.full((Cn, N), np.nan), np.full((Cn, N), np.nan)
         err[c_idx, sel[n_idx]], weight[c_idx, sel[n_idx]] = out["obs_err"], out["obs_weight"]
         with np.errstate(invalid="ignore"):
@@ -533,13 +596,16 @@ def bundle_adjust_rig(image_points, valid, poses, camera_params, points=None, ma
             sel = np.flatnonzero(used)
             offset, c_idx, n_idx, uv = _observation_problem(ip, kept, sel)
             # (the robust result is a state of the device's convention: camera 0 the world frame, mirrored if the start was)
-            out = ctx.rig_bundle_adjust(offset, c_idx, uv, stage["poses"], X1[sel], max_iters, ftol)
+            if lens:
+                lens["intrinsics"] = stage["intrinsics"]
+            out = adjust(offset, c_idx, uv, stage["poses"], X1[sel])
             out["cost_initial"] = stage["cost_initial"]
             rms = float(np.sqrt(out["cost"] / len(uv)))
             extra.update(robust_cost=stage["cost"], robust_iterations=stage["iterations"], robust_status=stage["status"])
             Xf = np.full((N, 3), np.nan)
             Xf[sel] = out["points"]
-            err = _residual_lengths(ip, vis, K, d, out["poses"][:, :9].reshape(Cn, 3, 3), out["poses"][:, 9:], Xf)
+            Kf, df = (K, d) if not lens else _intrinsics(_camera_entries(out["intrinsics"]), Cn)
+            err = _residual_lengths(ip, vis, Kf, df, out["poses"][:, :9].reshape(Cn, 3, 3), out["poses"][:, 9:], Xf)
         extra["obs_err_px"] = err
     Rn, tn, Xn = out["poses"][:, :9].reshape(Cn, 3, 3), out["poses"][:, 9:], out["points"]
     if mirror:
@@ -547,6 +613,9 @@ def bundle_adjust_rig(image_points, valid, poses, camera_params, points=None, ma
     pts = np.full((N, 3), np.nan)
     pts[sel] = (Xn - t0) @ R0  # back to the caller's world frame
     new = [{"R": Rn[c] @ R0, "t": (tn[c] + Rn[c] @ t0).reshape(3, 1)} for c in range(Cn)]
+    if lens:
+        extra.update(camera_params=_camera_entries(out["intrinsics"]),
+                     intrinsics_start=_camera_entries(np.c_[K[:, 0, 0], K[:, 1, 1], K[:, 0, 2], K[:, 1, 2], d]))
     return {"poses": new, "points": pts, "used": used, "cost_initial": out["cost_initial"], "cost": out["cost"], "rms_px": rms,
             "iterations": out["iterations"], "history": out["history"], "status": out["status"], "mirrored": mirror, **extra}
 
@@ -558,10 +627,29 @@ def calibrate_rig(image_points, valid, camera_params, threshold=10.0, hypotheses
     dict plus poses_initial and init (the initialisation's details); its poses and points go to `set_origin`, `set_floor` and
     `save_extrinsics` as the reference's do.  loss, loss_scale, inlier_weight, refit: `bundle_adjust_rig`'s (the RANSAC of
     the initialisation protects the start; loss="cauchy" protects the adjustment from the outliers of a real capture)."""
+    return _calibrate_rig(image_points, valid, camera_params, threshold, hypotheses, seed, max_iters, ftol, ctx, loss, loss_scale,
+                          inlier_weight, refit)
+
+
+def calibrate_rig_intrinsics(image_points, valid, camera_params, threshold=10.0, hypotheses=1000, seed=0, max_iters=50, ftol=1e-12,
+                             ctx=None, loss=None, loss_scale=None, inlier_weight=0.25, refit=True, refine_intrinsics="focal+center+radial2"):
+    """`calibrate_rig` whose adjustment also refines the lenses camera_params holds: `rig_initial_poses` on camera_params as they
+    came, then `bundle_adjust_rig_intrinsics`.  refine_intrinsics and the two keys the dict gains, camera_params (for
+    `save_intrinsics`) and intrinsics_start: `bundle_adjust_rig_intrinsics`'s."""
+    if refine_intrinsics is None:
+        raise ValueError("refine_intrinsics: a name of REFINE_MASKS or int masks (calibrate_rig leaves the lenses alone)")
+    return _calibrate_rig(image_points, valid, camera_params, threshold, hypotheses, seed, max_iters, ftol, ctx, loss, loss_scale,
+                          inlier_weight, refit, refine_intrinsics)
+
+
+def _calibrate_rig(image_points, valid, camera_params, threshold, hypotheses, seed, max_iters, ftol, ctx, loss, loss_scale, inlier_weight,
+                   refit, refine_intrinsics=None):
     _check_loss(loss, loss_scale, inlier_weight)
+    _refine_masks(refine_intrinsics, len(np.asarray(image_points)))
     ctx = ctx or default_context()
     initial, info = rig_initial_poses(image_points, valid, camera_params, threshold, hypotheses, seed, ctx, details=True)
-    out = bundle_adjust_rig(image_points, valid, initial, camera_params, None, max_iters, ftol, ctx, loss, loss_scale, inlier_weight, refit)
+    out = _bundle_adjust_rig(image_points, valid, initial, camera_params, None, max_iters, ftol, ctx, loss, loss_scale, inlier_weight, refit,
+                             refine_intrinsics)
     out["poses_initial"], out["init"] = initial, info
     return out
 

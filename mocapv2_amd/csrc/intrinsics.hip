@@ -94,10 +94,7 @@ __device__ __forceinline__ bool observe_board(const double* kd, const double* P,
     Projected o;
     const bool front = project<JAC>(m, q, P + 9, ou, ov, r, o);
     if (JAC) {
-        j0[0] = o.xd; j0[1] = 0.0; j0[2] = 1.0; j0[3] = 0.0;
-        j1[0] = 0.0; j1[1] = o.yd; j1[2] = 0.0; j1[3] = 1.0;
-        j0[4] = m.fx * (o.x * o.r2); j0[5] = m.fx * (o.x * o.r4); j0[6] = m.fx * (2.0 * o.xy); j0[7] = m.fx * o.tx; j0[8] = m.fx * (o.x * o.r6);
-        j1[4] = m.fy * (o.y * o.r2); j1[5] = m.fy * (o.y * o.r4); j1[6] = m.fy * o.ty; j1[7] = m.fy * (2.0 * o.xy); j1[8] = m.fy * (o.y * o.r6);
+        lens_columns(m, o, j0, j1);
         pose_columns(o.A[0], q, j0 + 9);
         pose_columns(o.A[1], q, j1 + 9);
     }

@@ -486,6 +486,60 @@ void launch_rig_residuals(const RigArgs& a, hipStream_t s); // behind launch_rig
 int rig_lin_blocks(int N);
 int rig_schur_chunks(int N);
 
+// bundle adjustment of a rig that also refines every camera's lens (rig_selfcal.hip): RigArgs' problem with camera blocks 15 wide
+// (kd's 9, then the pose's 6) for every camera, camera 0 included; D = 15 C.  The state record and the scalars are rig_ba.hip's.
+constexpr int SELFCAL_P = 15;                      // a camera block
+constexpr int SELFCAL_U = 120 + SELFCAL_P;         // a camera's sums of the point kernel: the upper triangle of U_c, then g_c
+constexpr int SELFCAL_BLK = SELFCAL_P * SELFCAL_P + SELFCAL_P; // a pair's sums of the Schur kernel: W_a V*^-1 W_b^T, then W_a V*^-1 g_n
+struct SelfcalArgs {
+    const int32_t* obs_offset; // [N + 1], [n_obs], [n_obs][2]: as RigArgs
+    const int32_t* obs_cam;
+    const double* obs_uv;
+    int C, N, n_obs;
+    int n_pairs, n_lin_blocks, n_chunks; // C (C + 1) / 2 pairs of cameras; workgroups of the point kernels; chunks of the Schur kernel
+    int schur_chunk;           // points of a chunk (selfcal_schur_chunk(N)): n_chunks = ceil(N / schur_chunk)
+    int loss;
+    double loss_c2;
+    double* kd_io;             // [C][9] the caller's: fx, fy, cx, cy, k1, k2, p1, p2, k3
+    double* poses_io;          // [C][12] the caller's
+    double* points_io;         // [N][3] the caller's
+    // scratch of the context
+    const int32_t* free_cols;  // [C] device copy: bit i = column i of the camera's block is free (bits 0..8 the caller's mask,
+                               //   bits 9..14 the pose: set for cameras 1.., clear for camera 0)
+    int32_t* cam_count;        // [C] observations of every camera (zeroed before the init kernel)
+    RigState* state;
+    double* kd;                // [2][C][9] current and trial state (state->cur)
+    double* poses;             // [2][C][12]
+    double* points;            // [2][N][3]
+    uint32_t* mask;            // [N] bit c: camera c sees the point
+    double* W;                 // [n_obs][45] W_nc, 15x3 row-major
+    double* Vinv;              // [N][6]
+    double* vdiag;             // [N][3]
+    double* gp;                // [N][3]
+    double* lin_part;          // [n_lin_blocks][C][SELFCAL_U]
+    double* cost_part;         // [n_lin_blocks]
+    double* schur_part;        // [n_chunks][n_pairs][SELFCAL_BLK]
+    double* S;                 // [D][D] the damped reduced camera matrix; a fixed column's diagonal entry is 1
+    double* rhs;               // [D]
+    double* gc;                // [D]
+    double* udiag;             // [D]
+    double* chol;              // [D (D + 1) / 2] the factor when it does not fit LDS
+    double* delta_c;           // [D]
+    double* upd_part;          // [n_lin_blocks][3]
+    double* scalars;           // [RIG_N_SCALARS]
+    double* history;           // [max_iters][4] the caller's (or null for a linearisation alone)
+    double* result;            // [4] the caller's
+    double* obs_err;           // [n_obs] the caller's or null
+    double* obs_weight;        // [n_obs] the caller's or null
+};
+void launch_selfcal_init(const SelfcalArgs& a, double lambda0, hipStream_t s);
+void launch_selfcal_linearize(const SelfcalArgs& a, hipStream_t s);
+void launch_selfcal_iteration(const SelfcalArgs& a, int it, int max_iters, double ftol, hipStream_t s);
+void launch_selfcal_finish(const SelfcalArgs& a, hipStream_t s);
+void launch_selfcal_residuals(const SelfcalArgs& a, hipStream_t s); // behind launch_selfcal_finish: obs_err, obs_weight
+int selfcal_lin_blocks(int N);
+int selfcal_schur_chunk(int N);
+
 // intrinsic calibration of every camera of a rig from planar-board views (intrinsics.hip): one loop, and one state record, per
 // camera; no kernel reads another camera's.  status: RIG_STOP_* / INTR_ERR_*
 using IntrState = LmState;

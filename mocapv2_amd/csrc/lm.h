@@ -1,6 +1,7 @@
-// lm.h -- what the two Levenberg-Marquardt solvers (rig_ba.hip, intrinsics.hip) share, each defined once: the camera model
-// with its derivatives, the step-control rule over the state record LmState of kernels.h (both: DESIGN.md section 2, restated
-// by tests/lm_ref.py), and the small index helpers of their packed triangles.
+// lm.h -- what the Levenberg-Marquardt solvers (rig_ba.hip, rig_selfcal.hip, intrinsics.hip) share, each defined once: the camera
+// model with its derivatives, the step-control rule over the state record LmState of kernels.h (both: DESIGN.md section 2,
+// restated by tests/lm_ref.py), the small index helpers of their packed triangles, and the rig solvers' dense algebra (the
+// inverse of a point's 3x3, the packed Cholesky of the reduced camera matrix).
 // The library is built with -ffp-contract=off: every product and sum below is rounded on its own, and the restatement forms
 // each value by the same operations in the same order.
 #pragma once
@@ -73,6 +74,16 @@ __device__ __forceinline__ bool project(const Lens& m, const double q[3], const 
     return front;
 }
 
+// The lens columns of an observation's Jacobian, d pixel / d (fx, fy, cx, cy, k1, k2, p1, p2, k3), from what project<true> left
+// behind: j0[0..8] the row of u, j1[0..8] the row of v
+__device__ __forceinline__ void lens_columns(const Lens& m, const Projected& o, double* j0, double* j1)
+{
+    j0[0] = o.xd; j0[1] = 0.0; j0[2] = 1.0; j0[3] = 0.0;
+    j1[0] = 0.0; j1[1] = o.yd; j1[2] = 0.0; j1[3] = 1.0;
+    j0[4] = m.fx * (o.x * o.r2); j0[5] = m.fx * (o.x * o.r4); j0[6] = m.fx * (2.0 * o.xy); j0[7] = m.fx * o.tx; j0[8] = m.fx * (o.x * o.r6);
+    j1[4] = m.fy * (o.y * o.r2); j1[5] = m.fy * (o.y * o.r4); j1[6] = m.fy * o.ty; j1[7] = m.fy * (2.0 * o.xy); j1[8] = m.fy * (o.y * o.r6);
+}
+
 // One row of the pose Jacobian under the local perturbation R <- Exp(w) R, t <- t + dt, from the same row of A: the columns
 // w = A (-[q]x), then dt = A
 __device__ __forceinline__ void pose_columns(const double A[3], const double q[3], double j[6])
@@ -81,6 +92,62 @@ __device__ __forceinline__ void pose_columns(const double A[3], const double q[3
     j[1] = A[0] * q[2] - A[2] * q[0];
     j[2] = A[1] * q[0] - A[0] * q[1];
     j[3] = A[0]; j[4] = A[1]; j[5] = A[2];
+}
+
+// inverse of the symmetric 3x3 with upper triangle v[6] = (00, 01, 02, 11, 12, 22) by the adjugate; same layout out
+__device__ __forceinline__ void inv_sym3(const double v[6], double o[6])
+{
+    const double c00 = v[3] * v[5] - v[4] * v[4], c01 = v[2] * v[4] - v[1] * v[5], c02 = v[1] * v[4] - v[2] * v[3];
+    const double det = (v[0] * c00 + v[1] * c01) + v[2] * c02;
+    const double c11 = v[0] * v[5] - v[2] * v[2], c12 = v[1] * v[2] - v[0] * v[4], c22 = v[0] * v[3] - v[1] * v[1];
+    o[0] = c00 / det; o[1] = c01 / det; o[2] = c02 / det; o[3] = c11 / det; o[4] = c12 / det; o[5] = c22 / det;
+}
+__device__ __forceinline__ double sym3(const double v[6], int i, int j)
+{
+    const int a = i < j ? i : j, b = i < j ? j : i;
+    return v[a == 0 ? b : (a == 1 ? 2 + b : 5)];
+}
+
+// The reduced camera system of the rig solvers (rig_ba.hip, rig_selfcal.hip), by one workgroup of 256 threads.
+// In-place Cholesky S = L L^T on the packed lower triangle (right-looking); false when a pivot is not positive
+__device__ __forceinline__ bool cholesky_packed(double* L, int D)
+{
+    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+    for (int k = 0; k < D; k++) {
+        __syncthreads();
+        const double d = L[low(k, k)];
+        if (!(d > 0.0) || !finite(d)) return false; // uniform: every thread reads the same value
+        const double sd = sqrt(d);
+        __syncthreads();
+        for (int i = k + tid; i < D; i += 256) L[low(i, k)] = i == k ? sd : L[low(i, k)] / sd;
+        __syncthreads();
+        for (int i = k + 1 + ty; i < D; i += 16) {
+            const double lik = L[low(i, k)];
+            for (int j = k + 1 + tx; j <= i; j += 16) L[low(i, j)] -= lik * L[low(j, k)];
+        }
+    }
+    __syncthreads();
+    return true;
+}
+
+// L L^T x = b with b, x in s_x (LDS), column by column
+__device__ __forceinline__ void solve_packed(const double* L, int D, double* s_x)
+{
+    const int tid = threadIdx.x;
+    for (int k = 0; k < D; k++) {
+        if (tid == 0) s_x[k] = s_x[k] / L[low(k, k)];
+        __syncthreads();
+        const double xk = s_x[k];
+        for (int i = k + 1 + tid; i < D; i += 256) s_x[i] -= L[low(i, k)] * xk;
+        __syncthreads();
+    }
+    for (int k = D - 1; k >= 0; k--) {
+        if (tid == 0) s_x[k] = s_x[k] / L[low(k, k)];
+        __syncthreads();
+        const double xk = s_x[k];
+        for (int i = tid; i < k; i += 256) s_x[i] -= L[low(k, i)] * xk;
+        __syncthreads();
+    }
 }
 
 // The robust loss of an observation with squared residual length s = rx^2 + ry^2 and squared scale c2 = c^2 (DESIGN.md

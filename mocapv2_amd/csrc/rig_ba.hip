@@ -6,7 +6,8 @@
 // is the definition of DESIGN.md section 2, restated in NumPy by tests/rig_ba_ref.py.  Observations are point-major
 // (obs_offset [N + 1], obs_cam, obs_uv), a point's cameras in ascending order; rig_init_kernel checks that and turns each
 // point's camera list into a 32-bit visibility mask, which is all the later kernels index with.
-// The camera model with its derivatives and the step-control rule are lm.h's, shared with intrinsics.hip.
+// The camera model with its derivatives and the step-control rule are lm.h's, shared with intrinsics.hip; the inverse of a
+// point's 3x3 and the packed Cholesky of the reduced matrix are lm.h's too, shared with rig_selfcal.hip.
 // The library is built with -ffp-contract=off: every product and sum below is rounded on its own, and the restatement forms
 // every per-observation quantity by the same operations in the same order.  What differs is the order of the sums over
 // observations and points, which is fixed here: no floating-point atomics anywhere, a lane sums its own points in order,
@@ -98,20 +99,6 @@ __device__ __forceinline__ double robustify(double c2, double r[2], double jc[2]
 
 // the pair of free cameras of a workgroup of the Schur and the reduce kernel: pair index -> (ca, cb), 1 <= ca <= cb < C, row by row
 __device__ __forceinline__ void pair_cameras(int pair, int C, int& ca, int& cb) { tri_unrank(pair, C - 1, ca, cb); ca++; cb++; }
-
-// inverse of the symmetric 3x3 with upper triangle v[6] = (00, 01, 02, 11, 12, 22) by the adjugate; same layout out
-__device__ __forceinline__ void inv_sym3(const double v[6], double o[6])
-{
-    const double c00 = v[3] * v[5] - v[4] * v[4], c01 = v[2] * v[4] - v[1] * v[5], c02 = v[1] * v[4] - v[2] * v[3];
-    const double det = (v[0] * c00 + v[1] * c01) + v[2] * c02;
-    const double c11 = v[0] * v[5] - v[2] * v[2], c12 = v[1] * v[2] - v[0] * v[4], c22 = v[0] * v[3] - v[1] * v[1];
-    o[0] = c00 / det; o[1] = c01 / det; o[2] = c02 / det; o[3] = c11 / det; o[4] = c12 / det; o[5] = c22 / det;
-}
-__device__ __forceinline__ double sym3(const double v[6], int i, int j)
-{
-    const int a = i < j ? i : j, b = i < j ? j : i;
-    return v[a == 0 ? b : (a == 1 ? 2 + b : 5)];
-}
 
 __device__ __forceinline__ bool gated(const RigState* st) { return st->stop || st->layout_err; }
 
@@ -336,51 +323,6 @@ __global__ __launch_bounds__(64) void rig_reduce_kernel(RigArgs a)
         a.scalars[RIG_LIN_COST] = 0.5 * s;
     }
 }
-
-namespace {
-
-// In-place Cholesky S = L L^T on the packed lower triangle (right-looking), 256 threads; false when a pivot is not positive
-__device__ __forceinline__ bool cholesky_packed(double* L, int D)
-{
-    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
-    for (int k = 0; k < D; k++) {
-        __syncthreads();
-        const double d = L[low(k, k)];
-        if (!(d > 0.0) || !finite(d)) return false; // uniform: every thread reads the same value
-        const double sd = sqrt(d);
-        __syncthreads();
-        for (int i = k + tid; i < D; i += 256) L[low(i, k)] = i == k ? sd : L[low(i, k)] / sd;
-        __syncthreads();
-        for (int i = k + 1 + ty; i < D; i += 16) {
-            const double lik = L[low(i, k)];
-            for (int j = k + 1 + tx; j <= i; j += 16) L[low(i, j)] -= lik * L[low(j, k)];
-        }
-    }
-    __syncthreads();
-    return true;
-}
-
-// L L^T x = b with b, x in s_x (LDS), column by column
-__device__ __forceinline__ void solve_packed(const double* L, int D, double* s_x)
-{
-    const int tid = threadIdx.x;
-    for (int k = 0; k < D; k++) {
-        if (tid == 0) s_x[k] = s_x[k] / L[low(k, k)];
-        __syncthreads();
-        const double xk = s_x[k];
-        for (int i = k + 1 + tid; i < D; i += 256) s_x[i] -= L[low(i, k)] * xk;
-        __syncthreads();
-    }
-    for (int k = D - 1; k >= 0; k--) {
-        if (tid == 0) s_x[k] = s_x[k] / L[low(k, k)];
-        __syncthreads();
-        const double xk = s_x[k];
-        for (int i = tid; i < k; i += 256) s_x[i] -= L[low(k, i)] * xk;
-        __syncthreads();
-    }
-}
-
-} // namespace
 
 // One workgroup.  Also the keeper of the state record's first cost, and of the two failures a linearisation can show.
 __global__ __launch_bounds__(256) void rig_solve_kernel(RigArgs a, int it)

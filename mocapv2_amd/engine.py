@@ -592,9 +592,10 @@ class MocapContext:
             out.append(r)
         return out
 
-    def _rig_upload(self, obs_offset, obs_cam, obs_uv, poses, points):
+    def _rig_upload(self, obs_offset, obs_cam, obs_uv, poses, points, need_cameras=True):
         """Device copies of a rig problem in the layout of mocap_rig_bundle_adjust (checked here, so that a mistake is a
-        ValueError with a reason and not only the kernel's MOCAP_RIG_E_LAYOUT)."""
+        ValueError with a reason and not only the kernel's MOCAP_RIG_E_LAYOUT).  need_cameras=False: the caller hands the
+        lenses in itself (the entries that refine them), set_cameras is not asked for."""
         off = np.ascontiguousarray(obs_offset, np.int32).reshape(-1)
         cam = np.ascontiguousarray(obs_cam, np.int32).reshape(-1)
         uv = np.ascontiguousarray(obs_uv, np.float64).reshape(-1, 2)
@@ -614,7 +615,7 @@ class MocapContext:
         inner[off[:-1]] = False
         if (np.diff(cam, prepend=-1)[inner] <= 0).any():
             raise ValueError("a point's observations must come in strictly ascending camera order")
-        if getattr(self, "n_cam", 0) < Cn:
+        if need_cameras and getattr(self, "n_cam", 0) < Cn:
             raise ValueError(f"set_cameras: {getattr(self, 'n_cam', 0)} cameras set, {Cn} needed (their K and dist are used)")
         if not (np.isfinite(uv).all() and np.isfinite(poses).all() and np.isfinite(points).all()):
             raise ValueError("observations, poses and points must be finite")
@@ -671,12 +672,35 @@ class MocapContext:
         costs 1/2 sum rho; "none" gives the bits of loss=None).  The robust call returns two more keys: obs_err [n_obs], the
         length of every observation's unweighted residual at the returned state, and obs_weight [n_obs], its weight
         1 / (1 + s / c^2) there (1 for "none")."""
-        robust = () if loss is None else self._rig_loss(loss, loss_scale)
-        Cn, N, n_obs, d_off, d_cam, d_uv, d_poses, d_pts = self._rig_upload(obs_offset, obs_cam, obs_uv, poses, points)
+        return self._rig_bundle_adjust(obs_offset, obs_cam, obs_uv, poses, points, max_iters, ftol, lambda0, loss, loss_scale)
+
+    def rig_bundle_adjust_intrinsics(self, obs_offset, obs_cam, obs_uv, intrinsics, refine, poses, points, max_iters=50, ftol=1e-12,
+                                     lambda0=1e-3, loss=None, loss_scale=None):
+        """rig_bundle_adjust with the cameras' lenses among the unknowns (mocap_rig_bundle_adjust_intrinsics; K and dist of
+        set_cameras are not used).  intrinsics [C][9]: fx, fy, cx, cy, k1, k2, p1, p2, k3 per camera, camera 0 included, the
+        start; refine: an int mask for all cameras or one per camera, bit i frees parameter i.  Every other argument as
+        rig_bundle_adjust's.  Returns its dict plus intrinsics [C][9], a fixed parameter with the bits it came with, and
+        obs_err / obs_weight as the robust call's (loss=None is "none")."""
+        return self._rig_bundle_adjust(obs_offset, obs_cam, obs_uv, poses, points, max_iters, ftol, lambda0, loss, loss_scale,
+                                       intrinsics, refine)
+
+    def _rig_bundle_adjust(self, obs_offset, obs_cam, obs_uv, poses, points, max_iters, ftol, lambda0, loss, loss_scale,
+                           intrinsics=None, refine=None):
+        """The one body of rig_bundle_adjust and rig_bundle_adjust_intrinsics: upload, the entry the arguments name, sync, dict"""
+        selfcal = intrinsics is not None
+        robust = () if loss is None and not selfcal else self._rig_loss(loss or 0, loss_scale)
+        Cn, N, n_obs, d_off, d_cam, d_uv, d_poses, d_pts = self._rig_upload(obs_offset, obs_cam, obs_uv, poses, points, not selfcal)
         max_iters = int(max_iters)
         hist = torch.empty((max_iters, 4), dtype=torch.float64, device=self.device)
         result = torch.zeros((4,), dtype=torch.float64, device=self.device)
-        if robust:
+        if selfcal:
+            d_kd, mask = self._rig_lenses(intrinsics, refine, Cn)
+            per_obs = torch.empty((2, n_obs), dtype=torch.float64, device=self.device)
+            _abi.check(self.lib.mocap_rig_bundle_adjust_intrinsics(
+                self._h, Cn, N, n_obs, _ptr(d_off), _ptr(d_cam), _ptr(d_uv), _ptr(d_kd), mask.ctypes.data_as(C.POINTER(C.c_int)),
+                _ptr(d_poses), _ptr(d_pts), max_iters, float(ftol), float(lambda0), _ptr(hist), _ptr(result), *robust,
+                _ptr(per_obs[0]), _ptr(per_obs[1]), _stream()))
+        elif robust:
             per_obs = torch.empty((2, n_obs), dtype=torch.float64, device=self.device)
             _abi.check(self.lib.mocap_rig_bundle_adjust_robust(self._h, Cn, N, n_obs, _ptr(d_off), _ptr(d_cam), _ptr(d_uv), _ptr(d_poses),
                                                                _ptr(d_pts), max_iters, float(ftol), float(lambda0), _ptr(hist),
@@ -689,7 +713,9 @@ class MocapContext:
         result = result.cpu().numpy()
         status, iters = int(result[0]), int(result[1])
         if status <= 0:
-            what = {-2: "the observation arrays break the layout rules (MOCAP_RIG_E_LAYOUT)",
+            what = {-2: "the observation arrays break the layout rules" + (", or a camera has fewer observations than twice the lens "
+                                                                                 "parameters its mask frees" if selfcal else "") +
+                        " (MOCAP_RIG_E_LAYOUT)",
                     -3: "in the start state a point is not in front of a camera that sees it, or the cost is not finite "
                         "(MOCAP_RIG_E_BEHIND)"}.get(status, f"status {status}")
             raise _abi.MocapError(status, "mocap_rig_bundle_adjust: " + what)
@@ -698,7 +724,43 @@ class MocapContext:
         if robust:
             per_obs = per_obs.cpu().numpy()
             out["obs_err"], out["obs_weight"] = per_obs[0].copy(), per_obs[1].copy()
+        if selfcal:
+            out["intrinsics"] = d_kd.cpu().numpy()
         return out
+
+    def _rig_lenses(self, intrinsics, refine, Cn):
+        """(device copy of intrinsics [C][9], host int32 mask [C]) of the entries that refine the lenses.  Only the shapes are
+        checked here: what the values lack is the library's MOCAP_E_INVALID."""
+        kd = np.ascontiguousarray(intrinsics, np.float64)
+        if kd.shape != (Cn, 9):
+            raise ValueError(f"intrinsics must be [{Cn}][9] (fx, fy, cx, cy, k1, k2, p1, p2, k3), got {kd.shape}")
+        mask = np.ascontiguousarray(np.broadcast_to(np.asarray(refine, np.int32), (Cn,)))
+        return torch.from_numpy(kd).to(self.device), mask
+
+    def rig_linearize_intrinsics(self, obs_offset, obs_cam, obs_uv, intrinsics, refine, poses, points, lam, loss=None, loss_scale=None):
+        """The pieces of one iteration of rig_bundle_adjust_intrinsics at a given state and damping
+        (mocap_rig_linearize_intrinsics): dict with cost, gradient [15 C + 3 N] (per camera the 9 lens parameters, then the 6 of
+        the pose; then the points), S [15 C][15 C], rhs [15 C], behind.  Arguments as rig_bundle_adjust's."""
+        robust = self._rig_loss(loss or 0, loss_scale)
+        Cn, N, n_obs, d_off, d_cam, d_uv, d_poses, d_pts = self._rig_upload(obs_offset, obs_cam, obs_uv, poses, points, False)
+        d_kd, mask = self._rig_lenses(intrinsics, refine, Cn)
+        D = 15 * Cn
+        dev = self.device
+        cost = torch.zeros((1,), dtype=torch.float64, device=dev)
+        grad = torch.zeros((D + 3 * N,), dtype=torch.float64, device=dev)
+        S = torch.zeros((D, D), dtype=torch.float64, device=dev)
+        rhs = torch.zeros((D,), dtype=torch.float64, device=dev)
+        status = torch.zeros((2,), dtype=torch.int32, device=dev)
+        _abi.check(self.lib.mocap_rig_linearize_intrinsics(
+            self._h, Cn, N, n_obs, _ptr(d_off), _ptr(d_cam), _ptr(d_uv), _ptr(d_kd), mask.ctypes.data_as(C.POINTER(C.c_int)),
+            _ptr(d_poses), _ptr(d_pts), float(lam), _ptr(cost), _ptr(grad), _ptr(S), _ptr(rhs), _ptr(status), *robust, _stream()))
+        self.sync()
+        status = status.cpu().numpy()
+        if status[0]:
+            raise _abi.MocapError(-2, "mocap_rig_linearize_intrinsics: the observation arrays break the layout rules, or a camera has "
+                                      "fewer observations than twice the lens parameters its mask frees (MOCAP_RIG_E_LAYOUT)")
+        return {"cost": float(cost.cpu().numpy()[0]), "gradient": grad.cpu().numpy(), "S": S.cpu().numpy(), "rhs": rhs.cpu().numpy(),
+                "behind": bool(status[1])}
 
     def _intr_upload(self, view_offset, point_offset, obj_xy, img_uv):
         """Host offsets and device copies of a board-view problem in the layout of mocap_intrinsics_calibrate.  Only the
