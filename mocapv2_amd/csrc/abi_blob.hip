@@ -129,7 +129,7 @@ static ScanBounds scan_bounds(const mocap_ctx* c, int slot_base, int cam_mod, in
     auto t5 = [](int n) { return (n - 1 < 2 ? n - 1 : 2) + 1; }; // taps of a window at the border, per axis
     auto t5full = [](int n) { return n < 5 ? n : 5; };
     const long long per_tap = 1024LL * (2LL * thr_mul - 2LL * b.base - 1), per_tap_alt = 1024LL * (2LL * thr_mul - 2LL * b.base_alt - 1);
-    if (!c->tile_rows || !c->tile_cols || !c->reach || !c->cflags) ok = false;
+    if (!c->tile_rows || !c->reach || !c->cflags) ok = false;
     if (ok && wmax > 0 && per_tap > 0) {
         b.allow = (int)((per_tap * t5full(c->W) * t5full(c->H) - 1) / wmax); // windows with all their taps
         const long long taps1 = t5(c->W) * t5full(c->H) < t5full(c->W) * t5(c->H) ? t5(c->W) * t5full(c->H) : t5full(c->W) * t5(c->H);
@@ -222,8 +222,6 @@ static BoxArgs box_args(const mocap_ctx* c, const Batch& bt, const FilterPath& p
     a.tile_rows = c->tile_rows + (c->tile_rows_flip ? tr_words : 0);
     a.tile_rows_next = c->tile_rows + (c->tile_rows_flip ? 0 : tr_words);
     a.n_clear = c->tile_rows_hold[c->tile_rows_flip ^ 1];
-    a.tile_cols = c->tile_cols + (c->tile_rows_flip ? tr_words / 4 : 0);
-    a.tile_cols_next = c->tile_cols + (c->tile_rows_flip ? 0 : tr_words / 4);
     a.wide_split = c->tune.wide_split == 2 || (c->tune.wide_split == 1 && !c->hot_dense); // (1: sparse scenes only, as scan_hotmap and contour_defer)
     a.cluster = c->tune.cluster;
     a.cur_box = bt.own_mask ? c->cur_box : c->cur_box_ext;
@@ -245,8 +243,7 @@ static BoxArgs box_args(const mocap_ctx* c, const Batch& bt, const FilterPath& p
 }
 
 // the scan's arguments, without probe and hot map
-static BrightArgs bright_args(const mocap_ctx* c, const Batch& bt, const FilterPath& p, const ScanBounds& sb, uint32_t* tile_rows, uint32_t* tile_cols,
-                              bool scan_zeroes)
+static BrightArgs bright_args(const mocap_ctx* c, const Batch& bt, const FilterPath& p, const ScanBounds& sb, uint32_t* tile_rows, bool scan_zeroes)
 {
     const Tiling tl = tiling(c);
     // floor(i / ncx) = umulhi(i, ceil(2^32 / ncx)) is exact while i * ncx < 2^32
@@ -266,17 +263,15 @@ static BrightArgs bright_args(const mocap_ctx* c, const Batch& bt, const FilterP
     b.zero_counters = scan_zeroes ? c->n_items.p : nullptr;
     b.block_ctr = c->n_items + 160; // (words 160..223 of the counter block zeroed above: one per slice)
     b.slices = c->tune.scan_slices; b.image0 = 0; b.slice_images = bt.n_images;
-    b.tile_cols = tile_cols;
     return b;
 }
 
 // One streaming pass over the frames marks the tiles (and their boxes) that can hold set pixels.  `b` keeps what it ran with,
 // for mark_tiles_kernel when that one has to follow (`mark_after_scan`).
-static int scan_tiles(mocap_ctx* c, const Batch& bt, const FilterPath& p, const ScanBounds& sb, uint32_t* tile_rows, uint32_t* tile_cols,
-                      bool scan_zeroes, BrightArgs& b, bool& mark_after_scan)
+static int scan_tiles(mocap_ctx* c, const Batch& bt, const FilterPath& p, const ScanBounds& sb, uint32_t* tile_rows, bool scan_zeroes, BrightArgs& b, bool& mark_after_scan)
 {
     const hipStream_t s = bt.s;
-    b = bright_args(c, bt, p, sb, tile_rows, tile_cols, scan_zeroes);
+    b = bright_args(c, bt, p, sb, tile_rows, scan_zeroes);
     const bool probe = sb.fixed_base < 0 && !c->probe_pending && sb.allow_alt >= 0 && sb.base_alt != sb.base && !p.bayer &&
                        (c->probe_age == 0 || c->probe_age >= 32);
     if (probe) {
@@ -433,7 +428,7 @@ static int run_filter(mocap_ctx* c, const void* frames, int n_images, int cam_mo
     a.zero8 = bt.own_mask ? c->walk_count.p : nullptr; // (the contour stage of this batch follows on the same stream; null before its first batch)
     c->walk_count_zeroed = a.zero8 != nullptr;
     BrightArgs mark_args{}; bool mark_after_scan = false;
-    if (!a.dense) TRY(scan_tiles(c, bt, p, sb, a.tile_rows, const_cast<uint32_t*>(a.tile_cols), scan_zeroes, mark_args, mark_after_scan));
+    if (!a.dense) TRY(scan_tiles(c, bt, p, sb, a.tile_rows, scan_zeroes, mark_args, mark_after_scan));
     else if (p.bayer) { // no early-out (not provable for this table, or MOCAP_SKIP_DARK=0): the plain gray pass
         launch_bayer_gray(p.bl, s);
         HIP_TRY(hipGetLastError());
@@ -577,14 +572,12 @@ static int grow_mask_group(mocap_ctx* c, size_t n_images)
     const size_t tiles = n_images * cells_per_image(c);
     TRY(c->mask.reserve(n_images * mask_image_words(c->H, c->wpr), true));
     TRY(c->cells.reserve(tiles, true));
-    // every tile starts with the empty box (0xffffffff, 0) and an empty recorded region (x0 = 1 > x1 = 0)
-    std::vector<uint32_t> init(tiles * 4);
-    for (size_t i = 0; i < init.size(); i += 2) { init[i] = 0xffffffffu; init[i + 1] = 0u; }
+    // every tile starts with the empty record (0xffffffff, 0, 0, 0) and an empty recorded region (x0 = 1 > x1 = 0)
+    std::vector<uint32_t> init(tiles * 4, 0u);
+    for (size_t i = 0; i < init.size(); i += 4) init[i] = 0xffffffffu;
     TRY(c->tile_rows.reserve(2 * init.size()));
     HIP_TRY(hipMemcpy(c->tile_rows, init.data(), sizeof(uint32_t) * init.size(), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(c->tile_rows + init.size(), init.data(), sizeof(uint32_t) * init.size(), hipMemcpyHostToDevice));
-    TRY(c->tile_cols.reserve(2 * tiles)); // the column words beside them: no column marked
-    HIP_TRY(hipMemset(c->tile_cols, 0, sizeof(uint32_t) * 2 * tiles));
     // the hot map, sized for either scan form
     const int hw0 = hot_map_words(c->H, c->W, 0), hw1 = hot_map_words(c->H, c->W, 1);
     TRY(c->hotmap.reserve(n_images * (hw0 > hw1 ? hw0 : hw1), true)); // all zeros between batches: the scan stores hot words only, mark_tiles_kernel clears them
@@ -603,7 +596,7 @@ static int ensure_mask(mocap_ctx* c, int n_images)
     if ((size_t)n_images <= c->mask_images) return 0;
     c->mask_images = 0; c->last_images = 0;
     if (int rc = grow_mask_group(c, n_images)) { // not half a group: the error is returned once, the next call starts over
-        c->mask.release(); c->cells.release(); c->tile_rows.release(); c->tile_cols.release(); c->hotmap.release(); c->cur_box.release();
+        c->mask.release(); c->cells.release(); c->tile_rows.release(); c->hotmap.release(); c->cur_box.release();
         c->items.release(); c->wide_tiles.release();
         return rc;
     }

@@ -219,11 +219,10 @@ __global__ __launch_bounds__(256) void bayer_gray_scan_kernel(BayerArgs a, Brigh
         const int slot = image % b.cam_mod;
         const uint2* __restrict__ reach = b.reach + (size_t)slot * n;
         const uint8_t* __restrict__ cflags = b.cflags + (size_t)slot * n;
-        uint32_t* __restrict__ rows = b.tile_rows + (size_t)image * b.n_chunks * b.n_strips * 4;
-        uint32_t* __restrict__ cols = b.tile_cols + (size_t)image * b.n_chunks * b.n_strips;
+        uint32_t* __restrict__ rec = b.tile_rows + (size_t)image * b.n_chunks * b.n_strips * 4;
         const int ci = cy * ncx + (x0 >> 3);
-        mark_hot_cell(b, reach, cflags, rows, cols, ci, acc0);
-        mark_hot_cell(b, reach, cflags, rows, cols, ci + 1, acc1);
+        mark_hot_cell(b, reach, cflags, rec, ci, acc0);
+        mark_hot_cell(b, reach, cflags, rec, ci + 1, acc1);
     }
 }
 

@@ -43,8 +43,9 @@ __device__ __forceinline__ uint4 load_once16(const uint8_t* p)
 // whose doubled excess exceeds `hot` (4 * hot <= allow, so four dark cells can never exceed the 2x2-block bound above;
 // `hot_edge` and `hot_corner`, from the bounds of the 15- and 9-tap windows, for the cells that feed windows cut by the image
 // border in one axis or in both) marks every filter tile its reach touches (reach = the box of output pixels that read
-// the cell, tabulated at set-up, + 4 pixels of blur and median) by widening the tile's range of reachable mask rows
-// and columns (atomic min / max).  Tiles left unmarked, and rows outside the range, provably filter to zeros.
+// the cell, tabulated at set-up, + 4 pixels of blur and median) by widening the tile's record: its range of reachable mask rows
+// (atomic min / max) and its mask of reachable quad columns (atomic or; kernels.h: tile_quad_bits).  Tiles left unmarked, and rows
+// outside the range, provably filter to zeros.
 // WIDE (W, pitch, image stride and base multiples of 16): the two cells of a thread are neighbours in one cell row and
 // come in with one 16-byte load per image row (8 loads of 16 B instead of 16 of 8 B per thread).
 // FULL (H a multiple of 8, wide only): every cell has its 8 rows, no row clamping and no per-row validity test.
@@ -106,8 +107,7 @@ __device__ __forceinline__ void bright_cells_block(const BrightArgs& a, const in
     const int slot = image % a.cam_mod;
     const uint2* __restrict__ reach = a.reach + (size_t)slot * n;
     const uint8_t* __restrict__ cflags = a.cflags + (size_t)slot * n;
-    uint32_t* __restrict__ rows = a.tile_rows + (size_t)image * a.n_chunks * a.n_strips * 4;
-    uint32_t* __restrict__ cols = a.tile_cols + (size_t)image * a.n_chunks * a.n_strips;
+    uint32_t* __restrict__ rec = a.tile_rows + (size_t)image * a.n_chunks * a.n_strips * 4;
     const uint32_t base4 = (uint32_t)a.base * 0x01010101u, c8 = 8u * (uint32_t)a.base;
     uint32_t level[2] = {0u, 0u}, sum[2];
 #pragma unroll
@@ -144,8 +144,8 @@ __device__ __forceinline__ void bright_cells_block(const BrightArgs& a, const in
     }
     // (the hot cells mark their tiles once both sums stand: the frame bytes need no registers beside that rare path's)
     if (!MAP) {
-        mark_hot_cell(a, reach, cflags, rows, cols, ci[0], sum[0]);
-        mark_hot_cell(a, reach, cflags, rows, cols, ci[1], sum[1]);
+        mark_hot_cell(a, reach, cflags, rec, ci[0], sum[0]);
+        mark_hot_cell(a, reach, cflags, rec, ci[1], sum[1]);
     }
     if (MAP) {
         // The hot map: two bits per cell in cell order, so the 128 cells of a wave are 8 whole words (WIDE: consecutive lanes hold
@@ -182,12 +182,12 @@ __device__ __forceinline__ void bright_cells_block(const BrightArgs& a, const in
 // at 8 markers per frame, 1.133 at 32: most scan waves carry a hot cell then).
 // The hot cells of a marker lie in the same few waves and reach the same one or two tiles, and a memory atomic costs what
 // it costs whether it changes anything or not (the first version issued four per hot cell and tile: 4 M of them per batch
-// at 8 markers, 0.29 ms; 0.89 ms at 32): the wave first merges its cells' rectangles, and the byte columns they overlap, per tile in
+// at 8 markers, 0.29 ms; 0.89 ms at 32): the wave first merges its cells' rectangles, rows and quad columns (tile_quad_bits), per tile in
 // a 32-entry table in LDS (tag = tile; a collision goes to memory directly) and then widens each tile it touched once.
 __global__ __launch_bounds__(256) void mark_tiles_kernel(BrightArgs a)
 {
     __shared__ uint16_t s_list[4][1024];
-    __shared__ uint32_t s_tab[4][32][6]; // tile | first row | last row | first column | last column | column bits
+    __shared__ uint32_t s_tab[4][32][5]; // tile | first row | last row | quad mask, low word | high word
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     // a wave takes 256 consecutive words (4 per lane) of one image at a time; with a fixed grid (a few workgroups per CU) the
     // waves go on to further pieces: few workgroups to place beside another batch's scan, which holds every wave slot of the chip
@@ -206,25 +206,19 @@ __global__ __launch_bounds__(256) void mark_tiles_kernel(BrightArgs a)
 #pragma unroll
     for (int k = 0; k < 4; k++)
         if (wk[k] != 0u) hm[wave_word0 + 64 * k + lane] = 0u; // the map is all zeros again for the next batch's scan
-    uint32_t (*tab)[6] = s_tab[wv];
-    if (lane < 32) { tab[lane][0] = 0xffffffffu; tab[lane][1] = 0xffffffffu; tab[lane][2] = 0u; tab[lane][3] = 0xffffffffu; tab[lane][4] = 0u; tab[lane][5] = 0u; }
+    uint32_t (*tab)[5] = s_tab[wv];
+    if (lane < 32) { tab[lane][0] = 0xffffffffu; tab[lane][1] = 0xffffffffu; tab[lane][2] = 0u; tab[lane][3] = 0u; tab[lane][4] = 0u; }
     const int slot = image % a.cam_mod;
     const uint2* __restrict__ reach = a.reach + (size_t)slot * n_cells;
     const uint8_t* __restrict__ cflags = a.cflags + (size_t)slot * n_cells;
-    uint32_t* __restrict__ rows = a.tile_rows + (size_t)image * a.n_chunks * a.n_strips * 4;
-    uint32_t* __restrict__ cols = a.tile_cols + (size_t)image * a.n_chunks * a.n_strips;
-    // widen one tile's box in memory and mark its columns (a box that already holds the rectangle, and a column word that holds
-    // its columns, need no atomics)
-    auto widen = [&](int t, uint32_t ya, uint32_t yb, uint32_t xa, uint32_t xb, uint32_t m) __attribute__((always_inline)) {
-        const uint4 cur = *(const uint4*)(rows + 4 * t);
-        const uint32_t have = cols[t];
-        if (!(cur.x <= ya && cur.y >= yb && cur.z <= xa && cur.w >= xb)) {
-            atomicMin(&rows[4 * t], ya);
-            atomicMax(&rows[4 * t + 1], yb);
-            atomicMin(&rows[4 * t + 2], xa);
-            atomicMax(&rows[4 * t + 3], xb);
-        }
-        if ((have & m) != m) atomicOr(&cols[t], m);
+    uint32_t* __restrict__ rec = a.tile_rows + (size_t)image * a.n_chunks * a.n_strips * 4;
+    // widen one tile's record in memory (one 16-byte load; a word that already holds its part of the rectangle needs no atomic)
+    auto widen = [&](int t, uint32_t ya, uint32_t yb, uint32_t mlo, uint32_t mhi) __attribute__((always_inline)) {
+        const uint4 cur = *(const uint4*)(rec + 4 * t);
+        if (cur.x > ya) atomicMin(&rec[4 * t], ya);
+        if (cur.y < yb) atomicMax(&rec[4 * t + 1], yb);
+        if ((cur.z & mlo) != mlo) atomicOr(&rec[4 * t + 2], mlo);
+        if ((cur.w & mhi) != mhi) atomicOr(&rec[4 * t + 3], mhi);
     };
 #pragma unroll 1
     for (int k = 0; k < 4; k++) {
@@ -264,14 +258,15 @@ __global__ __launch_bounds__(256) void mark_tiles_kernel(BrightArgs a)
                         for (int ch = ch0; ch <= ch1; ch++)
                             for (int st = st0; st <= st1; st++) {
                                 const int t = ch * a.n_strips + st, q = t & 31;
-                                const uint32_t m = tile_col_bits(st, xa, xb);
+                                const uint64_t m = tile_quad_bits(st, xa, xb);
+                                const uint32_t mlo = (uint32_t)m, mhi = (uint32_t)(m >> 32);
                                 const uint32_t old = atomicCAS(&tab[q][0], 0xffffffffu, (uint32_t)t);
                                 if (old == 0xffffffffu || old == (uint32_t)t) {
                                     atomicMin(&tab[q][1], (uint32_t)ya); atomicMax(&tab[q][2], (uint32_t)yb);
-                                    atomicMin(&tab[q][3], (uint32_t)xa); atomicMax(&tab[q][4], (uint32_t)xb);
-                                    atomicOr(&tab[q][5], m);
+                                    if (mlo) atomicOr(&tab[q][3], mlo);
+                                    if (mhi) atomicOr(&tab[q][4], mhi);
                                 } else
-                                    widen(t, (uint32_t)ya, (uint32_t)yb, (uint32_t)xa, (uint32_t)xb, m);
+                                    widen(t, (uint32_t)ya, (uint32_t)yb, mlo, mhi);
                             }
                     }
                 }
@@ -280,7 +275,7 @@ __global__ __launch_bounds__(256) void mark_tiles_kernel(BrightArgs a)
         __builtin_amdgcn_s_waitcnt(0xc07f);
         __builtin_amdgcn_wave_barrier(); // (the list is rewritten by the next k)
     }
-    if (lane < 32 && tab[lane][0] != 0xffffffffu) widen((int)tab[lane][0], tab[lane][1], tab[lane][2], tab[lane][3], tab[lane][4], tab[lane][5]);
+    if (lane < 32 && tab[lane][0] != 0xffffffffu) widen((int)tab[lane][0], tab[lane][1], tab[lane][2], tab[lane][3], tab[lane][4]);
     __builtin_amdgcn_s_waitcnt(0xc07f);
     __builtin_amdgcn_wave_barrier(); // (the table is initialised anew for the wave's next piece)
     }

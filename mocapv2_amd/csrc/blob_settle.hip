@@ -2,7 +2,7 @@
 // (tile, image), turns the box the scan left on the tile (reachable mask rows and columns) into work items of a bounded size in ONE
 // global list (box_filter_kernel, blob_boxes.hip) -- or, a wide box, into entries of the wide-tile list that the sliding row pipeline
 // works through (blob_rows.hip); a wide box with empty columns between its markers is cut at them into items after all --, clears
-// what the previous batch left in the mask where this batch will not write, and empties the next batch's boxes and column words.
+// what the previous batch left in the mask where this batch will not write, and empties the next batch's tile records.
 // The records it writes (items, wide-tile entries, the tiles' regions) are defined in kernels.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -38,7 +38,15 @@ __device__ __forceinline__ void choose_split(int nb, int h, int& nx, int& ny)
 namespace {
 
 struct Rect { int x0, x1, y0, y1; }; // columns [x0, x1], rows [y0, y1]; x0 > x1 or y0 > y1: empty
-constexpr uint4 NO_BOX = {0xffffffffu, 0u, 0xffffffffu, 0u}; // a tile of tile_rows the scan did not mark (first row > last row)
+constexpr uint4 NO_BOX = {0xffffffffu, 0u, 0u, 0u}; // a tile of tile_rows the scan did not mark (first row > last row, no quad)
+
+// a tile's record as the box it stands for: its rows, and the first and last marked quad column of strip `st` clamped into the image
+__device__ __forceinline__ Rect record_box(uint4 rec, int st, int W)
+{
+    Rect b{0, 0, (int)rec.x, (int)rec.y};
+    tile_quad_columns(st, (uint64_t)rec.w << 32 | rec.z, W, b.x0, b.x1);
+    return b;
+}
 
 // ---- thread -> (tile, slot, time step) ----------------------------------------------------------------------------------
 // Time fastest: the items of one tile of one camera lie together in the list, so the waves that work at the same time share
@@ -64,14 +72,17 @@ __device__ __forceinline__ TileOfThread tile_of_thread(const BoxArgs& a, int n_a
 }
 
 // ---- the scan's box of the tile: where exact pixels are needed / bits can be set -------------------------------------------
-// (the scan's boxes of this batch are only read here: neighbouring tiles look at each other's).  false: the tile is not marked.
-__device__ __forceinline__ bool scan_box(const BoxArgs& a, const TileOfThread& t, bool valid, Rect& box)
+// (the scan's records of this batch are only read here: neighbouring tiles look at each other's).  false: the tile is not marked.
+// quads: the record's quad mask (0 where there is no record).  The box's columns are the mask's: whole quads inside the tile's window.
+__device__ __forceinline__ bool scan_box(const BoxArgs& a, const TileOfThread& t, bool valid, Rect& box, uint64_t& quads)
 {
     box = {0, a.W - 1, 0, a.H - 1};
+    quads = 0;
     if (!valid || a.dense) return valid;
     const uint4 raw = *(const uint4*)(a.tile_rows + 4 * t.idx);
     if (raw.x > raw.y) return false;
-    box = {(int)raw.z, (int)raw.w, (int)raw.x, (int)raw.y};
+    quads = (uint64_t)raw.w << 32 | raw.z;
+    box = record_box(raw, t.strip, a.W);
     return true;
 }
 
@@ -94,7 +105,10 @@ __device__ __forceinline__ bool cluster_decision(const BoxArgs& a, const TileOfT
         if (o.x > o.y) continue;
         if (first < 0) first = k;
         n_marked++;
-        u.y0 = imin(u.y0, (int)o.x); u.y1 = imax(u.y1, (int)o.y); u.x0 = imin(u.x0, (int)o.z); u.x1 = imax(u.x1, (int)o.w);
+        // (a rectangle that reaches this tile from beyond its window also marks the neighbour it comes from: inside the block's own
+        // window, which is all that e and the item's patch look at, the union of the windows' columns is the union of the rectangles')
+        const Rect ob = record_box(o, sx, a.W);
+        u.y0 = imin(u.y0, ob.y0); u.y1 = imax(u.y1, ob.y1); u.x0 = imin(u.x0, ob.x0); u.x1 = imax(u.x1, ob.x1);
     }
     if (n_marked < 2) return true;
     // the union, clipped to the block and the image, in whole mask bytes
@@ -140,9 +154,10 @@ __device__ __forceinline__ void clear_previous(const BoxArgs& a, bool need_clear
         const int x0 = span_first(cx), x1 = span_last(cx), y0 = span_first(cy), y1 = span_last(cy);
         uint8_t* m = (uint8_t*)(a.mask + (size_t)cimage * mask_image_words(a.H, a.words_per_row));
         // consecutive lanes walk down the rows of one byte column: 32 of them share a line of the blocked mask
-        const int b0 = x0 >> 3, nr = y1 - y0 + 1, n = nr * ((x1 >> 3) - b0 + 1);
+        const int b0 = x0 >> 3, nr = y1 - y0 + 1, n = nr * ((x1 >> 3) - b0 + 1); // n <= 30 byte columns x the rows of a tile
+        const float rcp_nr = __builtin_amdgcn_rcpf((float)nr);
         for (int i = lane; i < n; i += 64) {
-            const int bc = i / nr;
+            const int bc = small_div(i, rcp_nr);
             m[mask_byte_index(y0 + (i - bc * nr), b0 + bc, a.words_per_row)] = 0;
         }
     }
@@ -181,7 +196,7 @@ __device__ __forceinline__ void count_split(const BoxArgs& a, bool split)
 // then nx and ny of its parts (3 bits each).  A tile that is not split has one piece, of which only nx and ny are used.
 __device__ __forceinline__ uint64_t piece_pack(int b0, int b1, int nx, int ny) { return (uint64_t)(b0 | b1 << 5 | nx << 10 | ny << 13); }
 
-// A tile on its way to the wide list whose column word (the byte columns some hot cell's rectangle overlaps, scan_mark.h) has empty
+// A tile on its way to the wide list whose column word (the byte columns some hot cell's rectangle overlaps: tile_quad_bytes of its record) has empty
 // columns inside the region: the maximal runs of set columns become one piece each, IF there are at least two, every run alone
 // (its bytes x the region's h rows) would be routed to the box kernel, and the parts of all of them together are at most
 // BOX_MAX_PARTS -- what the item list's capacity rests on.  Else the tile stays a wide entry (0 is returned).
@@ -269,14 +284,15 @@ __global__ __launch_bounds__(256) void settle_tiles_kernel(BoxArgs a)
     const TileOfThread t = tile_of_thread(a, n_all);
     if (t.valid && !a.dense && t.image < n_all) { // the buffer the NEXT batch's scan will widen -- read by the previous batch's settle -- is emptied
         const uint4 nxt = *(const uint4*)(a.tile_rows_next + 4 * t.idx);
-        if (nxt.x <= nxt.y) { *(uint4*)(a.tile_rows_next + 4 * t.idx) = NO_BOX; a.tile_cols_next[t.idx] = 0u; }
+        if (nxt.x <= nxt.y) *(uint4*)(a.tile_rows_next + 4 * t.idx) = NO_BOX;
     }
     const bool valid = t.valid && t.image < a.n_images; // (images beyond the batch: nothing else happens for them)
     const int tile = t.chunk * a.n_strips + t.strip;
     const int tile_r0 = t.chunk * a.rows_per_chunk, tile_r1 = imin(tile_r0 + a.rows_per_chunk, a.H) - 1;
     const int tile_x0 = 240 * t.strip, tile_x1 = imin(tile_x0 + 239, a.W - 1);
     Rect box;
-    bool marked = scan_box(a, t, valid, box);
+    uint64_t quads;
+    bool marked = scan_box(a, t, valid, box, quads);
     // output region of the tile: the box clipped to the tile, whole mask bytes
     Rect out{imax(box.x0, tile_x0) & ~7, imin(imin(box.x1, tile_x1) | 7, tile_x1), imax(box.y0, tile_r0), imin(box.y1, tile_r1)};
     if (marked && (out.x0 > out.x1 || out.y0 > out.y1)) marked = false;
@@ -297,7 +313,7 @@ __global__ __launch_bounds__(256) void settle_tiles_kernel(BoxArgs a)
         const bool own = cover.x0 == out.x0 && cover.x1 == out.x1 && cover.y0 == out.y0 && cover.y1 == out.y1; // no cluster item
         wide = emits && own && a.wide_tiles != nullptr && 2 * nb + 2 * nx >= limit;
         if (wide && a.wide_split && a.wide_bands == 1 && !a.dense) {
-            n_pieces = split_at_gaps(a.tile_cols[t.idx], (out.x0 - tile_x0) >> 3, (out.x1 - tile_x0) >> 3, h, limit, pieces);
+            n_pieces = split_at_gaps(tile_quad_bytes(quads), (out.x0 - tile_x0) >> 3, (out.x1 - tile_x0) >> 3, h, limit, pieces);
             split = n_pieces != 0;
             wide = !split;
         }

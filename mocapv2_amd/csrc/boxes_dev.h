@@ -13,8 +13,6 @@ namespace {
 
 __device__ __forceinline__ int imin(int a, int b) { return a < b ? a : b; }
 __device__ __forceinline__ int imax(int a, int b) { return a > b ? a : b; }
-// floor(n / d) for 0 <= n < 4096, 1 <= d <= 4096 (float reciprocal, +0.5 keeps every quotient away from an integer)
-__device__ __forceinline__ int small_div(int n, float rcp_d) { return (int)(((float)n + 0.5f) * rcp_d); }
 
 // ---- gray values formed from raw Bayer frames (box_filter_kernel<true>) ------------------------------------------------------
 // gray(x, y) = site_gray at (clamp(x, 1, W-2), clamp(y, 1, H-2)) -- the arithmetic of orc_bayer_gray_u8 / bayer_gray_any_kernel --

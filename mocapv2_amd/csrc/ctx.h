@@ -123,10 +123,9 @@ struct mocap_ctx {
     Buf<uint32_t> cells;                   // occupancy cells written by the filter kernels for c->mask
     int last_images = 0;                   // images of the most recent batch that wrote c->cells
     Buf<uint32_t> hotmap;                  // [mask_images][hot_map_words(H, W, 1)] the scan's hot map (BrightArgs::hotmap)
-    Buf<uint32_t> tile_rows;               // [2][mask_images][tiles][4] the scan's box per tile (see BoxArgs): two arrays, alternating
+    Buf<uint32_t> tile_rows;               // [2][mask_images][tiles][4] the scan's record per tile (see BoxArgs): two arrays, alternating
     int tile_rows_flip = 0;                //   per batch: the one the scan widens and settle reads / the one settle empties
     int tile_rows_hold[2] = {0, 0};        //   images whose boxes each of the two may still hold (batches of varying size)
-    Buf<uint32_t> tile_cols;               // [2][mask_images][tiles] the scan's column word per tile (see BoxArgs): two arrays, flipped with tile_rows
     Buf<uint32_t> cur_box;                 // [mask_images][tiles][4] output region / scan box of the last batch per tile (BoxArgs)
     Buf<BoxItem> items;                    // work list of the box kernel
     Buf<uint4> wide_tiles;                 // list of the tiles with wide boxes (filter_mask_kernel, list form)

@@ -31,6 +31,9 @@ __device__ __forceinline__ unsigned long long uni64(unsigned long long v)
     return (unsigned long long)hi << 32 | lo;
 }
 
+// floor(n / d) for 0 <= n < 4096, 1 <= d <= 4096 from d's float reciprocal (+0.5 keeps every quotient away from an integer)
+__device__ __forceinline__ int small_div(int n, float rcp_d) { return (int)(((float)n + 0.5f) * rcp_d); }
+
 // Sums with a fixed order, for results that must have the same bits on every run (no floating-point atomics): the lanes of a
 // wave by shuffles (offsets 32 .. 1; lane 0 holds the sum) ...
 __device__ __forceinline__ double wave_sum(double v)
@@ -113,6 +116,42 @@ constexpr int SPLIT_COUNTER = 12;                   // word of the counter block
 __host__ __device__ __forceinline__ uint32_t span_pack(int a, int b) { return (uint32_t)a | ((uint32_t)b << 16); }
 __host__ __device__ __forceinline__ int span_first(uint32_t s) { return (int)(s & 0xffffu); }
 __host__ __device__ __forceinline__ int span_last(uint32_t s) { return (int)(s >> 16); }
+// A tile's record of the scan (BoxArgs::tile_rows): .x / .y the first / last mask row some hot cell's rectangle reaches, .z / .w the low
+// and high word of the tile's quad mask.  Bit q (0..61) of the mask: a rectangle overlaps the 4-pixel quad column 240 st - 4 + 4 q .. + 3
+// of strip st -- the window [240 st - 4, 240 st + 243], the tile and the 4 pixels a patch reaches beyond it on either side, which is all
+// of a rectangle's column extent that a consumer of the tile looks at, and none looks at it more finely than a quad.  Not marked:
+// (0xffffffff, 0, 0, 0), first row > last row.
+// the quads of strip st that the columns [xa, xb] overlap (the caller has found that they overlap the strip)
+__host__ __device__ __forceinline__ uint64_t tile_quad_bits(int st, int xa, int xb)
+{
+    const int base = 240 * st - 4;
+    const int qa = xa > base ? (xa - base) >> 2 : 0, qb = xb - base < 248 ? (xb - base) >> 2 : 61;
+    return (2ull << qb) - (1ull << qa);
+}
+// first and last marked column of the mask `m` (not 0) of strip st, clamped into the image (quad 0 of strip 0 lies left of it)
+__host__ __device__ __forceinline__ void tile_quad_columns(int st, uint64_t m, int W, int& x0, int& x1)
+{
+    const uint32_t lo = (uint32_t)m, hi = (uint32_t)(m >> 32);
+#if defined(__HIP_DEVICE_COMPILE__)
+    const int q0 = lo ? __ffs((int)lo) - 1 : 31 + __ffs((int)hi), q1 = hi ? 63 - __clz((int)hi) : 31 - __clz((int)lo);
+#else
+    const int q0 = lo ? __builtin_ctz(lo) : 32 + __builtin_ctz(hi), q1 = hi ? 63 - __builtin_clz(hi) : 31 - __builtin_clz(lo);
+#endif
+    const int base = 240 * st - 4, a = base + 4 * q0, b = base + 4 * q1 + 3;
+    x0 = a > 0 ? a : 0; x1 = b < W - 1 ? b : W - 1;
+}
+// the mask byte columns of the strip that the marked quads overlap: bit b (0..29, columns 240 st + 8 b .. + 7) = quads 2 b + 1, 2 b + 2
+__host__ __device__ __forceinline__ uint32_t tile_quad_bytes(uint64_t m)
+{
+    uint64_t v = ((m | (m >> 1)) >> 1) & 0x0555555555555555ull; // bit 2 b = quad 2 b + 1 or 2 b + 2; the even bits are pressed together
+    v = (v | (v >> 1)) & 0x3333333333333333ull;
+    v = (v | (v >> 2)) & 0x0f0f0f0f0f0f0f0full;
+    v = (v | (v >> 4)) & 0x00ff00ff00ff00ffull;
+    v = (v | (v >> 8)) & 0x0000ffff0000ffffull;
+    v = (v | (v >> 16)) & 0x00000000ffffffffull;
+    return (uint32_t)v;
+}
+
 // One work item of the box kernel, moved as its two 16-byte halves.  head: image, tile (chunk * n_strips + strip), the output region's
 // columns and rows as spans (an empty part of a split: columns 1 > 0, the consumer skips it); box: the columns and rows of the scan's
 // box the item takes its exact pixels from (not clipped to the tile), two words of padding.
@@ -153,13 +192,10 @@ struct BoxArgs {
     int cam_mod, n_images, n_steps;
     int thr_mul;
     int rows_per_chunk, n_strips, n_chunks;
-    uint32_t* tile_rows;        // [n_images][n_chunks][n_strips][4]: the scan's boxes of this batch (first / last row, first / last
-                                //   column; (0xffffffff, 0) = none), read-only for settle
+    uint32_t* tile_rows;        // [n_images][n_chunks][n_strips][4]: the scan's records of this batch (first / last row, the quad mask's two
+                                //   words: tile_quad_bits; (0xffffffff, 0, 0, 0) = none), read-only for settle
     uint32_t* tile_rows_next;   // the same array for the next batch (the two alternate): emptied by settle
-    const uint32_t* tile_cols;  // [n_images][n_chunks][n_strips]: the scan's column word of each tile of this batch (bit b, 0..29: a hot cell's
-                                //   rectangle overlaps mask byte column b of the tile, clipped to it; 0 = not marked), read-only for settle
-    uint32_t* tile_cols_next;   // the same array for the next batch: emptied by settle wherever it empties tile_rows_next
-    int wide_split;             // 1 = a wide tile whose column word has gaps is cut into one set of items per run of columns (the host decides: tuning.def)
+    int wide_split;             // 1 = a wide tile whose byte columns (tile_quad_bytes) have gaps is cut into one set of items per run of columns (the host decides: tuning.def)
     int n_clear;                // images whose boxes tile_rows_next may still hold (an earlier, larger batch): emptied too
     int cluster;                // 1 = a box spanning tiles that all hold it becomes one item (A/B switch)
     uint32_t* cur_box;          // [n_images][n_chunks][n_strips][4]: words 0-1 the tile's output region of this batch
@@ -261,7 +297,7 @@ struct BrightArgs {
                                   //   _corner for cells feeding windows the image border cuts in one axis / in both
     const uint2* reach;           // [cam_mod][cells]: box of the output pixels that read the 8x8 source cell, x0 | x1 << 16, y0 | y1 << 16
     const uint8_t* cflags;        // [cam_mod][cells]: 1 / 2 = the cell feeds windows the image border cuts in one axis / in both
-    uint32_t* tile_rows; int n_chunks, n_strips; uint32_t rows_magic; // reachable mask rows / columns per tile, see FilterArgs;
+    uint32_t* tile_rows; int n_chunks, n_strips; uint32_t rows_magic; // reachable mask rows / quad columns per tile, see BoxArgs;
                                   //   rows_magic = ceil(2^23 / rows per chunk)
     uint32_t* mask; size_t mask_words; int mask_aligned16; // caller-owned bit masks to clear on the side (mask_words = 0: none)
     // probe (optional): on every 16th image also count the cells that are hot under the current base and under the alternative
@@ -279,7 +315,6 @@ struct BrightArgs {
     int hot_words;                // words per image: hot_map_words(H, W, wide)
     uint32_t* zero_counters;      // not null: 256 words (the context's counter block) that workgroup 0 of the scan zeroes -- in place of a fill launch
     int mark_grid;                // > 0: workgroups of mark_tiles_kernel (its waves loop over the map); 0 = one piece per wave
-    uint32_t* tile_cols;          // [n_images][n_chunks][n_strips] beside tile_rows: bit b = some hot cell's rectangle overlaps mask byte column b of the tile
 };
 int hot_map_words(int H, int W, int wide);
 void launch_mark_tiles(const BrightArgs& a, hipStream_t s); // hot map -> tile boxes (tile_rows), behind launch_bright_cells

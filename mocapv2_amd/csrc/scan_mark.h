@@ -18,18 +18,10 @@ __device__ __forceinline__ uint32_t excess2_row(uint32_t lo, uint32_t hi, uint32
     return s - c8;
 }
 
-// The mask byte columns of strip `st` (bit b = columns 240 st + 8 b .. + 7, b = 0..29) that the columns [xa, xb] overlap, clipped to
-// the strip (the caller has found that they overlap it).
-__device__ __forceinline__ uint32_t tile_col_bits(int st, int xa, int xb)
-{
-    const int x0 = 240 * st, ca = xa > x0 ? xa - x0 : 0, cb = xb - x0 < 239 ? xb - x0 : 239;
-    return (2u << (cb >> 3)) - (1u << (ca >> 3));
-}
-
-// What a hot cell does: for every filter tile its reach (+ 4 pixels of blur and median) overlaps, that tile's box of
-// reachable mask rows and columns is widened, and the byte columns the rectangle overlaps are marked in the tile's column word.
-// rc = reach of the cell (x0 | x1 << 16, y0 | y1 << 16; x0 > x1: none), rows: the image's tile boxes, cols: its column words.
-__device__ __forceinline__ void widen_tile_boxes(const BrightArgs& a, const uint2 rc, uint32_t* __restrict__ rows, uint32_t* __restrict__ cols)
+// What a hot cell does: for every filter tile its reach (+ 4 pixels of blur and median) overlaps, the tile's record (kernels.h,
+// tile_quad_bits) is widened: its reachable mask rows, and the quad columns the rectangle overlaps.
+// rc = reach of the cell (x0 | x1 << 16, y0 | y1 << 16; x0 > x1: none), rec: the image's tile records.
+__device__ __forceinline__ void widen_tile_boxes(const BrightArgs& a, const uint2 rc, uint32_t* __restrict__ rec)
 {
     const int x0 = (int)(rc.x & 0xffffu), x1 = (int)(rc.x >> 16), y0 = (int)(rc.y & 0xffffu), y1 = (int)(rc.y >> 16);
     if (x0 > x1) return;
@@ -43,33 +35,29 @@ __device__ __forceinline__ void widen_tile_boxes(const BrightArgs& a, const uint
     for (int ch = ch0; ch <= ch1; ch++)
         for (int st = st0; st <= st1; st++) {
             const int t = ch * a.n_strips + st;
-            // a box that already holds the rectangle needs no atomics (boxes only grow inside a launch, so a stale
-            // value read here errs on the safe side): keeps a frame that is hot everywhere from serialising on them.  A rectangle
-            // inside the box is not yet inside the marked columns (one rectangle at the left and one at the right span it), hence
-            // the column word is read too, and each of the two is widened only where it does not hold the rectangle yet.
-            const uint32_t m = tile_col_bits(st, xa, xb);
-            const uint4 cur = *(const uint4*)(rows + 4 * t);
-            const uint32_t have = cols[t];
-            if (!(cur.x <= (uint32_t)ya && cur.y >= (uint32_t)yb && cur.z <= (uint32_t)xa && cur.w >= (uint32_t)xb)) {
-                atomicMin(&rows[4 * t], (uint32_t)ya);
-                atomicMax(&rows[4 * t + 1], (uint32_t)yb);
-                atomicMin(&rows[4 * t + 2], (uint32_t)xa);
-                atomicMax(&rows[4 * t + 3], (uint32_t)xb);
-            }
-            if ((have & m) != m) atomicOr(&cols[t], m);
+            // a record that already holds the rectangle needs no atomics (records only grow inside a launch, so a stale
+            // value read here errs on the safe side): keeps a frame that is hot everywhere from serialising on them.  One 16-byte
+            // load shows all of it; each of the four words is widened only where it does not hold the rectangle yet.
+            const uint64_t m = tile_quad_bits(st, xa, xb);
+            const uint32_t mlo = (uint32_t)m, mhi = (uint32_t)(m >> 32);
+            const uint4 cur = *(const uint4*)(rec + 4 * t);
+            if (cur.x > (uint32_t)ya) atomicMin(&rec[4 * t], (uint32_t)ya);
+            if (cur.y < (uint32_t)yb) atomicMax(&rec[4 * t + 1], (uint32_t)yb);
+            if ((cur.z & mlo) != mlo) atomicOr(&rec[4 * t + 2], mlo);
+            if ((cur.w & mhi) != mhi) atomicOr(&rec[4 * t + 3], mhi);
         }
 }
 
-// A cell whose doubled excess sum `acc` exceeds its threshold widens the boxes of the tiles it can reach -- from inside the
+// A cell whose doubled excess sum `acc` exceeds its threshold widens the records of the tiles it can reach -- from inside the
 // kernel that looks at the pixels (the fused Bayer pass).  reach / cflags: the tables of the image's undistort slot.
 __device__ __forceinline__ void mark_hot_cell(const BrightArgs& a, const uint2* __restrict__ reach, const uint8_t* __restrict__ cflags,
-                                              uint32_t* __restrict__ rows, uint32_t* __restrict__ cols, int ci, uint32_t acc)
+                                              uint32_t* __restrict__ rec, int ci, uint32_t acc)
 {
     if ((int)acc > a.hot_corner) { // rare: a few cells per marker
         // flag bits: the cell feeds windows cut by the image border in one axis (1) / in both (2): fewer taps, smaller bound
         const uint2 rc = reach[ci];
         const uint32_t fl = cflags[ci];
-        if ((int)acc > ((fl & 2u) ? a.hot_corner : (fl & 1u) ? a.hot_edge : a.hot)) widen_tile_boxes(a, rc, rows, cols);
+        if ((int)acc > ((fl & 2u) ? a.hot_corner : (fl & 1u) ? a.hot_edge : a.hot)) widen_tile_boxes(a, rc, rec);
     }
 }
 
