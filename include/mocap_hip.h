@@ -617,6 +617,14 @@ MOCAP_API int mocap_tile_stats(mocap_ctx_t ctx, uint64_t* tiles, uint64_t* skipp
  * 2 = always, 1 = unless the context's last probe found the scene crowded; the default).  All 0
  * when the batch took the dense path.  Any pointer may be null.  Synchronises the device. */
 MOCAP_API int mocap_list_stats(mocap_ctx_t ctx, uint32_t* items, uint32_t* wide, uint32_t* split);
+/* The context's own mask, read back for tests: the first n_images images of the mask mocap_blob_centroids (and its Bayer form)
+ * filters into, as the row-major mask of mocap_filter_mask ([n_images][height][ceil(width/32)] uint32; mask_dev zero-initialised by
+ * the caller).  That mask is never zeroed between batches.  The invariant it must keep, and this call exposes: after a batch every
+ * image of it is exactly that batch's filtered image -- zero outside the regions the batch's tiles recorded, whatever an earlier
+ * batch wrote there -- and the images beyond the batch still are what the last batch that held them left.  Reads only (no state of
+ * the context changes), ordered on `stream`, does not synchronise.  MOCAP_E_INVALID: n_images < 1, a null pointer, or more
+ * images than the own mask holds (0 before the first batch). */
+MOCAP_API int mocap_own_mask(mocap_ctx_t ctx, int n_images, uint32_t* mask_dev, void* stream);
 /* HIP-event timing of the kernels launched by mocap_blob_centroids / mocap_filter_mask / mocap_correspond / mocap_correspond_visible, recorded
  * on their stream.  mocap_profile_read synchronises, returns accumulated milliseconds and launch counts and resets:
  * index 0 = box_filter_kernel (or the general filter_mask_kernel), 1 = contours_kernel, 2 = correspond_kernel and

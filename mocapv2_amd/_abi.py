@@ -83,6 +83,7 @@ SIGNATURES = {
     "mocap_allgather_centroids": [_vp, _vp, _vp, _l, _vp],
     "mocap_tile_stats": [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
     "mocap_list_stats": [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
+    "mocap_own_mask": [_vp, _i, _vp, _vp],
     "mocap_profile_enable": [_vp, _i],
     "mocap_profile_read": [_vp, _dp, _ip],
 }

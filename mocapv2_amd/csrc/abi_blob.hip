@@ -197,6 +197,7 @@ static int filter_dense(mocap_ctx* c, const Batch& bt, const FilterPath& p, int 
     a.staged = p.rows_staged; a.stage_dw = p.rows_dw;
     if (p.bayer) { launch_bayer_gray(p.bl, bt.s); HIP_TRY(hipGetLastError()); }
     if (bt.own_mask) c->mask_dirty = true;
+    HIP_TRY(hipMemsetAsync(c->n_items, 0, 1024, bt.s)); // no work lists: mocap_list_stats reports none (not the previous batch's)
     EvPair ev; bool on;
     prof_begin(c, bt.s, ev, on);
     launch_filter_mask(a, p.remap, bt.s);
@@ -852,6 +853,20 @@ int mocap_list_stats(mocap_ctx_t c, uint32_t* items, uint32_t* wide, uint32_t* s
     if (items) *items = cnt[0];
     if (wide) *wide = cnt[8];
     if (split) *split = cnt[SPLIT_COUNTER];
+    return MOCAP_OK;
+}
+
+// read-back of the context's own mask (tests): a reader only -- no state of the context changes, no scratch, no synchronisation
+int mocap_own_mask(mocap_ctx_t c, int n_images, uint32_t* mask_dev, void* stream)
+{
+    if (!c) return fail(MOCAP_E_INVALID, "null argument");
+    if (n_images < 1) return fail(MOCAP_E_INVALID, "n_images = %d", n_images);
+    if (!mask_dev) return fail(MOCAP_E_INVALID, "null argument");
+    if ((size_t)n_images > c->mask_images)
+        return fail(MOCAP_E_INVALID, "n_images = %d, the context's own mask holds %zu images", n_images, c->mask_images);
+    if (set_device(c)) return MOCAP_E_HIP;
+    launch_mask_convert(c->mask, mask_dev, n_images, c->H, c->wpr, false, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
     return MOCAP_OK;
 }
 

@@ -896,6 +896,13 @@ class MocapContext:
         _abi.check(self.lib.mocap_list_stats(self._h, C.byref(a), C.byref(b), C.byref(s)))
         return a.value, b.value, s.value
 
+    def own_mask(self, n):
+        """The first n images of the context's own mask -- what blob_centroids filtered into, kept from batch to batch -- as the
+        row-major int32 [n, H, ceil(W / 32)] mask of filter_mask (mocap_own_mask).  Reads only; stream-ordered."""
+        mask = torch.zeros((int(n), self.height, (self.width + 31) // 32), dtype=torch.int32, device=self.device)
+        _abi.check(self.lib.mocap_own_mask(self._h, int(n), _ptr(mask), _stream()))
+        return mask
+
     def profile(self, on=True):
         _abi.check(self.lib.mocap_profile_enable(self._h, int(on)))
 
