@@ -1,6 +1,7 @@
 """NumPy restatement of the rig bundle adjustment that also refines every camera's lens, built on
 tests/rig_ba_ref.py, tests/rig_robust_ref.py and tests/lm_ref.py without a change to any of them, and the seeded cases the
-tests share.  Not a test module: the yardstick of tests/test_rig_selfcal_host.py and tests/test_gpu_rig_selfcal.py.
+tests share.  Not a test module: the yardstick of tests/test_rig_selfcal_host.py, tests/test_gpu_rig_selfcal.py and
+tests/test_gpu_rig_selfcal_shapes.py.
 
 Definition.  The problem of rig_robust_ref (point-major observations, partial visibility, camera 0 the world frame, loss none
 or Cauchy) with nine more unknowns per camera, camera 0 included: kd = (fx, fy, cx, cy, k1, k2, p1, p2, k3).  A camera's block
@@ -241,10 +242,12 @@ def rms_px(prob, cost):
     return float(np.sqrt(cost / len(prob.pt)))
 
 
-def order_spread(prob, kd, R, t, X, lam, masks, loss_c=None, n_perm=10):
+def order_spread(prob, kd, R, t, X, lam, masks, loss_c=None, n_perm=10, base=None):
     """rig_ba_ref.order_spread for these pieces: largest difference of cost, gradient, S and rhs between the sorted problem and
-    n_perm seeded permutations of its observations, each relative to the quantity's largest entry: dict name -> spread"""
-    base = linearize(prob.sorted(), kd, R, t, X, lam, masks, loss_c)
+    n_perm seeded permutations of its observations, each relative to the quantity's largest entry: dict name -> spread.
+    base: the sorted problem's pieces, where the caller has them already."""
+    if base is None:
+        base = linearize(prob.sorted(), kd, R, t, X, lam, masks, loss_c)
     out = {k: 0.0 for k in ("cost", "gradient", "S", "rhs")}
     for s in range(n_perm):
         lin = linearize(rb.permuted(prob, 1000 + s), kd, R, t, X, lam, masks, loss_c)
@@ -255,11 +258,13 @@ def order_spread(prob, kd, R, t, X, lam, masks, loss_c=None, n_perm=10):
 
 
 # ---- the cases ---------------------------------------------------------------------------------------------------------------
-def lens_case(n_cam, n_points, seed, sigma, dropout=0.3, width=1920, height=1080, extent=0.8):
+def lens_case(n_cam, n_points, seed, sigma, dropout=0.3, width=1920, height=1080, extent=0.8, central=0):
     """Seeded ring of n_cam cameras (synth.MixedScene) whose true K and lens differ per camera by seeded draws around
     synth.intrinsics and synth.MILD_DIST: from default_rng(seed), in this order, per camera f (+-2 %, fy = fx (1 +- 0.5 %)),
     the principal point (+-20 px), k1 (+-0.02), k2 (+-0.01), p1, p2 (+-1e-3); then rig_ba_ref._rig_case's draws (points,
-    dropout, noise) from default_rng(seed + 1).  Returns dict: scene, X, prob (true intrinsics), kd_true [C][9], sigma."""
+    dropout, noise) from default_rng(seed + 1).  central: after the draws the first `central` points are pulled to a tenth of
+    their distance from the origin and lose no view to the dropout, so that every camera sees them.
+    Returns dict: scene, X, prob (true intrinsics), kd_true [C][9], sigma."""
     from mocapv2_amd import synth
     rng = np.random.default_rng(seed)
     K0 = synth.intrinsics(width, height)
@@ -275,6 +280,8 @@ def lens_case(n_cam, n_points, seed, sigma, dropout=0.3, width=1920, height=1080
     X = rng.uniform(-extent, extent, size=(n_points, 3))
     drop = rng.uniform(0, 1, (n_points, n_cam)) < dropout
     noise = rng.normal(0, 1.0, (n_points, n_cam, 2)) * sigma
+    X[:central] *= 0.1
+    drop[:central] = False
     px = np.stack([scene.pixels(X, c) for c in range(n_cam)], 1) + noise
     z = np.stack([(X @ np.asarray(p["R"]).T + np.asarray(p["t"]).reshape(3))[:, 2] for p in scene.poses], 1)
     seen = (px[..., 0] >= 0) & (px[..., 0] < width) & (px[..., 1] >= 0) & (px[..., 1] < height) & (z > 0) & ~drop
@@ -298,12 +305,12 @@ def checkerboard_start(kd_true, seed, f=3e-3, center=3.0, radial=5e-3):
     return kd
 
 
-def small_case(n_cam, seed=31, n_points=60, views=None):
-    """The small rigs of the GPU tests: lens_case at sigma 0.3 with at most 60 points and a start moved off the truth
+def small_case(n_cam, seed=31, n_points=60, views=None, central=0):
+    """The rigs of the GPU tests: lens_case at sigma 0.3 (60 points drawn unless told otherwise) and a start moved off the truth
     (rig_ba_ref.perturbed_start's steps; the intrinsics by checkerboard_start).  views: no view is hidden, and point n keeps
     that many observations: of the cameras that see it, the first counted round the ring from camera n % C.
     Returns (prob, kd_true, kd_start, R, t, X)."""
-    c = lens_case(n_cam, n_points, seed, 0.3, dropout=0.0 if views else 0.3)
+    c = lens_case(n_cam, n_points, seed, 0.3, dropout=0.0 if views else 0.3, central=central)
     prob = c["prob"].sorted()
     if views:
         keep = np.zeros(len(prob.pt), bool)
@@ -343,3 +350,60 @@ def loop_case(name):
         masks = np.array(masks)
         _loop_cases[name] = (prob, kd, R, t, X, masks, loss_c, lm(prob, kd, R, t, X, masks, loss_c, ftol=LOOP_FTOL))
     return _loop_cases[name]
+
+
+def first_points(prob, X, n):
+    """(the problem of the first n points, renumbered and sorted, their start X [n][3]): sets N exactly"""
+    keep = prob.pt < n
+    points = np.unique(prob.pt[keep])
+    assert len(points) == n
+    return rb.Problem(np.searchsorted(points, prob.pt[keep]), prob.cam[keep], prob.uv[keep], prob.K, prob.dist, n).sorted(), X[points]
+
+
+# The rigs of tests/test_gpu_rig_selfcal_shapes.py, each named for the shape it reaches: name -> (cameras, points drawn, points
+# kept or None, points pulled to the centre, masks, loss scale or None, walks the loop).  PT_THREADS = SCHUR_CHUNK = 256 points
+# make a workgroup, 90 rows is the most the Cholesky holds in LDS, 32 cameras (480 rows, 528 pairs) the most a rig may have.
+_MIXED6 = [0, 0x1FF, 0x03F, 0x003, 0x1FF, 0x00F]
+SHAPE_CASES = {
+    "two": (2, 600, None, 0, [0, 0x003], None, True),
+    "six_lds": (6, 60, None, 0, _MIXED6, None, True),
+    "six_600": (6, 600, None, 0, _MIXED6, None, True),
+    "six_600_cauchy": (6, 600, None, 0, _MIXED6, 2.0, True),
+    "blocks_255": (4, 600, 255, 0, LOOP_CASES["mixed4"][2], None, True),
+    "blocks_256": (4, 600, 256, 0, LOOP_CASES["mixed4"][2], None, True),
+    "blocks_257": (4, 600, 257, 0, LOOP_CASES["mixed4"][2], None, True),
+    "blocks_513": (4, 600, 513, 0, LOOP_CASES["mixed4"][2], None, True),
+    "rig32": (32, 140, None, 4, [0x03F] * 32, None, True),
+    "rig32_cauchy": (32, 140, None, 4, [0x03F] * 32, 2.0, True),
+    "chunk_growth": (2, 140000, 65537, 0, [0, 0x003], None, False),  # 3 s a linearisation here: pieces only
+}
+SHAPE_LOOPS = [k for k, v in SHAPE_CASES.items() if v[6]]
+
+
+def lin_blocks(N):
+    """Workgroups of the point-owning kernels (selfcal_lin_blocks)"""
+    return -(-N // 256)
+
+
+def schur_chunks(N):
+    """(points per workgroup of the Schur kernel, workgroups): 256 points, or what leaves 256 workgroups (selfcal_schur_chunk)"""
+    chunk = max(256, -(-N // 256))
+    return chunk, -(-N // chunk)
+
+
+_shape_cases = {}
+
+
+def shape_case(name):
+    """loop_case for SHAPE_CASES; the loop is None for a case that does not walk it"""
+    if name not in _shape_cases:
+        n_cam, n_points, n_keep, central, masks, loss_c, loop = SHAPE_CASES[name]
+        prob, _, kd, R, t, X = small_case(n_cam, n_points=n_points, central=central)
+        if n_keep:
+            prob, X = first_points(prob, X, n_keep)
+        # the gauge of the definition, which the device imposes on the state it is handed and `lm` on its own: perturbed_start
+        # leaves camera 0 a few 1e-16 off the world frame, and `linearize` would take that as it comes
+        R[0], t[0] = np.eye(3), 0.0
+        masks = np.array(masks)
+        _shape_cases[name] = (prob, kd, R, t, X, masks, loss_c, lm(prob, kd, R, t, X, masks, loss_c, ftol=LOOP_FTOL) if loop else None)
+    return _shape_cases[name]

@@ -7,11 +7,9 @@ import numpy as np
 import pytest
 
 import rig_selfcal_ref as sc
+from rig_selfcal_gpu import adjust, adjust_raw, assert_loop_walks_the_restatements, assert_pieces_agree, gpu_args, loss_args, poses12
 
 pytestmark = pytest.mark.gpu
-
-U = float(np.finfo(float).eps) / 2  # unit roundoff of FP64, 1.1e-16
-P = sc.P
 
 
 @pytest.fixture(scope="module")
@@ -20,44 +18,7 @@ def ctx():
     return MocapContext(1, 1)
 
 
-def poses12(R, t):
-    return np.c_[np.asarray(R, float).reshape(len(R), 9), np.asarray(t, float).reshape(len(R), 3)]
-
-
-def gpu_args(prob, R, t, X):
-    return (*prob.point_major(), poses12(R, t), X)
-
-
-def loss_args(loss_c):
-    return {} if loss_c is None else {"loss": "cauchy", "loss_scale": loss_c}
-
-
-def adjust(ctx, prob, kd, R, t, X, masks, loss_c=None, **kw):
-    return ctx.rig_bundle_adjust_intrinsics(*prob.point_major(), kd, masks, poses12(R, t), X, **loss_args(loss_c), **kw)
-
-
-def rot_err(Ra, Rb):
-    return float(np.linalg.norm(Ra @ Rb.T - np.eye(3)) / np.sqrt(2))  # = 2 sin(angle / 2), about the angle in radians
-
-
 MIXED = ["mixed3", "mixed3_cauchy", "mixed4", "mixed4_cauchy"]
-
-
-def damping_allowance(ref):
-    """What the loop test's allowance on the costs, 1e-8 of each, leaves of the damping's agreement, per iteration, from the
-    restatement's own history.  An accepted step multiplies lambda by mu = max(1/3, 1 - (2 rho - 1)^3) with rho = (cost - trial)
-    / predicted.  Two costs known to 1e-8 of themselves leave their difference known to 2e-8 / rel of itself, rel the step's
-    relative decrease -- near the stop, where rel is about ftol, rho is hardly known at all; the predicted reduction comes
-    from the step, 1e-6.  d mu / d rho = 6 (2 rho - 1)^2 above the floor of 1/3, 0 on it; a rejected step multiplies by nu
-    exactly.  The errors of the factors add up along the loop: entry k is the allowance on the lambda iteration k was solved
-    with."""
-    h, rho = ref["history"], ref["rho"]
-    before = np.r_[ref["cost_initial"], h[:-1, 0]]
-    with np.errstate(all="ignore"):
-        rel = (before - h[:, 0]) / before
-        mu = 1.0 - (2.0 * rho - 1.0) ** 3
-        factor = np.where((h[:, 2] > 0) & (mu > 1.0 / 3.0), 6.0 * (2.0 * rho - 1.0) ** 2 * np.abs(rho) / mu * (2e-8 / rel + 1e-6), 0.0)
-    return 1e-12 + np.r_[0.0, np.cumsum(factor)[:-1]]
 
 
 # ---- 1. pieces ------------------------------------------------------------------------------------------------------------------
@@ -84,20 +45,7 @@ def test_pieces_agree_with_the_restatement(ctx, name):
     spread = sc.order_spread(prob, kd, R, t, X, 1e-3, masks, loss_c)
     ref = sc.linearize(prob.sorted(), kd, R, t, X, 1e-3, masks, loss_c)
     got = ctx.rig_linearize_intrinsics(*prob.point_major(), kd, masks, poses12(R, t), X, 1e-3, **loss_args(loss_c))
-    assert not got["behind"]
-    allowed = {k: 8 * spread[k] + (4 * U if k == "cost" else 0.0) for k in spread}
-    for k in ("cost", "gradient", "S", "rhs"):
-        a, b = np.asarray(ref[k], float), np.asarray(got[k], float)
-        diff = float(np.abs(a - b).max() / np.abs(a).max())
-        print(f"{name} {k}: restatement's spread {spread[k]:.3e}  GPU - restatement {diff:.3e}  allowed {allowed[k]:.3e}")
-    for k in ("cost", "gradient", "S", "rhs"):
-        a, b = np.asarray(ref[k], float), np.asarray(got[k], float)
-        assert a.shape == b.shape and np.abs(a - b).max() <= allowed[k] * np.abs(a).max(), k
-        assert spread[k] > 0 or k == "cost"
-    assert np.array_equal(got["S"], got["S"].T)
-    fixed = ~sc.free_columns(masks, prob.C).reshape(-1)
-    assert fixed.sum() >= 15 + 3  # camera 0 whole, and the three lens parameters mask 0x03F leaves out
-    assert np.array_equal(got["S"][fixed], np.eye(P * prob.C)[fixed]) and not got["rhs"][fixed].any() and not got["gradient"][:P * prob.C][fixed].any()
+    assert_pieces_agree(name, prob, masks, got, ref, spread)
 
 
 # ---- 2. loop --------------------------------------------------------------------------------------------------------------------
@@ -122,39 +70,7 @@ def test_loop_walks_the_restatements_iterations(ctx, name):
     kd against what it moved 6.3e-12 / 5.7e-11 / 5.7e-13 / 2.2e-12 / 6.6e-11, rotations, t and points 2.2e-12 / 2.3e-11 / 2.9e-13 /
     3.7e-13 / 7.9e-11; lambda 1.3e-7 / 4.1e-6 / 1.8e-10 / 1.8e-10 / 1.8e-7 (at the last iterations, where the allowance is 1e-4
     and more), step lengths 5.1e-9 / 3.3e-8 / 3.9e-9 / 1.4e-9 / 1.6e-7."""
-    prob, kd, R, t, X, masks, loss_c, ref = sc.loop_case(name)
-    got = adjust(ctx, prob, kd, R, t, X, masks, loss_c, ftol=sc.LOOP_FTOL)
-    m = min(len(ref["history"]), len(got["history"]))
-    rel = np.abs(got["history"][:m, 0] - ref["history"][:m, 0]) / ref["history"][:m, 0]
-    Rg, tg = got["poses"][:, :9].reshape(-1, 3, 3), got["poses"][:, 9:]
-    moved = {"R": max(rot_err(ref["R"][c], R[c]) for c in range(1, prob.C)), "t": np.abs(ref["t"] - t).max(), "X": np.abs(ref["X"] - X).max()}
-    diff = {"R": max(rot_err(Rg[c], ref["R"][c]) for c in range(prob.C)), "t": np.abs(tg - ref["t"]).max(), "X": np.abs(got["points"] - ref["X"]).max()}
-    kd_moved, kd_diff = np.abs(ref["kd"] - kd).max(0), np.abs(got["intrinsics"] - ref["kd"]).max(0)
-    print(f"{name}: iterations {got['iterations']} / {ref['iterations']}  status {got['status']} / {ref['status']}")
-    print("accepted", got["history"][:, 2], "restatement", ref["history"][:, 2])
-    print("cost, relative difference per iteration", rel, "largest", rel.max())
-    print("kd: moved", kd_moved, "GPU - restatement", kd_diff)
-    print("poses and points: moved", moved, "GPU - restatement", diff)
-    assert got["iterations"] == ref["iterations"] and got["status"] == ref["status"] == sc.STOP_FTOL
-    assert np.array_equal(got["history"][:, 2], ref["history"][:, 2])
-    assert (rel <= 1e-8).all()
-    lam_allowed = damping_allowance(ref)
-    lam_rel, step_rel = np.abs(got["history"][:, 1] / ref["history"][:, 1] - 1), np.abs(got["history"][:, 3] / ref["history"][:, 3] - 1)
-    print("lambda, relative difference", lam_rel, "allowed", lam_allowed, "step", step_rel)
-    assert (lam_rel <= lam_allowed).all()              # the damping follows rho
-    assert (step_rel <= 1e-6 + lam_allowed).all()      # and the steps have the same length
-    assert abs(got["cost_initial"] / ref["cost_initial"] - 1) < 1e-12 and abs(got["cost"] / ref["cost"] - 1) < 1e-8
-    free = sc.free_columns(masks, prob.C)[:, :9]
-    assert (kd_diff <= 1e-6 * kd_moved).all() and (kd_moved[free.any(0)] > 0).all()
-    for k in diff:
-        assert diff[k] <= 1e-6 * moved[k], k
-    # the gauge: camera 0 is the world frame, |t_1| is the start's
-    assert np.array_equal(got["poses"][0], np.r_[np.eye(3).reshape(9), 0, 0, 0])
-    assert abs(np.linalg.norm(tg[1]) - np.linalg.norm(t[1])) <= 4 * U * np.linalg.norm(t[1])
-    # obs_err is the residual of the returned state under the returned lenses
-    s = got["obs_err"] ** 2
-    cost = 0.5 * np.sum(s if loss_c is None else loss_c ** 2 * np.log1p(s / loss_c ** 2))
-    assert abs(cost / got["cost"] - 1) < 1e-9
+    assert_loop_walks_the_restatements(ctx, name, sc.loop_case(name))
 
 
 # ---- 3. masks, failures, bits -----------------------------------------------------------------------------------------------------
@@ -198,23 +114,11 @@ def test_a_point_behind_a_camera_leaves_everything_as_it_was(ctx):
         adjust(ctx, prob, kd, R, t, X2, masks)
     assert e.value.code == -3
     # through the C-ABI, where the arrays can be looked at after the negative status
-    import ctypes as C
-    import torch
-    from mocapv2_amd.engine import _ptr, _stream
-    dev = ctx.device
-    d = {k: torch.from_numpy(np.ascontiguousarray(v)).to(dev) for k, v in
-         (("off", off), ("cam", cam), ("uv", uv), ("kd", kd), ("poses", poses12(R, t)), ("pts", X2))}
-    hist = torch.zeros((10, 4), dtype=torch.float64, device=dev)
-    result = torch.zeros((4,), dtype=torch.float64, device=dev)
-    mask = np.ascontiguousarray(masks, np.int32)
-    rc = ctx.lib.mocap_rig_bundle_adjust_intrinsics(ctx._h, prob.C, prob.N, len(cam), _ptr(d["off"]), _ptr(d["cam"]), _ptr(d["uv"]), _ptr(d["kd"]),
-                                                    mask.ctypes.data_as(C.POINTER(C.c_int)), _ptr(d["poses"]), _ptr(d["pts"]), 10, 1e-12, 1e-3,
-                                                    _ptr(hist), _ptr(result), 0, 0.0, None, None, _stream())
-    ctx.sync()
-    assert rc == 0 and result.cpu().numpy()[0] == -3
-    assert d["kd"].cpu().numpy().tobytes() == kd.tobytes()
-    assert d["poses"].cpu().numpy().tobytes() == poses12(R, t).tobytes() and d["pts"].cpu().numpy().tobytes() == X2.tobytes()
-    assert not hist.cpu().numpy().any()
+    rc, result, kd2, poses2, pts2, hist = adjust_raw(ctx, off, cam, uv, kd, masks, poses12(R, t), X2, prob.C, prob.N)
+    assert rc == 0 and result[0] == -3
+    assert kd2.tobytes() == kd.tobytes()
+    assert poses2.tobytes() == poses12(R, t).tobytes() and pts2.tobytes() == X2.tobytes()
+    assert not hist.any()
 
 
 def test_two_runs_give_the_same_bits_also_after_a_larger_problem(ctx):

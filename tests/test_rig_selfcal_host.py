@@ -183,6 +183,65 @@ def test_loop_cases_are_far_from_every_decision_boundary(name):
     assert cond < 1e6
 
 
+@pytest.mark.parametrize("name", sc.SHAPE_LOOPS)
+def test_shape_loop_cases_are_far_from_every_decision_boundary(name):
+    """The same four conditions for the rigs tests/test_gpu_rig_selfcal_shapes.py walks beside the restatement (and the
+    blocks_* cases it only linearises).
+    Measured, in the order iterations, smallest |rho|, the two relative decreases nearest ftol as multiples of it, scaled
+    cond(S):            two             13  0.67  9.2 x / 0.018 x   6.1e2
+                        six_lds         10  0.99  2.15 x / 0.29 x   4.6e3
+                        six_600          9  1.0   6.5 x / 0.072 x   4.0e3
+                        six_600_cauchy   9  1.0   13 x / 0.25 x     4.2e3
+                        blocks_255       9  0.99  6.8 x / 0.0077 x  3.2e3
+                        blocks_256       9  0.99  7.0 x / 0.0088 x  3.2e3
+                        blocks_257       9  0.99  7.8 x / 0.0094 x  3.1e3
+                        blocks_513       9  1.0   8.8 x / 0.014 x   3.4e3
+                        rig32           12  0.98  7.0 x / 0.36 x    4.7e3
+                        rig32_cauchy    12  0.99  9.7 x / 0.67 x    5.4e3
+    Every step of every case is accepted and every stop is ftol's."""
+    prob, kd, R, t, X, masks, loss_c, ref = sc.shape_case(name)
+    cost = np.r_[ref["cost_initial"], ref["history"][:, 0]]
+    rel = (cost[:-1] - cost[1:])[ref["history"][:, 2] > 0] / cost[:-1][ref["history"][:, 2] > 0]
+    lin = sc.linearize(prob, kd, R, t, X, 1e-3, masks, loss_c)
+    d = np.sqrt(np.diag(lin["S"]))
+    cond = np.linalg.cond(lin["S"] / d[:, None] / d[None, :])
+    print(f"{name}: {ref['iterations']} iterations, status {ref['status']}, smallest |rho| {np.abs(ref['rho']).min():.3g}, relative "
+          f"decreases nearest ftol {rel[np.argsort(np.abs(np.log(rel / sc.LOOP_FTOL)))[:2]] / sc.LOOP_FTOL} x ftol, scaled cond(S) {cond:.3e}")
+    assert ref["status"] == sc.STOP_FTOL and ref["iterations"] < 50
+    assert (np.abs(ref["rho"]) >= 1e-3).all()
+    assert ((rel >= 1.2 * sc.LOOP_FTOL) | (rel <= sc.LOOP_FTOL / 1.2)).all()
+    assert cond < 1e6
+
+
+def test_shape_cases_have_the_shapes_they_are_named_for():
+    """What each case of SHAPE_CASES is there for, restated from its sizes: the workgroups of the point kernels and the Schur
+    kernel's chunks (PT_THREADS = SCHUR_CHUNK = 256 in csrc/rig_selfcal.hip), the rows of S against the 90 the Cholesky holds in
+    LDS and the 480 of the largest rig, and for rig32 a point that all 32 cameras see (bit 31 of a visibility mask, every one of
+    the 528 pairs) and observations in camera 31.  Every case passes the layout check."""
+    import re
+    with open(os.path.join(ROOT, "mocapv2_amd", "csrc", "rig_selfcal.hip")) as f:
+        source = f.read()
+    constants = {k: int(v) for k, v in re.findall(r"constexpr int (PT_THREADS|SCHUR_CHUNK|CHOL_LDS_ROWS) = (\d+);", source)}
+    assert constants == {"PT_THREADS": 256, "SCHUR_CHUNK": 256, "CHOL_LDS_ROWS": 90}  # what lin_blocks and schur_chunks restate
+    for name, (n_cam, _, n_keep, _, masks, _, _) in sc.SHAPE_CASES.items():
+        prob, _, _, _, X, m, _, _ = sc.shape_case(name)
+        assert prob.C == n_cam and len(X) == prob.N and (n_keep is None or prob.N == n_keep) and sc.layout_ok(prob, m), name
+        assert np.array_equal(prob.pt, np.sort(prob.pt)) and (np.bincount(prob.pt, minlength=prob.N) >= 2).all(), name
+    sizes = {name: sc.shape_case(name)[0] for name in sc.SHAPE_CASES}
+    assert sizes["two"].N == 289 and sc.lin_blocks(289) == 2 and np.bincount(sizes["two"].pt).tolist() == [2] * 289
+    assert sc.P * sizes["six_lds"].C == 90 and sizes["six_lds"].N == 59
+    assert sizes["six_600"].N == 594 and len(sizes["six_600"].pt) == 2554 and sc.lin_blocks(594) == 3 and sc.schur_chunks(594) == (256, 3)
+    for n, blocks in ((255, 1), (256, 1), (257, 2), (513, 3)):
+        assert sizes[f"blocks_{n}"].N == n and sc.lin_blocks(n) == blocks and sc.schur_chunks(n) == (256, blocks)
+    rig = sizes["rig32"]
+    count = np.bincount(rig.cam, minlength=32)
+    assert sc.P * rig.C == 480 and rig.N == 140 and rig.C * (rig.C + 1) // 2 == 528
+    assert (np.bincount(rig.pt) == 32).sum() >= 1 and count[31] > 0 and count.min() >= 2 * 6
+    print(f"rig32: {len(rig.pt)} observations, {(np.bincount(rig.pt) == 32).sum()} points seen by all cameras, at least {count.min()} per camera")
+    grown = sizes["chunk_growth"]
+    assert grown.N == 65537 and sc.schur_chunks(grown.N) == (257, 256) and sc.lin_blocks(grown.N) == 257
+
+
 def test_the_named_masks_are_the_python_surfaces():
     from mocapv2_amd import calibrate
     assert calibrate.REFINE_MASKS == sc.MASKS
