@@ -1,5 +1,6 @@
 // abi_calib.hip -- C-ABI host file: the calibration solvers (fundamental matrices by RANSAC, the rig's bundle adjustment, the
 // cameras' intrinsics).
+#include <functional>
 #include "ctx.h"
 
 extern "C" {
@@ -49,25 +50,27 @@ int mocap_fundamental_ransac(mocap_ctx_t c, int n_pairs, const double* pts_a, co
     return MOCAP_OK;
 }
 
-// The scratch of a rig bundle adjustment, carved out of one block the context owns (grown to twice what a call needs).  The
-// partition depends on the problem's sizes alone, never on the block's: a call's results do not depend on earlier calls.
-static int rig_args(mocap_ctx* c, int C, int N, int n_obs, const int32_t* obs_offset, const int32_t* obs_cam, const double* obs_uv,
-                    double* poses, double* points, RigArgs& a)
+// The scratch of a rig bundle adjustment by the solver sv, carved out of one block the context owns (grown to twice what a
+// call needs; calls on one context are ordered on one stream).  The partition depends on the problem's sizes alone, never on
+// the block's: a call's results do not depend on earlier calls.  `own` takes the solver's own buffers, behind the state record.
+static int rig_args(mocap_ctx* c, const RigSolver& sv, int C, int N, int n_obs, const int32_t* obs_offset, const int32_t* obs_cam,
+                    const double* obs_uv, double* poses, double* points, RigArgs& a, const std::function<void(Carver&)>& own)
 {
     if (C < 2 || C > 32 || N < 1 || N > (1 << 24) || n_obs < 2 * (long long)N || n_obs > (long long)N * C)
         return fail(MOCAP_E_INVALID, "C=%d N=%d n_obs=%d: 2..32 cameras, 1..2^24 points, 2..C observations per point", C, N, n_obs);
-    if (c->n_cam < C) return fail(MOCAP_E_STATE, "mocap_set_cameras: %d cameras set, %d needed (their K and dist are used)", c->n_cam, C);
     a = RigArgs{};
-    a.cams = c->cams; a.obs_offset = obs_offset; a.obs_cam = obs_cam; a.obs_uv = obs_uv; a.C = C; a.N = N; a.n_obs = n_obs;
-    a.n_pairs = (C - 1) * C / 2; a.n_lin_blocks = rig_lin_blocks(N); a.n_chunks = rig_schur_chunks(N);
+    a.obs_offset = obs_offset; a.obs_cam = obs_cam; a.obs_uv = obs_uv; a.C = C; a.N = N; a.n_obs = n_obs;
+    const int blocks = C - sv.FIRST, chunk = sv.schur_chunk(N); // cameras that have a block
+    a.n_pairs = blocks * (blocks + 1) / 2; a.n_lin_blocks = (N + PT_THREADS - 1) / PT_THREADS; a.n_chunks = (N + chunk - 1) / chunk;
     a.poses_io = poses; a.points_io = points;
-    const size_t D = 6 * (size_t)(C - 1);
+    const size_t P = sv.P, D = P * blocks;
     auto carve = [&](char* base) {
         Carver k{base};
-        k.take(a.state, 1); k.take(a.poses, 2 * 12 * (size_t)C); k.take(a.points, 2 * 3 * (size_t)N); k.take(a.mask, N);
-        k.take(a.W, 18 * (size_t)n_obs); k.take(a.Vinv, 6 * (size_t)N); k.take(a.vdiag, 3 * (size_t)N); k.take(a.gp, 3 * (size_t)N);
-        k.take(a.lin_part, 27 * (size_t)a.n_lin_blocks * (C - 1)); k.take(a.cost_part, a.n_lin_blocks);
-        k.take(a.schur_part, 42 * (size_t)a.n_chunks * a.n_pairs);
+        k.take(a.state, 1); own(k);
+        k.take(a.poses, 2 * 12 * (size_t)C); k.take(a.points, 2 * 3 * (size_t)N); k.take(a.mask, N);
+        k.take(a.W, 3 * P * (size_t)n_obs); k.take(a.Vinv, 6 * (size_t)N); k.take(a.vdiag, 3 * (size_t)N); k.take(a.gp, 3 * (size_t)N);
+        k.take(a.lin_part, (P * (P + 1) / 2 + P) * (size_t)a.n_lin_blocks * blocks); k.take(a.cost_part, a.n_lin_blocks);
+        k.take(a.schur_part, (P * P + P) * (size_t)a.n_chunks * a.n_pairs);
         k.take(a.S, D * D); k.take(a.rhs, D); k.take(a.gc, D); k.take(a.udiag, D); k.take(a.chol, D * (D + 1) / 2); k.take(a.delta_c, D);
         k.take(a.upd_part, 3 * (size_t)a.n_lin_blocks); k.take(a.scalars, RIG_N_SCALARS);
         return k.used;
@@ -78,7 +81,48 @@ static int rig_args(mocap_ctx* c, int C, int N, int n_obs, const int32_t* obs_of
     return 0;
 }
 
-// The loss of the two robust entries, checked before anything is launched: its number, and with Cauchy a finite scale > 0.
+// The plain solver's: the lenses are the context's cameras'.  Clears the state record.
+static int pose_args(mocap_ctx* c, int C, int N, int n_obs, const int32_t* obs_offset, const int32_t* obs_cam, const double* obs_uv,
+                     double* poses, double* points, hipStream_t s, RigArgs& a)
+{
+    TRY(rig_args(c, rig_pose_solver(), C, N, n_obs, obs_offset, obs_cam, obs_uv, poses, points, a, [](Carver&) {}));
+    if (c->n_cam < C) return fail(MOCAP_E_STATE, "mocap_set_cameras: %d cameras set, %d needed (their K and dist are used)", c->n_cam, C);
+    a.cams = c->cams;
+    HIP_TRY(hipMemsetAsync(a.state, 0, sizeof(RigState), s));
+    return 0;
+}
+
+// The lens-refining solver's, with the checks that need the caller's mask and a host copy of kd: nothing is launched for a
+// mask with bits above 8 or a kd that is not finite or has fx, fy <= 0.  Uploads the cameras' free columns, clears the state
+// record and the cameras' counts.
+static int lens_args(mocap_ctx* c, int C, int N, int n_obs, const int32_t* obs_offset, const int32_t* obs_cam, const double* obs_uv,
+                     double* kd, const int32_t* refine_mask_host, double* poses, double* points, hipStream_t s, RigArgs& a)
+{
+    int32_t* d_free;
+    TRY(rig_args(c, rig_lens_solver(), C, N, n_obs, obs_offset, obs_cam, obs_uv, poses, points, a, [&](Carver& k) {
+        k.take(a.cam_count, C); // cleared with the state record as one span up to d_free
+        k.take(d_free, C); k.take(a.kd, 2 * 9 * (size_t)C);
+    }));
+    int32_t free_cols[32];
+    for (int k = 0; k < C; k++) {
+        if (refine_mask_host[k] < 0 || refine_mask_host[k] > 0x1ff)
+            return fail(MOCAP_E_INVALID, "refine_mask[%d] = 0x%x: bits 0..8 (fx, fy, cx, cy, k1, k2, p1, p2, k3)", k, (unsigned)refine_mask_host[k]);
+        free_cols[k] = refine_mask_host[k] | (k > 0 ? 0x3f << 9 : 0);
+    }
+    double kd_host[32 * 9];
+    HIP_TRY(hipMemcpyAsync(kd_host, kd, 8 * 9 * (size_t)C, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int k = 0; k < 9 * C; k++)
+        if (!(fabs(kd_host[k]) <= 1.7976931348623157e308) || (k % 9 < 2 && !(kd_host[k] > 0.0)))
+            return fail(MOCAP_E_INVALID, "kd[%d][%d] = %g: every entry finite, fx and fy > 0", k / 9, k % 9, kd_host[k]);
+    a.kd_io = kd; a.free_cols = d_free; a.schur_chunk = rig_lens_solver().schur_chunk(N);
+    // pageable host memory: the copy has left `free_cols` when this returns
+    HIP_TRY(hipMemcpyAsync(d_free, free_cols, sizeof(int32_t) * C, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(a.state, 0, (char*)d_free - (char*)a.state, s));
+    return 0;
+}
+
+// The loss of the robust entries, checked before anything is launched: its number, and with Cauchy a finite scale > 0.
 static int rig_loss(int loss, double loss_scale)
 {
     if (loss != MOCAP_RIG_LOSS_NONE && loss != MOCAP_RIG_LOSS_CAUCHY)
@@ -86,6 +130,45 @@ static int rig_loss(int loss, double loss_scale)
     if (loss == MOCAP_RIG_LOSS_CAUCHY && (!(loss_scale > 0.0) || !(loss_scale <= 1.7976931348623157e308)))
         return fail(MOCAP_E_INVALID, "loss_scale = %g: the Cauchy loss needs a finite scale > 0 (pixels)", loss_scale);
     return 0;
+}
+
+// Linearises the state handed in (it is only read: the init kernel copies it, no finish kernel runs) and copies out what the
+// linearize entries return.
+static int rig_linearize(const RigSolver& sv, RigArgs& a, double lambda, int loss, double loss_scale, double* cost, double* gradient,
+                         double* S, double* rhs, int32_t* status, hipStream_t s)
+{
+    a.loss = loss; a.loss_c2 = loss_scale * loss_scale;
+    const size_t D = sv.P * (size_t)(a.C - sv.FIRST);
+    sv.init(a, lambda, s);
+    sv.linearize(a, s);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(cost, a.scalars + RIG_LIN_COST, 8, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(gradient, a.gc, 8 * D, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(gradient + D, a.gp, 8 * 3 * (size_t)a.N, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(S, a.S, 8 * D * D, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(rhs, a.rhs, 8 * D, hipMemcpyDeviceToDevice, s));
+    // status: (layout error, a point not in front of a camera that sees it)
+    HIP_TRY(hipMemcpyAsync(status, &a.state->layout_err, 4, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(status + 1, &a.state->behind, 4, hipMemcpyDeviceToDevice, s));
+    return MOCAP_OK;
+}
+
+// The loop: the caller's outputs cleared, then init, max_iters iterations, finish and, where asked for, the residuals.
+static int rig_adjust(const RigSolver& sv, RigArgs& a, int max_iters, double ftol, double lambda0, double* history, double* result,
+                      int loss, double loss_scale, double* obs_err, double* obs_weight, hipStream_t s)
+{
+    a.history = history; a.result = result;
+    a.loss = loss; a.loss_c2 = loss_scale * loss_scale; a.obs_err = obs_err; a.obs_weight = obs_weight;
+    HIP_TRY(hipMemsetAsync(history, 0, 8 * 4 * (size_t)max_iters, s));
+    if (obs_err) HIP_TRY(hipMemsetAsync(obs_err, 0, 8 * (size_t)a.n_obs, s));
+    if (obs_weight) HIP_TRY(hipMemsetAsync(obs_weight, 0, 8 * (size_t)a.n_obs, s));
+    sv.init(a, lambda0, s);
+    // every iteration is enqueued; the kernels of an iteration after the stop return at once (DESIGN.md section 4.6)
+    for (int it = 0; it < max_iters; it++) sv.iteration(a, it, max_iters, ftol, s);
+    sv.finish(a, s);
+    if (obs_err || obs_weight) sv.residuals(a, s);
+    HIP_TRY(hipGetLastError());
+    return MOCAP_OK;
 }
 
 int mocap_rig_linearize(mocap_ctx_t c, int C, int N, int n_obs, const int32_t* obs_offset, const int32_t* obs_cam, const double* obs_uv,
@@ -106,25 +189,10 @@ int mocap_rig_linearize_robust(mocap_ctx_t c, int C, int N, int n_obs, const int
     TRY(rig_loss(loss, loss_scale));
     if (set_device(c)) return MOCAP_E_HIP;
     std::lock_guard<std::mutex> lk(c->mu);
-    RigArgs a;
-    // (the state handed in is only read: the init kernel copies it, no finish kernel runs)
-    TRY(rig_args(c, C, N, n_obs, obs_offset, obs_cam, obs_uv, const_cast<double*>(poses), const_cast<double*>(points), a));
-    a.loss = loss; a.loss_c2 = loss_scale * loss_scale;
     hipStream_t s = (hipStream_t)stream;
-    const size_t D = 6 * (size_t)(C - 1);
-    HIP_TRY(hipMemsetAsync(a.state, 0, sizeof(RigState), s));
-    launch_rig_init(a, lambda, s);
-    launch_rig_linearize(a, s);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(cost, a.scalars + RIG_LIN_COST, 8, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipMemcpyAsync(gradient, a.gc, 8 * D, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipMemcpyAsync(gradient + D, a.gp, 8 * 3 * (size_t)N, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipMemcpyAsync(S, a.S, 8 * D * D, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipMemcpyAsync(rhs, a.rhs, 8 * D, hipMemcpyDeviceToDevice, s));
-    // status: (layout error, a point not in front of a camera that sees it)
-    HIP_TRY(hipMemcpyAsync(status, &a.state->layout_err, 4, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipMemcpyAsync(status + 1, &a.state->behind, 4, hipMemcpyDeviceToDevice, s));
-    return MOCAP_OK;
+    RigArgs a;
+    TRY(pose_args(c, C, N, n_obs, obs_offset, obs_cam, obs_uv, const_cast<double*>(poses), const_cast<double*>(points), s, a));
+    return rig_linearize(rig_pose_solver(), a, lambda, loss, loss_scale, cost, gradient, S, rhs, status, s);
 }
 
 int mocap_rig_bundle_adjust(mocap_ctx_t c, int C, int N, int n_obs, const int32_t* obs_offset, const int32_t* obs_cam,
@@ -146,71 +214,10 @@ int mocap_rig_bundle_adjust_robust(mocap_ctx_t c, int C, int N, int n_obs, const
     TRY(rig_loss(loss, loss_scale));
     if (set_device(c)) return MOCAP_E_HIP;
     std::lock_guard<std::mutex> lk(c->mu);
-    RigArgs a;
-    TRY(rig_args(c, C, N, n_obs, obs_offset, obs_cam, obs_uv, poses, points, a));
-    a.history = history; a.result = result;
-    a.loss = loss; a.loss_c2 = loss_scale * loss_scale; a.obs_err = obs_err; a.obs_weight = obs_weight;
     hipStream_t s = (hipStream_t)stream;
-    HIP_TRY(hipMemsetAsync(a.state, 0, sizeof(RigState), s));
-    HIP_TRY(hipMemsetAsync(history, 0, 8 * 4 * (size_t)max_iters, s));
-    if (obs_err) HIP_TRY(hipMemsetAsync(obs_err, 0, 8 * (size_t)n_obs, s));
-    if (obs_weight) HIP_TRY(hipMemsetAsync(obs_weight, 0, 8 * (size_t)n_obs, s));
-    launch_rig_init(a, lambda0, s);
-    // every iteration is enqueued; the kernels of an iteration after the stop return at once (DESIGN.md section 4.6)
-    for (int it = 0; it < max_iters; it++) launch_rig_iteration(a, it, max_iters, ftol, s);
-    launch_rig_finish(a, s);
-    if (obs_err || obs_weight) launch_rig_residuals(a, s);
-    HIP_TRY(hipGetLastError());
-    return MOCAP_OK;
-}
-
-// The scratch of a rig adjustment with the lenses among its unknowns, carved out of the rig adjustment's block (calls on one
-// context are ordered on one stream), after the checks that need the caller's mask and a host copy of kd: nothing is launched
-// for a mask with bits above 8 or a kd that is not finite or has fx, fy <= 0.  Uploads the cameras' free columns.
-static int selfcal_args(mocap_ctx* c, int C, int N, int n_obs, const int32_t* obs_offset, const int32_t* obs_cam, const double* obs_uv,
-                        double* kd, const int32_t* refine_mask_host, double* poses, double* points, hipStream_t s, SelfcalArgs& a)
-{
-    if (C < 2 || C > 32 || N < 1 || N > (1 << 24) || n_obs < 2 * (long long)N || n_obs > (long long)N * C)
-        return fail(MOCAP_E_INVALID, "C=%d N=%d n_obs=%d: 2..32 cameras, 1..2^24 points, 2..C observations per point", C, N, n_obs);
-    int32_t free_cols[32];
-    for (int k = 0; k < C; k++) {
-        if (refine_mask_host[k] < 0 || refine_mask_host[k] > 0x1ff)
-            return fail(MOCAP_E_INVALID, "refine_mask[%d] = 0x%x: bits 0..8 (fx, fy, cx, cy, k1, k2, p1, p2, k3)", k, (unsigned)refine_mask_host[k]);
-        free_cols[k] = refine_mask_host[k] | (k > 0 ? 0x3f << 9 : 0);
-    }
-    double kd_host[32 * 9];
-    HIP_TRY(hipMemcpyAsync(kd_host, kd, 8 * 9 * (size_t)C, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    for (int k = 0; k < 9 * C; k++)
-        if (!(fabs(kd_host[k]) <= 1.7976931348623157e308) || (k % 9 < 2 && !(kd_host[k] > 0.0)))
-            return fail(MOCAP_E_INVALID, "kd[%d][%d] = %g: every entry finite, fx and fy > 0", k / 9, k % 9, kd_host[k]);
-    a = SelfcalArgs{};
-    a.obs_offset = obs_offset; a.obs_cam = obs_cam; a.obs_uv = obs_uv; a.C = C; a.N = N; a.n_obs = n_obs;
-    a.n_pairs = C * (C + 1) / 2; a.n_lin_blocks = selfcal_lin_blocks(N);
-    a.schur_chunk = selfcal_schur_chunk(N); a.n_chunks = (N + a.schur_chunk - 1) / a.schur_chunk;
-    a.kd_io = kd; a.poses_io = poses; a.points_io = points;
-    const size_t D = SELFCAL_P * (size_t)C;
-    int32_t* d_free;
-    auto carve = [&](char* base) {
-        Carver k{base};
-        k.take(a.state, 1); k.take(a.cam_count, C); // cleared as one span up to d_free
-        k.take(d_free, C);
-        k.take(a.kd, 2 * 9 * (size_t)C); k.take(a.poses, 2 * 12 * (size_t)C); k.take(a.points, 2 * 3 * (size_t)N); k.take(a.mask, N);
-        k.take(a.W, 3 * SELFCAL_P * (size_t)n_obs); k.take(a.Vinv, 6 * (size_t)N); k.take(a.vdiag, 3 * (size_t)N); k.take(a.gp, 3 * (size_t)N);
-        k.take(a.lin_part, SELFCAL_U * (size_t)a.n_lin_blocks * C); k.take(a.cost_part, a.n_lin_blocks);
-        k.take(a.schur_part, SELFCAL_BLK * (size_t)a.n_chunks * a.n_pairs);
-        k.take(a.S, D * D); k.take(a.rhs, D); k.take(a.gc, D); k.take(a.udiag, D); k.take(a.chol, D * (D + 1) / 2); k.take(a.delta_c, D);
-        k.take(a.upd_part, 3 * (size_t)a.n_lin_blocks); k.take(a.scalars, RIG_N_SCALARS);
-        return k.used;
-    };
-    const size_t need = carve(nullptr);
-    if (need > c->rig_scratch.n) TRY(c->rig_scratch.reserve(need * 2));
-    carve(c->rig_scratch);
-    a.free_cols = d_free;
-    // pageable host memory: the copy has left `free_cols` when this returns
-    HIP_TRY(hipMemcpyAsync(d_free, free_cols, sizeof(int32_t) * C, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync(a.state, 0, (char*)d_free - (char*)a.state, s));
-    return 0;
+    RigArgs a;
+    TRY(pose_args(c, C, N, n_obs, obs_offset, obs_cam, obs_uv, poses, points, s, a));
+    return rig_adjust(rig_pose_solver(), a, max_iters, ftol, lambda0, history, result, loss, loss_scale, obs_err, obs_weight, s);
 }
 
 int mocap_rig_linearize_intrinsics(mocap_ctx_t c, int C, int N, int n_obs, const int32_t* obs_offset, const int32_t* obs_cam,
@@ -225,24 +232,10 @@ int mocap_rig_linearize_intrinsics(mocap_ctx_t c, int C, int N, int n_obs, const
     if (set_device(c)) return MOCAP_E_HIP;
     std::lock_guard<std::mutex> lk(c->mu);
     hipStream_t s = (hipStream_t)stream;
-    SelfcalArgs a;
-    // (the state handed in is only read: the init kernel copies it, no finish kernel runs)
-    TRY(selfcal_args(c, C, N, n_obs, obs_offset, obs_cam, obs_uv, const_cast<double*>(kd), refine_mask_host, const_cast<double*>(poses),
-                     const_cast<double*>(points), s, a));
-    a.loss = loss; a.loss_c2 = loss_scale * loss_scale;
-    const size_t D = SELFCAL_P * (size_t)C;
-    launch_selfcal_init(a, lambda, s);
-    launch_selfcal_linearize(a, s);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(cost, a.scalars + RIG_LIN_COST, 8, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipMemcpyAsync(gradient, a.gc, 8 * D, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipMemcpyAsync(gradient + D, a.gp, 8 * 3 * (size_t)N, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipMemcpyAsync(S, a.S, 8 * D * D, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipMemcpyAsync(rhs, a.rhs, 8 * D, hipMemcpyDeviceToDevice, s));
-    // status: (layout error, a point not in front of a camera that sees it)
-    HIP_TRY(hipMemcpyAsync(status, &a.state->layout_err, 4, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipMemcpyAsync(status + 1, &a.state->behind, 4, hipMemcpyDeviceToDevice, s));
-    return MOCAP_OK;
+    RigArgs a;
+    TRY(lens_args(c, C, N, n_obs, obs_offset, obs_cam, obs_uv, const_cast<double*>(kd), refine_mask_host, const_cast<double*>(poses),
+                  const_cast<double*>(points), s, a));
+    return rig_linearize(rig_lens_solver(), a, lambda, loss, loss_scale, cost, gradient, S, rhs, status, s);
 }
 
 int mocap_rig_bundle_adjust_intrinsics(mocap_ctx_t c, int C, int N, int n_obs, const int32_t* obs_offset, const int32_t* obs_cam,
@@ -258,20 +251,9 @@ int mocap_rig_bundle_adjust_intrinsics(mocap_ctx_t c, int C, int N, int n_obs, c
     if (set_device(c)) return MOCAP_E_HIP;
     std::lock_guard<std::mutex> lk(c->mu);
     hipStream_t s = (hipStream_t)stream;
-    SelfcalArgs a;
-    TRY(selfcal_args(c, C, N, n_obs, obs_offset, obs_cam, obs_uv, kd, refine_mask_host, poses, points, s, a));
-    a.history = history; a.result = result;
-    a.loss = loss; a.loss_c2 = loss_scale * loss_scale; a.obs_err = obs_err; a.obs_weight = obs_weight;
-    HIP_TRY(hipMemsetAsync(history, 0, 8 * 4 * (size_t)max_iters, s));
-    if (obs_err) HIP_TRY(hipMemsetAsync(obs_err, 0, 8 * (size_t)n_obs, s));
-    if (obs_weight) HIP_TRY(hipMemsetAsync(obs_weight, 0, 8 * (size_t)n_obs, s));
-    launch_selfcal_init(a, lambda0, s);
-    // every iteration is enqueued; the kernels of an iteration after the stop return at once (DESIGN.md section 4.6)
-    for (int it = 0; it < max_iters; it++) launch_selfcal_iteration(a, it, max_iters, ftol, s);
-    launch_selfcal_finish(a, s);
-    if (obs_err || obs_weight) launch_selfcal_residuals(a, s);
-    HIP_TRY(hipGetLastError());
-    return MOCAP_OK;
+    RigArgs a;
+    TRY(lens_args(c, C, N, n_obs, obs_offset, obs_cam, obs_uv, kd, refine_mask_host, poses, points, s, a));
+    return rig_adjust(rig_lens_solver(), a, max_iters, ftol, lambda0, history, result, loss, loss_scale, obs_err, obs_weight, s);
 }
 
 // The scratch of an intrinsic calibration, carved out of one block the context owns (grown to twice what a call needs); the

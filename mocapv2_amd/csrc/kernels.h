@@ -468,38 +468,50 @@ struct LmState {
     int32_t chol_fail, chol_fail_prev, behind, trial_behind;
 };
 
-// bundle adjustment of a rig (rig_ba.hip): one loop per call
+// bundle adjustment of a rig: one loop per call.  Two solvers share this record and every phase but one (rig_lm.h): the plain
+// one moves the poses of cameras 1..C-1 (rig_ba.hip: camera blocks 6 wide, camera 0 has none), the other also every camera's
+// lens (rig_selfcal.hip: blocks 15 wide -- kd's 9, then the pose's 6 -- for every camera, camera 0 included).  Below, P is the
+// block's width, FIRST the first camera that has a block, D = P (C - FIRST) the rows of the reduced system.
 struct RigState : LmState {
     double t1_norm;            // |t_1| handed in: the gauge restored on return
     int32_t layout_err, pad;
 };
 enum { RIG_LIN_COST = 0, RIG_PRED_CAM = 1, RIG_NORM2_CAM = 2, RIG_N_SCALARS = 4 }; // (PRED_CAM, NORM2_CAM: lm_decide's `cam` pair)
 enum { RIG_STOP_MAX_ITERS = 1, RIG_STOP_FTOL = 2, RIG_STOP_LAMBDA = 3, RIG_STOP_CHOLESKY = 4, RIG_ERR_LAYOUT = -2, RIG_ERR_BEHIND = -3 };
+constexpr int PT_THREADS = 256; // points per workgroup of the point-owning kernels (linearize, update, residuals): n_lin_blocks = ceil(N / PT_THREADS)
 
 struct RigArgs {
-    const CameraTable* cams;   // K and dist of cameras 0..C-1, by true camera number
     const int32_t* obs_offset; // [N + 1] point n owns observations obs_offset[n] .. obs_offset[n + 1] - 1
     const int32_t* obs_cam;    // [n_obs] ascending within a point
     const double* obs_uv;      // [n_obs][2]
     int C, N, n_obs;
-    int n_pairs, n_lin_blocks, n_chunks; // (C - 1) C / 2 pairs of free cameras; workgroups of the point kernels; of the Schur kernel
+    int n_pairs, n_lin_blocks, n_chunks; // pairs a <= b of cameras that have a block; workgroups of the point kernels; chunks of the Schur kernel
     int loss;                  // LOSS_* of lm.h: which instantiation of the point kernels the launchers pick
     double loss_c2;            // the loss's squared scale c^2 in px^2 (unused by LOSS_NONE)
     double* poses_io;          // [C][12] the caller's: R row-major, then t
     double* points_io;         // [N][3] the caller's
+    // the cameras' lenses.  Used by the pose block alone (null otherwise): constant, from the context's table
+    const CameraTable* cams;   // K and dist of cameras 0..C-1, by true camera number
+    // used by the lens block alone (null / 0 otherwise): the first the caller's, the rest scratch of the context
+    double* kd_io;             // [C][9] the caller's: fx, fy, cx, cy, k1, k2, p1, p2, k3
+    double* kd;                // [2][C][9] current and trial state (state->cur)
+    const int32_t* free_cols;  // [C] device copy: bit i = column i of the camera's block is free (bits 0..8 the caller's mask,
+                               //   bits 9..14 the pose: set for cameras 1.., clear for camera 0)
+    int32_t* cam_count;        // [C] observations of every camera (zeroed before the init kernel)
+    int schur_chunk;           // points of a chunk of its Schur kernel: n_chunks = ceil(N / schur_chunk)
     // scratch of the context
     RigState* state;
     double* poses;             // [2][C][12] current and trial state (state->cur)
     double* points;            // [2][N][3]
     uint32_t* mask;            // [N] bit c: camera c sees the point
-    double* W;                 // [n_obs][18] W_nc, 6x3 row-major (unused for camera 0)
+    double* W;                 // [n_obs][3 P] W_nc, P x 3 row-major (unused for a camera below FIRST)
     double* Vinv;              // [N][6] damped V^-1, upper triangle
     double* vdiag;             // [N][3] diagonal of the undamped V
     double* gp;                // [N][3] g_n
-    double* lin_part;          // [n_lin_blocks][C - 1][27] per-workgroup U_c (21) and g_c (6)
+    double* lin_part;          // [n_lin_blocks][C - FIRST][P (P + 1) / 2 + P] per-workgroup U_c (upper triangle) and g_c
     double* cost_part;         // [n_lin_blocks]
-    double* schur_part;        // [n_chunks][n_pairs][42]
-    double* S;                 // [D][D], D = 6 (C - 1): the damped reduced camera matrix
+    double* schur_part;        // [n_chunks][n_pairs][P P + P] W_a V*^-1 W_b^T, then W_a V*^-1 g_n
+    double* S;                 // [D][D] the damped reduced camera matrix; a fixed column's diagonal entry is 1
     double* rhs;               // [D] reduced right-hand side
     double* gc;                // [D] camera gradient
     double* udiag;             // [D] diagonal of the undamped U
@@ -513,67 +525,19 @@ struct RigArgs {
     double* obs_weight;        // [n_obs] the caller's or null: the loss's weight there (1 for LOSS_NONE)
 };
 
-void launch_rig_init(const RigArgs& a, double lambda0, hipStream_t s);
-void launch_rig_linearize(const RigArgs& a, hipStream_t s);
-void launch_rig_iteration(const RigArgs& a, int it, int max_iters, double ftol, hipStream_t s);
-void launch_rig_finish(const RigArgs& a, hipStream_t s);
-void launch_rig_residuals(const RigArgs& a, hipStream_t s); // behind launch_rig_finish: obs_err, obs_weight
-int rig_lin_blocks(int N);
-int rig_schur_chunks(int N);
-
-// bundle adjustment of a rig that also refines every camera's lens (rig_selfcal.hip): RigArgs' problem with camera blocks 15 wide
-// (kd's 9, then the pose's 6) for every camera, camera 0 included; D = 15 C.  The state record and the scalars are rig_ba.hip's.
-constexpr int SELFCAL_P = 15;                      // a camera block
-constexpr int SELFCAL_U = 120 + SELFCAL_P;         // a camera's sums of the point kernel: the upper triangle of U_c, then g_c
-constexpr int SELFCAL_BLK = SELFCAL_P * SELFCAL_P + SELFCAL_P; // a pair's sums of the Schur kernel: W_a V*^-1 W_b^T, then W_a V*^-1 g_n
-struct SelfcalArgs {
-    const int32_t* obs_offset; // [N + 1], [n_obs], [n_obs][2]: as RigArgs
-    const int32_t* obs_cam;
-    const double* obs_uv;
-    int C, N, n_obs;
-    int n_pairs, n_lin_blocks, n_chunks; // C (C + 1) / 2 pairs of cameras; workgroups of the point kernels; chunks of the Schur kernel
-    int schur_chunk;           // points of a chunk (selfcal_schur_chunk(N)): n_chunks = ceil(N / schur_chunk)
-    int loss;
-    double loss_c2;
-    double* kd_io;             // [C][9] the caller's: fx, fy, cx, cy, k1, k2, p1, p2, k3
-    double* poses_io;          // [C][12] the caller's
-    double* points_io;         // [N][3] the caller's
-    // scratch of the context
-    const int32_t* free_cols;  // [C] device copy: bit i = column i of the camera's block is free (bits 0..8 the caller's mask,
-                               //   bits 9..14 the pose: set for cameras 1.., clear for camera 0)
-    int32_t* cam_count;        // [C] observations of every camera (zeroed before the init kernel)
-    RigState* state;
-    double* kd;                // [2][C][9] current and trial state (state->cur)
-    double* poses;             // [2][C][12]
-    double* points;            // [2][N][3]
-    uint32_t* mask;            // [N] bit c: camera c sees the point
-    double* W;                 // [n_obs][45] W_nc, 15x3 row-major
-    double* Vinv;              // [N][6]
-    double* vdiag;             // [N][3]
-    double* gp;                // [N][3]
-    double* lin_part;          // [n_lin_blocks][C][SELFCAL_U]
-    double* cost_part;         // [n_lin_blocks]
-    double* schur_part;        // [n_chunks][n_pairs][SELFCAL_BLK]
-    double* S;                 // [D][D] the damped reduced camera matrix; a fixed column's diagonal entry is 1
-    double* rhs;               // [D]
-    double* gc;                // [D]
-    double* udiag;             // [D]
-    double* chol;              // [D (D + 1) / 2] the factor when it does not fit LDS
-    double* delta_c;           // [D]
-    double* upd_part;          // [n_lin_blocks][3]
-    double* scalars;           // [RIG_N_SCALARS]
-    double* history;           // [max_iters][4] the caller's (or null for a linearisation alone)
-    double* result;            // [4] the caller's
-    double* obs_err;           // [n_obs] the caller's or null
-    double* obs_weight;        // [n_obs] the caller's or null
+// What the host needs of a solver: its block's figures, the points of a chunk of its Schur kernel for N points, and its launches
+// (rig_lm.h's, instantiated for its block; residuals goes behind finish: obs_err, obs_weight).
+struct RigSolver {
+    int P, FIRST;
+    int (*schur_chunk)(int N);
+    void (*init)(const RigArgs& a, double lambda0, hipStream_t s);
+    void (*linearize)(const RigArgs& a, hipStream_t s);
+    void (*iteration)(const RigArgs& a, int it, int max_iters, double ftol, hipStream_t s);
+    void (*finish)(const RigArgs& a, hipStream_t s);
+    void (*residuals)(const RigArgs& a, hipStream_t s);
 };
-void launch_selfcal_init(const SelfcalArgs& a, double lambda0, hipStream_t s);
-void launch_selfcal_linearize(const SelfcalArgs& a, hipStream_t s);
-void launch_selfcal_iteration(const SelfcalArgs& a, int it, int max_iters, double ftol, hipStream_t s);
-void launch_selfcal_finish(const SelfcalArgs& a, hipStream_t s);
-void launch_selfcal_residuals(const SelfcalArgs& a, hipStream_t s); // behind launch_selfcal_finish: obs_err, obs_weight
-int selfcal_lin_blocks(int N);
-int selfcal_schur_chunk(int N);
+RigSolver rig_pose_solver(); // rig_ba.hip
+RigSolver rig_lens_solver(); // rig_selfcal.hip
 
 // intrinsic calibration of every camera of a rig from planar-board views (intrinsics.hip): one loop, and one state record, per
 // camera; no kernel reads another camera's.  status: RIG_STOP_* / INTR_ERR_*

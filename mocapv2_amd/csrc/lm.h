@@ -1,4 +1,4 @@
-// lm.h -- what the Levenberg-Marquardt solvers (rig_ba.hip, rig_selfcal.hip, intrinsics.hip) share, each defined once: the camera
+// lm.h -- what the Levenberg-Marquardt solvers (the two rig solvers through rig_lm.h, intrinsics.hip) share, each defined once: the camera
 // model with its derivatives, the step-control rule over the state record LmState of kernels.h (both: DESIGN.md section 2,
 // restated by tests/lm_ref.py), the small index helpers of their packed triangles, and the rig solvers' dense algebra (the
 // inverse of a point's 3x3, the packed Cholesky of the reduced camera matrix).
@@ -108,7 +108,7 @@ __device__ __forceinline__ double sym3(const double v[6], int i, int j)
     return v[a == 0 ? b : (a == 1 ? 2 + b : 5)];
 }
 
-// The reduced camera system of the rig solvers (rig_ba.hip, rig_selfcal.hip), by one workgroup of 256 threads.
+// The reduced camera system of the rig solvers (rig_lm.h), by one workgroup of 256 threads.
 // In-place Cholesky S = L L^T on the packed lower triangle (right-looking); false when a pivot is not positive
 __device__ __forceinline__ bool cholesky_packed(double* L, int D)
 {

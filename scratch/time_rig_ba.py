@@ -4,10 +4,12 @@ measurement, numbers in DESIGN.md section 5 and profiles/README.md).  The proble
 with device events after a warm-up, for max_iters = 50 (the default: every iteration is enqueued, those after the stop return
 at once) and for max_iters = the iterations the loop actually needs, which prices the enqueue-everything design against a
 host that would stop launching, and for max_iters = 1 (one iteration with its init and finish launches).  --loss-scale C times
-mocap_rig_bundle_adjust_robust with the Cauchy loss of scale C px and both per-observation outputs in its place.  Also prints
-the NumPy restatement's CPU time for the same problem (--numpy, the plain loop).
+mocap_rig_bundle_adjust_robust with the Cauchy loss of scale C px and both per-observation outputs in its place.
+--intrinsics times mocap_rig_bundle_adjust_intrinsics on the same problem and start: the context's K and dist as kd, every
+lens parameter of every camera free (mask 0x1ff), the loss of --loss-scale or none.  Also prints the NumPy restatement's CPU
+time for the same problem (--numpy, the plain loop).
 
-  python scratch/time_rig_ba.py [--points 20000] [--reps 5] [--loss-scale 2.0] [--numpy]
+  python scratch/time_rig_ba.py [--points 20000] [--reps 5] [--loss-scale 2.0] [--intrinsics] [--numpy]
   rocprofv3 --kernel-trace --stats -d DIR -- python scratch/time_rig_ba.py --reps 2     (kernel split, a run of its own)
 """
 import argparse
@@ -29,6 +31,7 @@ def main():
     ap.add_argument("--points", type=int, default=20000)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--loss-scale", type=float, default=None)
+    ap.add_argument("--intrinsics", action="store_true")
     ap.add_argument("--numpy", action="store_true")
     args = ap.parse_args()
     import torch
@@ -48,15 +51,23 @@ def main():
     stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
     per_obs = torch.zeros((2, len(cam)), dtype=torch.float64, device=dev)
+    kd = np.c_[prob.K[:, 0, 0], prob.K[:, 1, 1], prob.K[:, 0, 2], prob.K[:, 1, 2], prob.dist]
+    masks = np.full(prob.C, 0x1FF, np.int32)
 
     def call(max_iters):
-        d_poses, d_pts = torch.from_numpy(poses).to(dev), torch.from_numpy(X).to(dev)
+        d_poses, d_pts, d_kd = torch.from_numpy(poses).to(dev), torch.from_numpy(X).to(dev), torch.from_numpy(kd).to(dev)
         hist = torch.zeros((max_iters, 4), dtype=torch.float64, device=dev)
         res = torch.zeros(4, dtype=torch.float64, device=dev)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         torch.cuda.synchronize()
         e0.record()
-        if args.loss_scale is None:
+        if args.intrinsics:
+            robust = args.loss_scale is not None
+            rc = ctx.lib.mocap_rig_bundle_adjust_intrinsics(ctx._h, prob.C, prob.N, len(cam), p(d_off), p(d_cam), p(d_uv), p(d_kd),
+                                                            masks.ctypes.data_as(C.POINTER(C.c_int)), p(d_poses), p(d_pts), max_iters, 1e-12,
+                                                            1e-3, p(hist), p(res), int(robust), args.loss_scale or 0.0,
+                                                            p(per_obs[0]) if robust else None, p(per_obs[1]) if robust else None, stream)
+        elif args.loss_scale is None:
             rc = ctx.lib.mocap_rig_bundle_adjust(ctx._h, prob.C, prob.N, len(cam), p(d_off), p(d_cam), p(d_uv), p(d_poses), p(d_pts),
                                                  max_iters, 1e-12, 1e-3, p(hist), p(res), stream)
         else:
@@ -70,9 +81,9 @@ def main():
 
     _, res = call(50)  # warm-up: code objects, scratch
     iters = int(res[1])
-    out = {"points": prob.N, "observations": len(cam), "cameras": prob.C, "loss_scale": args.loss_scale, "status": int(res[0]),
+    out = {"points": prob.N, "observations": len(cam), "cameras": prob.C, "intrinsics": args.intrinsics, "loss_scale": args.loss_scale, "status": int(res[0]),
            "iterations": iters, "rms_px": float(np.sqrt(res[3] / len(cam)))}
-    for name, mi in (("ms_max_iters_50", 50), ("ms_max_iters_needed", iters), ("ms_max_iters_1", 1)):
+    for name, mi in (("ms_max_iters_50", 50), ("ms_max_iters_needed", max(iters, 1)), ("ms_max_iters_1", 1)):
         ms = [call(mi)[0] for _ in range(args.reps)]
         out[name] = {"median": float(np.median(ms)), "min": float(min(ms)), "max": float(max(ms))}
     if args.numpy:

@@ -267,7 +267,8 @@ def test_without_a_gpu_the_python_surface_fails_loudly():
 
 
 @pytest.mark.parametrize("src, stems", [
-    ("rig_ba.hip", ("rig_init", "rig_linearize", "rig_schur", "rig_reduce", "rig_solve", "rig_update", "rig_decide", "rig_finish")),
+    ("rig_ba.hip", ("rig_init", "rig_linearize", "rig_schur", "rig_reduce", "rig_solve", "rig_update", "rig_decide", "rig_finish",
+                    "rig_residuals")),
     ("intrinsics.hip", ("intr_begin", "intr_homography", "intr_start", "intr_linearize", "intr_solve", "intr_update", "intr_decide",
                         "intr_finish"))], ids=["rig_ba", "intrinsics"])
 def test_new_kernels_use_no_scratch_memory_and_spill_nothing(src, stems):

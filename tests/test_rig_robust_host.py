@@ -240,7 +240,7 @@ def test_every_instantiation_of_the_point_kernels_is_built_without_scratch():
     found = {}
     for stem in ("rig_linearize_kernel", "rig_update_kernel", "rig_residuals_kernel"):
         for loss in (0, 1):
-            hit = [k for name, k in ks.items() if "%sILi%dEE" % (stem, loss) in name]
+            hit = [k for name, k in ks.items() if stem + "I" in name and "ELi%dEE" % loss in name]  # <the camera block, loss>
             assert len(hit) == 1, (stem, loss, sorted(ks))
             print(hit[0])
             assert hit[0]["scratch"] == 0 and hit[0]["spill"] == 0 and hit[0]["agpr"] == 0

@@ -215,12 +215,14 @@ def test_shape_loop_cases_are_far_from_every_decision_boundary(name):
 
 def test_shape_cases_have_the_shapes_they_are_named_for():
     """What each case of SHAPE_CASES is there for, restated from its sizes: the workgroups of the point kernels and the Schur
-    kernel's chunks (PT_THREADS = SCHUR_CHUNK = 256 in csrc/rig_selfcal.hip), the rows of S against the 90 the Cholesky holds in
+    kernel's chunks (PT_THREADS = SCHUR_CHUNK = 256: csrc/kernels.h, csrc/rig_selfcal.hip), the rows of S against the 90 the Cholesky holds in
     LDS and the 480 of the largest rig, and for rig32 a point that all 32 cameras see (bit 31 of a visibility mask, every one of
     the 528 pairs) and observations in camera 31.  Every case passes the layout check."""
     import re
-    with open(os.path.join(ROOT, "mocapv2_amd", "csrc", "rig_selfcal.hip")) as f:
-        source = f.read()
+    source = ""
+    for name in ("rig_selfcal.hip", "rig_lm.h", "kernels.h"):  # the solver's file, the shared phases, the host's record
+        with open(os.path.join(ROOT, "mocapv2_amd", "csrc", name)) as f:
+            source += f.read()
     constants = {k: int(v) for k, v in re.findall(r"constexpr int (PT_THREADS|SCHUR_CHUNK|CHOL_LDS_ROWS) = (\d+);", source)}
     assert constants == {"PT_THREADS": 256, "SCHUR_CHUNK": 256, "CHOL_LDS_ROWS": 90}  # what lin_blocks and schur_chunks restate
     for name, (n_cam, _, n_keep, _, masks, _, _) in sc.SHAPE_CASES.items():
@@ -266,8 +268,9 @@ def test_kernels_use_no_scratch_memory_and_spill_nothing():
     spec.loader.exec_module(km)
     ks = km.kernels_of(os.path.join(km.CSRC, "rig_selfcal.hip"))
     names = " ".join(k["name"] for k in ks)
-    for want in ("init", "check", "linearize", "schur", "reduce", "solve", "update", "decide", "finish", "residuals"):
-        assert f"selfcal_{want}_kernel" in names
+    for want in ("rig_init", "selfcal_check", "rig_linearize", "selfcal_schur", "rig_reduce", "rig_solve", "rig_update", "rig_decide",
+                 "rig_finish", "rig_residuals"):
+        assert f"{want}_kernel" in names
     for k in ks:
         print(k)
         assert k["scratch"] == 0 and k["spill"] == 0 and k["lds"] <= 65536, k
