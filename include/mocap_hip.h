@@ -53,6 +53,9 @@ enum {
     MOCAP_RIGID_E_MODEL = -4,     /* the body's tables are not a model: n_markers outside 3..8, n_tri outside 1..56, or a triple
                                      that is not 0 <= a < b < c < n_markers */
     MOCAP_RIGID_E_HYP = -5,       /* more than max_hyp candidates for the body in the step: it has no result there */
+    MOCAP_REFINE_E_VIEWS = -2,    /* mocap_refine_points, status[t][q]: the row has fewer than 2 member cameras */
+    MOCAP_REFINE_E_INPUT = -3,    /* the row's point is not finite, a member's index lies outside [0, P), or its mask has bits at or above C */
+    MOCAP_REFINE_E_BEHIND = -4,   /* the row's point is not in front of every member camera */
     MOCAP_FUND_E_SAMPLE = -2,     /* mocap_fundamental_ransac: a sample index outside its pair's point list */
     MOCAP_FUND_E_DEGENERATE = -3  /* no valid hypothesis (e.g. coincident points), a winner with fewer than 8 inliers, or
                                      inliers that do not span a model in the refit */
@@ -362,6 +365,53 @@ MOCAP_API int mocap_rigid_poses(mocap_ctx_t ctx, const double* xyz_dev /*[T][Q][
                                 const int32_t* tri_dev /*[B][56][3]*/, const int32_t* n_tri_dev /*[B]*/, double tol, double gate,
                                 int min_markers, int max_hyp, double* R_dev, double* t_dev, double* q_dev, double* rms_dev,
                                 int32_t* n_in_dev, int32_t* label_dev, int32_t* status_dev, void* stream);
+
+/* Refinement of triangulated markers by their reprojection error, with the covariance of the result.  mocap_correspond and
+ * mocap_correspond_visible report the DLT, which minimises an algebraic error that weights every view by its depth; this call
+ * moves every row's point to the minimum of 1/2 sum |pixel(X) - observation|^2 over the row's member cameras by
+ * Levenberg-Marquardt, and reports (J^T J)^-1 there: the point's covariance in world units^2 per px^2 of image noise.  Every
+ * (time step, row) is independent (one lane each) and the call is stateless.  The reference has no counterpart: the contract is
+ * the definition of DESIGN.md section 2, restated by tests/refine_points_ref.py -- FP64 throughout, + - * / only, every operation
+ * rounded on its own, sums in ascending camera order, so the device equals the restatement bit for bit.  New symbol,
+ * MOCAP_ABI_VERSION stays 7.
+ *   xyz_dev     float64 [T][Q][3]  the points to start from (mocap_correspond_visible's xyz_dev, mocap_correspond's root_xyz)
+ *   n_dev       int32 [T]          rows of the step (the correspondence's n / n_roots as it is).  n_dev[t] <= 0: the step has no
+ *                                  rows; above Q: Q rows
+ *   views_dev   uint32 [T][Q]      bit c set: camera c is a member of the row.  NULL (grouped form only): all C cameras are
+ *   Camera c's observation of row (t, q) comes from one of two sources -- exactly one of pts_dev and grp_dev is not NULL:
+ *   indexed     point idx_dev[t][q][c] (int32 [T][Q][C]; read for members only) of camera c's list at time step t; the lists
+ *               are read through pt_stride_t / pt_stride_c / pts_f64 exactly as mocap_correspond_visible reads them (P = points
+ *               a list holds), so centroid records and all-gathered records work in place
+ *   grouped     grp_dev[t][q][c], float64 [T][Q][C][2]: mocap_correspond's root_grp as it is
+ *   distorted   0: the observations are ideal pinhole pixels (pixels of undistorted images), the model is fx x + cx exactly;
+ *               1: they are pixels of the raw frames and the residual is taken there, through the camera's lens (k1, k2, p1, p2,
+ *               k3 of mocap_set_cameras) -- no undistortion is involved
+ *   max_iters (1..10000), ftol (>= 0), lambda0 (0 < lambda0 <= 1e16): the loop's limits, as mocap_rig_bundle_adjust's; the step
+ *               control (gain ratio, Nielsen's damping, the four stops) is the one the rig solvers use
+ *   max_res2    > 0 turns pruning on: after a loop has stopped, while the row has more than min_views (2..C) members and has
+ *               dropped fewer than max_drop (>= 0), the member with the largest squared residual length r0^2 + r1^2 (px^2; ties:
+ *               the lower camera) is dropped when that length exceeds max_res2, and a new loop starts from the current point
+ *               with lambda0.  <= 0: no pruning
+ * Per row q < n_dev[t]:
+ *   xyz_out_dev float64 [T][Q][3]  the refined point (may be xyz_dev itself)
+ *   err_dev     float64 [T][Q]     mean of the squared residuals over both coordinates of all members left, px^2 (err_dev's
+ *                                  convention in mocap_correspond_visible)
+ *   res2_dev    float64 [T][Q][C]  r0^2 + r1^2 of every member left, -1 for a camera that is none
+ *   cov_dev     float64 [T][Q][6]  (J^T J)^-1 at the refined point, undamped: upper triangle (00, 01, 02, 11, 12, 22)
+ *   views_out_dev, dropped_dev uint32 [T][Q]  the members left, the members dropped
+ *   iters_dev   int32 [T][Q]       iterations of all the row's loops
+ *   status_dev  int32 [T][Q]       MOCAP_RIG_STOP_* (1..4) of the last loop, or MOCAP_REFINE_E_* (< 0): the row was not refined,
+ *                                  xyz_out holds the point handed in, views_out the mask handed in, and the row's other outputs
+ *                                  are unspecified.  Nothing is silent, and the other rows are unaffected
+ * Rows at and beyond n_dev[t] get status 0 and nothing else is written for them.
+ * T = 0 is a no-op.  Bad arguments (C above 32 among them) are MOCAP_E_INVALID and launch nothing.  Requires mocap_set_cameras.
+ * Asynchronous on `stream`.  No atomics: the same call gives the same bits. */
+MOCAP_API int mocap_refine_points(mocap_ctx_t ctx, const double* xyz_dev, const int32_t* n_dev, const uint32_t* views_dev, int T,
+                                  int Q, int C, const void* pts_dev, long pt_stride_t, long pt_stride_c, int pts_f64, int P,
+                                  const int32_t* idx_dev, const double* grp_dev, int distorted, int max_iters, double ftol,
+                                  double lambda0, double max_res2, int min_views, int max_drop, double* xyz_out_dev,
+                                  double* err_dev, double* res2_dev, double* cov_dev, uint32_t* views_out_dev,
+                                  uint32_t* dropped_dev, int32_t* iters_dev, int32_t* status_dev, void* stream);
 
 /* The scoring step of find_point_correspondance_and_object_points on its own (lib/Helpers.py:205-220), for one camera
  * pair: the epipolar line of every root point under Fs[f_index] (cv.computeCorrespondEpilines on the float32 point, :207;

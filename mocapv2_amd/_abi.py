@@ -60,6 +60,8 @@ SIGNATURES = {
     "mocap_correspond": [_vp, _vp, _l, _l, _vp, _l, _l, _i, _i, _i, _i, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "mocap_correspond_visible": [_vp, _vp, _l, _l, _vp, _l, _l, _i, _i, _i, _i, _i, _d, _d, _i, _d, _i, _i, _i, _vp, _vp, _vp, _vp,
                                  _vp, _vp],
+    "mocap_refine_points": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _l, _l, _i, _i, _vp, _vp, _i, _i, _d, _d, _d, _i, _i, _vp, _vp, _vp, _vp,
+                            _vp, _vp, _vp, _vp, _vp],
     "mocap_track_markers": [_vp, _vp, _vp, _i, _i, _vp, _i, _d, _d, _i, _vp, _vp, _vp, _vp, _vp],
     "mocap_rigid_poses": [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _d, _d, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "mocap_epipolar_scores": [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp],

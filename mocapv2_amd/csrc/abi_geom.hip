@@ -84,6 +84,38 @@ int mocap_correspond_visible(mocap_ctx_t c, const void* pts, long pt_st, long pt
     return MOCAP_OK;
 }
 
+int mocap_refine_points(mocap_ctx_t c, const double* xyz, const int32_t* n, const uint32_t* views, int T, int Q, int C, const void* pts,
+                        long pt_st, long pt_sc, int pts_f64, int P, const int32_t* idx, const double* grp, int distorted, int max_iters,
+                        double ftol, double lambda0, double max_res2, int min_views, int max_drop, double* xyz_out, double* err,
+                        double* res2, double* cov, uint32_t* views_out, uint32_t* dropped, int32_t* iters, int32_t* status, void* stream)
+{
+    if (c && T == 0) return MOCAP_OK; // no time step: nothing is read, nothing is launched
+    if (!c || !xyz || !n || !xyz_out || !err || !res2 || !cov || !views_out || !dropped || !iters || !status)
+        return fail(MOCAP_E_INVALID, "null argument");
+    if ((pts != nullptr) == (grp != nullptr)) return fail(MOCAP_E_INVALID, "exactly one of pts_dev (indexed form) and grp_dev (grouped form)");
+    if (pts && (!idx || !views)) return fail(MOCAP_E_INVALID, "the indexed form needs idx_dev and views_dev");
+    if (pts && ((pt_st | pt_sc) & 1)) return fail(MOCAP_E_INVALID, "point strides must be even (whole points)");
+    if (T < 0 || Q < 1 || Q > 65535 || C < 2 || C > 32 || (pts && P < 1))
+        return fail(MOCAP_E_INVALID, "T=%d Q=%d C=%d P=%d (T >= 0, Q: 1..65535, C: 2..32, P >= 1)", T, Q, C, P);
+    if (max_iters < 1 || max_iters > 10000 || !(ftol >= 0.0) || !(lambda0 > 0.0) || !(lambda0 <= 1e16))
+        return fail(MOCAP_E_INVALID, "max_iters=%d ftol=%g lambda0=%g", max_iters, ftol, lambda0);
+    if (!isfinite(max_res2) || min_views < 2 || min_views > C || max_drop < 0 || (distorted != 0 && distorted != 1))
+        return fail(MOCAP_E_INVALID, "max_res2=%g min_views=%d max_drop=%d distorted=%d (max_res2 finite, min_views: 2..C=%d, max_drop >= 0, distorted: 0 / 1)",
+                    max_res2, min_views, max_drop, distorted, C);
+    if (c->n_cam < C) return fail(MOCAP_E_STATE, "mocap_set_cameras: %d cameras set, %d needed", c->n_cam, C);
+    if (set_device(c)) return MOCAP_E_HIP;
+    RefinePointsArgs a;
+    a.cams = c->cams; a.xyz = xyz; a.n = n; a.views = views; a.T = T; a.Q = Q; a.C = C;
+    a.pts = pts; a.pt_st = pt_st; a.pt_sc = pt_sc; a.pts_f64 = pts_f64; a.P = P; a.idx = idx; a.grp = grp;
+    a.distorted = distorted; a.max_iters = max_iters; a.ftol = ftol; a.lambda0 = lambda0; a.max_res2 = max_res2;
+    a.min_views = min_views; a.max_drop = max_drop;
+    a.xyz_out = xyz_out; a.err = err; a.res2 = res2; a.cov = cov; a.views_out = views_out; a.dropped = dropped; a.iters = iters;
+    a.status = status;
+    launch_refine_points(a, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return MOCAP_OK;
+}
+
 int mocap_epipolar_scores(mocap_ctx_t c, const void* roots, int n_roots, const void* cand, int n_cand, int pts_f64, int f_index,
                           double* dist, float* lines, void* stream)
 {

@@ -654,6 +654,38 @@ struct RefineArgs {
 };
 void launch_refine_centroids(const RefineArgs& a, hipStream_t s);
 
+// refinement of triangulated markers by their reprojection error, with covariance (refine_points.hip).  A
+// row's status is a RIG_STOP_* code (refined), 0 (no row) or one of these, include/mocap_hip.h's MOCAP_REFINE_E_*
+enum { REFINE_ERR_VIEWS = -2, REFINE_ERR_INPUT = -3, REFINE_ERR_BEHIND = -4 };
+struct RefinePointsArgs {
+    const CameraTable* cams;   // K, dist, R, t of cameras 0..C-1
+    const double* xyz;         // [T][Q][3] the points handed in (may be xyz_out)
+    const int32_t* n;          // [T] rows of the step; <= 0: none
+    const uint32_t* views;     // [T][Q] bit c: camera c is a member; null (grouped form only) = all C cameras
+    int T, Q, C;
+    // indexed form: the member point of camera c is idx[t][q][c] of the camera's list, read as VisArgs' points are
+    const void* pts;
+    long pt_st, pt_sc;
+    int pts_f64, P;
+    const int32_t* idx;        // [T][Q][C]
+    // grouped form (pts == null)
+    const double* grp;         // [T][Q][C][2]
+    int distorted;             // 1 = the points are raw-frame pixels: the residual goes through the camera's five distortion terms
+    int max_iters;
+    double ftol, lambda0;
+    double max_res2;           // > 0: pruning is on
+    int min_views, max_drop;
+    double* xyz_out;           // [T][Q][3]
+    double* err;               // [T][Q]
+    double* res2;              // [T][Q][C] squared residual length per member, -1 = no member
+    double* cov;               // [T][Q][6] inv_sym3's layout
+    uint32_t* views_out;       // [T][Q]
+    uint32_t* dropped;         // [T][Q]
+    int32_t* iters;            // [T][Q]
+    int32_t* status;           // [T][Q]
+};
+void launch_refine_points(const RefinePointsArgs& a, hipStream_t s);
+
 void launch_fundamental_ransac(const FundArgs& a, hipStream_t s);
 
 enum { LDS_USER_CORRESPOND, LDS_USER_VISIBLE, LDS_USERS };

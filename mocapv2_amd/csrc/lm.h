@@ -94,13 +94,15 @@ __device__ __forceinline__ void pose_columns(const double A[3], const double q[3
     j[3] = A[0]; j[4] = A[1]; j[5] = A[2];
 }
 
-// inverse of the symmetric 3x3 with upper triangle v[6] = (00, 01, 02, 11, 12, 22) by the adjugate; same layout out
-__device__ __forceinline__ void inv_sym3(const double v[6], double o[6])
+// inverse of the symmetric 3x3 with upper triangle v[6] = (00, 01, 02, 11, 12, 22) by the adjugate; same layout out.  Returns
+// the determinant it divided by (refine_points.hip's test of a failed factorisation; the rig solvers do not look at it)
+__device__ __forceinline__ double inv_sym3(const double v[6], double o[6])
 {
     const double c00 = v[3] * v[5] - v[4] * v[4], c01 = v[2] * v[4] - v[1] * v[5], c02 = v[1] * v[4] - v[2] * v[3];
     const double det = (v[0] * c00 + v[1] * c01) + v[2] * c02;
     const double c11 = v[0] * v[5] - v[2] * v[2], c12 = v[1] * v[2] - v[0] * v[4], c22 = v[0] * v[3] - v[1] * v[1];
     o[0] = c00 / det; o[1] = c01 / det; o[2] = c02 / det; o[3] = c11 / det; o[4] = c12 / det; o[5] = c22 / det;
+    return det;
 }
 __device__ __forceinline__ double sym3(const double v[6], int i, int j)
 {

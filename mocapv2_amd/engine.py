@@ -421,6 +421,82 @@ class MocapContext:
                               rec_ints * stride_c, points is not None, T, Cn, P, distorted, cutoff, gate, min_views, max_err, max_passes,
                               max_hyp, Q, out)
 
+    def _refine_out(self, T, Q, Cn):
+        dev = self.device
+        out = {"xyz": torch.zeros((T, Q, 3), dtype=torch.float64, device=dev), "err": torch.zeros((T, Q), dtype=torch.float64, device=dev),
+               "res2": torch.zeros((T, Q, Cn), dtype=torch.float64, device=dev), "cov": torch.zeros((T, Q, 6), dtype=torch.float64, device=dev)}
+        for k in ("views", "dropped", "iters", "status"):  # views, dropped: the uint32 masks' bits (bit 31 = the sign)
+            out[k] = torch.zeros((T, Q), dtype=torch.int32, device=dev)
+        return out
+
+    def _refine_call(self, xyz, n, views, Cn, pts, P, idx, grp, distorted, max_iters, ftol, lambda0, max_res2, min_views, max_drop, out):
+        assert xyz.is_cuda and xyz.is_contiguous() and xyz.dtype == torch.float64 and xyz.dim() == 3 and xyz.shape[2] == 3, xyz.shape
+        assert n.is_cuda and n.is_contiguous() and n.dtype == torch.int32
+        T, Q = int(xyz.shape[0]), int(xyz.shape[1])
+        assert n.numel() >= T, (n.shape, T)
+        if int(max_drop) > 0 and max_res2 is None:
+            raise ValueError("max_drop > 0 asks for pruning: max_res2 (px^2) has no default, it is the capture's noise")
+        if views is not None:
+            assert views.is_cuda and views.is_contiguous() and views.dtype == torch.int32 and views.shape == (T, Q), views.shape
+        out = out or self._refine_out(T, Q, Cn)
+        shapes = {"xyz": (T, Q, 3), "err": (T, Q), "res2": (T, Q, Cn), "cov": (T, Q, 6), "views": (T, Q), "dropped": (T, Q), "iters": (T, Q),
+                  "status": (T, Q)}
+        assert all(out[k].shape == s and out[k].is_contiguous() for k, s in shapes.items()), {k: out[k].shape for k in shapes}
+        pts_ptr, pt_st, pt_sc, f64 = pts if pts is not None else (None, 0, 0, 1)
+        _abi.check(self.lib.mocap_refine_points(self._h, _ptr(xyz), _ptr(n), _ptr(views), T, Q, Cn, pts_ptr, pt_st, pt_sc, int(f64), int(P),
+                                                _ptr(idx), _ptr(grp), int(bool(distorted)), int(max_iters), float(ftol), float(lambda0),
+                                                0.0 if max_res2 is None else float(max_res2), int(min_views), int(max_drop),
+                                                _ptr(out["xyz"]), _ptr(out["err"]), _ptr(out["res2"]), _ptr(out["cov"]), _ptr(out["views"]),
+                                                _ptr(out["dropped"]), _ptr(out["iters"]), _ptr(out["status"]), _stream()))
+        return out
+
+    def refine_points(self, xyz, n, views=None, pts=None, idx=None, grp=None, distorted=False, max_iters=10, ftol=1e-9, lambda0=1e-3,
+                      max_res2=None, min_views=2, max_drop=0, out=None):
+        """Triangulated markers moved to the minimum of their reprojection error, with the covariance there (mocap_refine_points;
+        the definition is DESIGN.md section 2).  xyz [T, Q, 3] float64 and n [T] int32 on the GPU: the points to start from and
+        the rows of every step (a count <= 0: none), as the correspondence calls deliver them.  The observations come
+          indexed:  pts [T, C, P, 2] (int32 or float64), idx [T, Q, C] int32, views [T, Q] int32 (bit c = camera c is a member)
+                    -- correspond_visible's inputs and outputs as they are; or
+          grouped:  grp [T, Q, C, 2] float64 -- correspond's grp as it is; views may be None (every camera is a member).
+        distorted: the observations are raw-frame pixels and the residual goes through the cameras' lenses (False: ideal
+        pixels, an exact pinhole).  max_drop > 0 turns pruning on and needs max_res2 (px^2, no default: it is the capture's
+        noise): after a loop, the member with the largest squared residual is dropped when that exceeds max_res2 and more than
+        min_views members are left.  Returns a dict of device tensors: xyz [T, Q, 3] (out["xyz"] may be the input), err [T, Q]
+        (px^2), res2 [T, Q, C] (-1 = no member), cov [T, Q, 6] (upper triangle 00, 01, 02, 11, 12, 22; world units^2 per px^2),
+        views, dropped, iters, status [T, Q] int32 (status: RIG_STOP_* 1..4, 0 = no row, MOCAP_REFINE_E_* < 0 = not refined:
+        xyz and views are the input's, the rest of the row must not be read)."""
+        if (pts is None) == (grp is None):
+            raise ValueError("refine_points: either pts with idx and views (indexed form) or grp (grouped form)")
+        if grp is not None:
+            assert grp.is_cuda and grp.is_contiguous() and grp.dtype == torch.float64 and grp.dim() == 4 and grp.shape[3] == 2, grp.shape
+            assert tuple(grp.shape[:2]) == tuple(xyz.shape[:2]), (grp.shape, xyz.shape)
+            return self._refine_call(xyz, n, views, int(grp.shape[2]), None, 0, None, grp, distorted, max_iters, ftol, lambda0, max_res2,
+                                     min_views, max_drop, out)
+        if idx is None or views is None:
+            raise ValueError("refine_points: the indexed form needs idx and views")
+        assert pts.is_cuda and pts.is_contiguous() and pts.dim() == 4 and pts.shape[3] == 2 and pts.shape[0] == xyz.shape[0], pts.shape
+        f64 = pts.dtype == torch.float64
+        assert f64 or pts.dtype == torch.int32
+        Cn, P = int(pts.shape[1]), int(pts.shape[2])
+        assert idx.is_cuda and idx.is_contiguous() and idx.dtype == torch.int32 and idx.shape == tuple(xyz.shape[:2]) + (Cn,), idx.shape
+        return self._refine_call(xyz, n, views, Cn, (_ptr(pts), Cn * P * 2, P * 2, f64), P, idx, None, distorted, max_iters, ftol, lambda0,
+                                 max_res2, min_views, max_drop, out)
+
+    def refine_points_records(self, xyz, n, views, idx, records, Cn, t0=0, stride_t=None, stride_c=None, P=None, points=None,
+                              distorted=False, max_iters=10, ftol=1e-9, lambda0=1e-3, max_res2=None, min_views=2, max_drop=0, out=None):
+        """refine_points' indexed form straight from centroid records, laid out and read as correspond_visible_records reads
+        them (`points` included)."""
+        rec_ints = records.shape[-1]
+        flat = records.reshape(-1, rec_ints)
+        stride_t = Cn if stride_t is None else stride_t
+        stride_c = 1 if stride_c is None else stride_c
+        P = P or min(255, (rec_ints - 2) // 2)
+        base = flat.data_ptr() + 4 * rec_ints * stride_t * t0
+        pts = (C.c_void_p(base + 8), rec_ints * stride_t, rec_ints * stride_c, False) if points is None else \
+            self._record_points(points, records, P, stride_t, stride_c, t0) + (True,)
+        assert idx.is_cuda and idx.is_contiguous() and idx.dtype == torch.int32 and idx.shape == tuple(xyz.shape[:2]) + (Cn,), idx.shape
+        return self._refine_call(xyz, n, views, Cn, pts, P, idx, None, distorted, max_iters, ftol, lambda0, max_res2, min_views, max_drop, out)
+
     def track_state(self, max_tracks):
         """The state buffer of one tracker for track_markers (MOCAP_TRACK_STATE_BYTES: a 64-byte header and one 64-byte record per
         slot, include/mocap_hip.h), zeroed = the empty tracker.  The caller owns it; NumPy reads a copy of it with a structured dtype."""

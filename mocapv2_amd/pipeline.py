@@ -187,7 +187,7 @@ class BatchTracker:
     def __init__(self, K, dist, R, t, F, width, height, steps_per_rank, world=1, rank=0, device=0, group=None,
                  max_points=32, max_groups=4096, depth=1, bayer_pattern=None, gray_shift=GRAY_SHIFT, collective="auto",
                  force_collective=False, visibility="all", min_views=2, gate=10.0, max_err=25.0, max_passes=3, cutoff=10.0,
-                 max_hyp=8192, track=None, subpixel=None, bodies=None):
+                 max_hyp=8192, track=None, subpixel=None, bodies=None, refine=None):
         """visibility: which markers stage B reports --
              "all"   the reference's find_point_correspondance_and_object_points (mocap_correspond): a marker every camera sees,
                      searched from camera 0's points; the outputs are MocapContext.correspond's;
@@ -220,7 +220,26 @@ class BatchTracker:
              gain body_R [T, B, 9], body_t [T, B, 3], body_q [T, B, 4] (w, x, y, z), body_rms [T, B], body_n [T, B], body_label
              [T, B, 8] and body_status [T, B].  The labels are rows of xyz with visibility="any"; with "all" they are positions in
              `order`, as `track`'s rows are.  Stateless per time step: works with world > 1 and any depth, next to `track` or
-             without it.  None is the path as it was: no launch, no key."""
+             without it.  None is the path as it was: no launch, no key.
+           refine: None, or {"max_iters": 10, "ftol": 1e-9, "lambda0": 1e-3, "max_res2": px^2, "max_drop": 0} -- the markers moved
+             to the minimum of their reprojection error, with their covariance (MocapContext.refine_points, DESIGN.md section
+             2), right behind the correspondence on the same stream: from the image points it read (the sub-pixel ones with
+             `subpixel`) and the members it found with visibility="any" (pruning keeps at least min_views of them), from `grp`
+             with "all".  max_drop > 0 turns pruning on and needs max_res2 (no default: it is the capture's noise).  xyz, err and
+             idx stay what they were; the outputs gain xyz_refined [T, rows, 3], err_refined [T, rows], res2 [T, rows, C], cov
+             [T, rows, 6], views_refined, refine_dropped, refine_iters, refine_status [T, rows], row for row beside xyz.  `track` and
+             `bodies` then read xyz_refined.  Stateless per time step: works with world > 1 and any depth.  None is the path as
+             it was: no launch, no key."""
+        self.refine = None
+        if refine is not None:
+            unknown = set(refine) - {"max_iters", "ftol", "lambda0", "max_res2", "max_drop"}
+            if unknown:
+                raise ValueError(f"refine: a dict with max_iters, ftol, lambda0, max_res2, max_drop; got {sorted(refine)}")
+            self.refine = {"max_iters": int(refine.get("max_iters", 10)), "ftol": float(refine.get("ftol", 1e-9)),
+                           "lambda0": float(refine.get("lambda0", 1e-3)), "max_drop": int(refine.get("max_drop", 0)),
+                           "max_res2": None if refine.get("max_res2") is None else float(refine["max_res2"])}
+            if self.refine["max_drop"] > 0 and self.refine["max_res2"] is None:
+                raise ValueError("refine: max_drop > 0 asks for pruning, which needs max_res2 (px^2; no default: it is the capture's noise)")
         self.bodies = None
         if bodies is not None:
             known = {"models", "tol", "gate", "min_markers", "max_hyp", "min_area", "names"}
@@ -403,10 +422,29 @@ class BatchTracker:
             self.out["subpix_flags"] = self._cur.subpix["flags"]
         return self.out
 
+    REFINE_KEYS = {"xyz": "xyz_refined", "err": "err_refined", "res2": "res2", "cov": "cov", "views": "views_refined",
+                   "dropped": "refine_dropped", "iters": "refine_iters", "status": "refine_status"}
+
+    def refine_markers(self, out, gathered):
+        """The refinement of a batch's markers (the tracker was built with `refine`), from what `triangulate` read and wrote: adds
+        the REFINE_KEYS tensors to `out`."""
+        ctx = self._cur.ctx
+        prev = {k: out[v] for k, v in self.REFINE_KEYS.items()} if "xyz_refined" in out else None
+        if self.visibility == "any":
+            t0, st, sc = (0, self.n_cam, 1) if self.world == 1 else (self.rank * self.T, 1, self.t_total)
+            points = self._cur.subpix["xy"] if self.subpixel else None
+            res = ctx.refine_points_records(out["xyz"], out["n"], out["views"], out["idx"], gathered, self.n_cam, t0=t0, stride_t=st,
+                                            stride_c=sc, P=self.max_points, points=points, min_views=self.vis_params["min_views"],
+                                            out=prev, **self.refine)
+        else:
+            res = ctx.refine_points(out["xyz"], out["n"], grp=out["grp"], out=prev, **self.refine)
+        out.update({v: res[k] for k, v in self.REFINE_KEYS.items()})
+        return out
+
     def _marker_rows(self, out):
-        """The 3-D markers of a batch in the rows `track` and `bodies` speak of: xyz as it is with visibility="any"; with "all" the
-        reported roots in their order (rows beyond n: whatever `order` holds, clamped)"""
-        xyz = out["xyz"]
+        """The 3-D markers of a batch in the rows `track` and `bodies` speak of: xyz (with `refine`: xyz_refined) as it is with
+        visibility="any"; with "all" the reported roots in their order (rows beyond n: whatever `order` holds, clamped)"""
+        xyz = out["xyz_refined"] if self.refine else out["xyz"]
         if self.visibility == "all":
             pick = out["order"].clamp(0, xyz.shape[1] - 1).to(torch.int64)[:, :, None].expand(-1, -1, 3)
             xyz = torch.gather(xyz, 1, pick)
@@ -470,6 +508,8 @@ class BatchTracker:
         else:
             gathered = allgather_records(records, self.world, self.group, force=self.force_collective)
         out = self.triangulate(gathered)
+        if self.refine:
+            out = self.refine_markers(out, gathered)
         if self.track:
             out = self.track_ids(out, steps)
         return self.body_poses(out) if self.bodies else out

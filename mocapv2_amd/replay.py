@@ -38,7 +38,7 @@ class ReplayTracker:
 
     def __init__(self, K, dist, R, t, F, width, height, batch=64, obj_count=OBJ_COUNT, device=0, max_points=32,
                  max_groups=4096, bayer_pattern=None, gray_shift=GRAY_SHIFT, depth=1, visibility="all", min_views=2, gate=10.0,
-                 max_err=25.0, max_passes=3, cutoff=10.0, max_hyp=8192, track=None, subpixel=None, bodies=None):
+                 max_err=25.0, max_passes=3, cutoff=10.0, max_hyp=8192, track=None, subpixel=None, bodies=None, refine=None):
         """visibility="any" (BatchTracker's): a time step yields the markers at least min_views cameras see, found from any
         camera pair, in acceptance order (more views first, then smaller error) -- the first obj_count + 1 of them as
         object_points, image_points [markers, C, 2] float64 with NaN where a camera does not see the marker; F may be None.
@@ -54,7 +54,10 @@ class ReplayTracker:
         per time step; the dicts of run_batches gain body_R, body_t, body_q, body_rms, body_n, body_label, body_status (host
         arrays [n_steps, B, ...]) and body_messages: per time step one rigid_message per body, {"<name>": [w, x, y, z, tx, ty, tz]};
         a body without a pose in a step repeats its previous message (seven zeros until its first pose).  run() yields the same per
-        time step.  The labels are rows of the step's markers before the obj_count selection.  `messages` stay as they are."""
+        time step.  The labels are rows of the step's markers before the obj_count selection.  `messages` stay as they are.
+        refine (BatchTracker's): {"max_iters": 10, "ftol": 1e-9, "lambda0": 1e-3, "max_res2": ..., "max_drop": 0} -- the markers are
+        moved to the minimum of their reprojection error: object_points, and with them the messages, hold the refined points
+        (`track` and `bodies` read them too; a marker that could not be refined keeps its point).  None is the path as it was."""
         self.n_cam = len(K)
         self.batch = int(batch)
         self.obj_count = obj_count
@@ -63,8 +66,9 @@ class ReplayTracker:
         self.tracker = BatchTracker(K, dist, R, t, F, width, height, self.batch, device=device, max_points=max_points,
                                     max_groups=max_groups, bayer_pattern=bayer_pattern, gray_shift=gray_shift, depth=self.depth,
                                     visibility=visibility, min_views=min_views, gate=gate, max_err=max_err, max_passes=max_passes,
-                                    cutoff=cutoff, max_hyp=max_hyp, track=track, subpixel=subpixel, bodies=bodies)
+                                    cutoff=cutoff, max_hyp=max_hyp, track=track, subpixel=subpixel, bodies=bodies, refine=refine)
         self.visibility = visibility
+        self.refined = refine is not None
         self.tracked = track is not None
         self.body_names = self.tracker.body_tables["names"] if bodies is not None else None
         if self.body_names is not None:  # the message in force per body: zeros until its first pose
@@ -117,7 +121,7 @@ class ReplayTracker:
         n = self.tracker.finish(out, first_step=b0)[:nb]  # raises CapacityError: no time step is answered from shortened lists
         if self.visibility == "any":
             return self._collect_any(b0, nb, out, n)
-        xyz = out["xyz"].cpu().numpy()[:nb]
+        xyz = out["xyz_refined" if self.refined else "xyz"].cpu().numpy()[:nb]
         grp = out["grp"].cpu().numpy()[:nb].astype(np.int64)
         order = out["order"].cpu().numpy()[:nb]
         oc = self.obj_count
@@ -164,7 +168,7 @@ class ReplayTracker:
         """_collect for visibility="any": the rows below n[s] are the markers, already in their order; nothing beyond them is
         read (mocap_correspond_visible leaves those rows unspecified)."""
         lane = next(l for l in self.tracker.lanes if l.out is out)
-        xyz = out["xyz"].cpu().numpy()[:nb]
+        xyz = out["xyz_refined" if self.refined else "xyz"].cpu().numpy()[:nb]
         idx = out["idx"].cpu().numpy()[:nb]
         xy, _ = MocapContext.record_views(lane.records)
         xy = xy.cpu().numpy().reshape(self.batch, self.n_cam, -1, 2)[:nb]
