@@ -402,22 +402,24 @@ class BatchTracker:
             o += n
         return self.records
 
+    @property
+    def record_layout(self):
+        """Where the *_records entries find this rank's time steps in the records of all cameras: world == 1: the lane's own
+        records, time-major; else the all-gathered records, camera-major, from time step rank * T"""
+        t0, st, sc = (0, self.n_cam, 1) if self.world == 1 else (self.rank * self.T, 1, self.t_total)
+        return {"t0": t0, "stride_t": st, "stride_c": sc, "P": self.max_points}
+
     def triangulate(self, gathered):
         """Stage B for this rank's time steps [rank * T, (rank + 1) * T) from the records of all cameras
         (world == 1: self.records, time-major; else the all-gathered records, camera-major)."""
         ctx = self.ctx
         points = self._cur.subpix["xy"] if self.subpixel else None  # (world == 1: `gathered` is this lane's records)
         if self.visibility == "any":
-            t0, st, sc = (0, self.n_cam, 1) if self.world == 1 else (self.rank * self.T, 1, self.t_total)
-            self.out = ctx.correspond_visible_records(gathered, self.T, self.n_cam, t0=t0, stride_t=st, stride_c=sc,
-                                                      P=self.max_points, out=self.out, points=points, **self.vis_params)
-        elif self.world == 1:
-            self.out = ctx.correspond_records(gathered, self.T, self.n_cam, t0=0, stride_t=self.n_cam, stride_c=1,
-                                              P=self.max_points, max_groups=self.max_groups, out=self.out, points=points)
+            self.out = ctx.correspond_visible_records(gathered, self.T, self.n_cam, **self.record_layout, out=self.out, points=points,
+                                                      **self.vis_params)
         else:
-            self.out = ctx.correspond_records(gathered, self.T, self.n_cam, t0=self.rank * self.T, stride_t=1,
-                                              stride_c=self.t_total, P=self.max_points, max_groups=self.max_groups,
-                                              out=self.out)
+            self.out = ctx.correspond_records(gathered, self.T, self.n_cam, **self.record_layout, max_groups=self.max_groups,
+                                              out=self.out, points=points)
         if self.subpixel:
             self.out["subpix_flags"] = self._cur.subpix["flags"]
         return self.out
@@ -431,11 +433,9 @@ class BatchTracker:
         ctx = self._cur.ctx
         prev = {k: out[v] for k, v in self.REFINE_KEYS.items()} if "xyz_refined" in out else None
         if self.visibility == "any":
-            t0, st, sc = (0, self.n_cam, 1) if self.world == 1 else (self.rank * self.T, 1, self.t_total)
             points = self._cur.subpix["xy"] if self.subpixel else None
-            res = ctx.refine_points_records(out["xyz"], out["n"], out["views"], out["idx"], gathered, self.n_cam, t0=t0, stride_t=st,
-                                            stride_c=sc, P=self.max_points, points=points, min_views=self.vis_params["min_views"],
-                                            out=prev, **self.refine)
+            res = ctx.refine_points_records(out["xyz"], out["n"], out["views"], out["idx"], gathered, self.n_cam, **self.record_layout,
+                                            points=points, min_views=self.vis_params["min_views"], out=prev, **self.refine)
         else:
             res = ctx.refine_points(out["xyz"], out["n"], grp=out["grp"], out=prev, **self.refine)
         out.update({v: res[k] for k, v in self.REFINE_KEYS.items()})
