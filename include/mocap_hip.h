@@ -601,13 +601,14 @@ MOCAP_API int mocap_rig_linearize_intrinsics(mocap_ctx_t ctx, int C, int N, int 
  *                         status > 0: MOCAP_RIG_STOP_*; status < 0: MOCAP_INTR_E_*, and that camera's kd and poses are left
  *                         as they were.  Every camera has its own damping, stop and status: a finished or failed camera
  *                         changes nothing in another, and a camera's results are the bits it gives when calibrated alone
- * A camera needs at least 3 views and a view at least 4 points, else the camera reports MOCAP_INTR_E_LAYOUT.  Offsets that
+ * A camera needs at least 3 views, a view at least 4 points, and the camera at least as many equations as unknowns, 2 points
+ * >= 9 + 6 views (3 views of 4 points fall short: 24 for 27), else the camera reports MOCAP_INTR_E_LAYOUT.  Offsets that
  * descend or sizes outside the ranges are bad arguments (MOCAP_E_INVALID).
  * Asynchronous on `stream`: all max_iters iterations are enqueued (four launches each), the kernels of a camera that has
  * stopped return at once, and no array of the iteration crosses to the host.  No floating-point atomics: the same call gives
  * the same bits.  The scratch belongs to the context and grows on demand: calls on one context must be ordered on one stream. */
 enum {
-    MOCAP_INTR_E_LAYOUT = -2,     /* fewer than 3 views, or a view with fewer than 4 points */
+    MOCAP_INTR_E_LAYOUT = -2,     /* fewer than 3 views, a view with fewer than 4 points, or 2 points < 9 + 6 views */
     MOCAP_INTR_E_BEHIND = -3,     /* in the start state a point is not in front of its view's camera, or the cost is not finite */
     MOCAP_INTR_E_DEGENERATE = -4  /* the initialisation cannot tell the focal lengths apart from the views' distances (all views
                                      fronto-parallel, for one): 2x2 determinant <= 1e-10 (trace / 2)^2, or a solution not positive */

@@ -661,7 +661,8 @@ def calibrate_intrinsics(views, image_sizes, start=None, max_iters=50, ftol=1e-1
     reference's counterpart is cv2.calibrateCamera(objpoints, imgpoints, size, None, None) per camera
     (CalculateCameraIntrinsic.py:58); finding the corners in the images (:35-45) stays with the caller.
     views[c]: the views of camera c, each (object points [n][2] or [n][3] with Z = 0 -- the board's corners in board
-    coordinates --, image points [n][2] pixels), at least 3 views of at least 4 points; image_sizes: (width, height), one pair
+    coordinates --, image points [n][2] pixels), at least 3 views of at least 4 points and at least as many equations as unknowns, 2 points >=
+    9 + 6 views (3 views of 4 points fall short: 24 for 27); image_sizes: (width, height), one pair
     for all cameras or one per camera; start: None, or per camera (camera_params entry, list of {"R", "t"} poses).
     Returns one dict per camera: intrinsic_matrix (3x3) and distortion_coef ([k1, k2, p1, p2, k3]) -- the entry is a
     camera_params entry as `calibrate_rig` and `save_intrinsics` take it --, poses (list of {"R": 3x3, "t": 3x1} board ->
@@ -670,7 +671,8 @@ def calibrate_intrinsics(views, image_sizes, start=None, max_iters=50, ftol=1e-1
     point behind its camera, -4 views that cannot tell the focal lengths: all fronto-parallel, for one), iterations, history
     [iterations][4] (cost, lambda, accepted, |step|).  A camera that failed (status < 0) is reported, not raised, so that one bad
     camera does not lose the others: its matrices are the start's (None without one) and its rms_px is NaN.  What the host
-    can see before the call -- too few views or points, shapes, a board that is not flat -- raises ValueError naming the camera."""
+    can see before the call -- too few views or points (also fewer equations than unknowns: the loop would fit such a camera
+    exactly and report a wrong lens with rms 0), shapes, a board that is not flat -- raises ValueError naming the camera."""
     n_cams = len(views)
     if n_cams < 1:
         raise ValueError("no cameras")
@@ -695,6 +697,10 @@ def calibrate_intrinsics(views, image_sizes, start=None, max_iters=50, ftol=1e-1
             objs.append(obj[:, :2])
             imgs.append(img)
             poff.append(poff[-1] + len(obj))
+        n_pts = poff[-1] - poff[voff[-1]]
+        if 2 * n_pts < 9 + 6 * len(cam_views):
+            raise ValueError(f"camera {c}: {n_pts} points in {len(cam_views)} views are {2 * n_pts} equations for "
+                             f"{9 + 6 * len(cam_views)} unknowns, at least as many are needed")
         voff.append(voff[-1] + len(cam_views))
     begin = None
     if start is not None:

@@ -258,7 +258,7 @@ int mocap_rig_bundle_adjust_intrinsics(mocap_ctx_t c, int C, int N, int n_obs, c
 
 // The scratch of an intrinsic calibration, carved out of one block the context owns (grown to twice what a call needs); the
 // partition depends on the problem's sizes alone.  Checks the host-side layout, and uploads it with what it implies: the
-// camera of every view, and per camera whether it has its 3 views of 4 points.
+// camera of every view, and per camera whether it has its 3 views of 4 points and as many equations as unknowns.
 static int intr_args(mocap_ctx* c, int n_cams, const int32_t* view_offset, const int32_t* point_offset, const int32_t* image_size,
                      const double* obj, const double* img, hipStream_t s, IntrArgs& a)
 {
@@ -284,7 +284,8 @@ static int intr_args(mocap_ctx* c, int n_cams, const int32_t* view_offset, const
     memcpy(h_voff, view_offset, sizeof(int32_t) * ((size_t)n_cams + 1));
     memcpy(h_poff, point_offset, sizeof(int32_t) * ((size_t)n_views + 1));
     for (int k = 0; k < n_cams; k++) {
-        bool bad = view_offset[k + 1] - view_offset[k] < 3;
+        const int64_t views = view_offset[k + 1] - view_offset[k], points = point_offset[view_offset[k + 1]] - point_offset[view_offset[k]];
+        bool bad = views < 3 || 2 * points < 9 + 6 * views; // two equations a point, 9 + 6 views unknowns
         for (int v = view_offset[k]; v < view_offset[k + 1]; v++) { h_vcam[v] = k; bad = bad || point_offset[v + 1] - point_offset[v] < 4; }
         h_bad[k] = bad;
         h_size[2 * k] = image_size ? image_size[2 * k] : 1; h_size[2 * k + 1] = image_size ? image_size[2 * k + 1] : 1;

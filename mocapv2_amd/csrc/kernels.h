@@ -553,7 +553,7 @@ struct IntrArgs {
     const int32_t* point_offset; // [n_views + 1] view v owns points point_offset[v] .. point_offset[v + 1] - 1     made by the
     const int32_t* view_cam;     // [n_views] the view's camera                                                      entry point)
     const int32_t* image_size;   // [n_cams][2] width, height (read by the initialisation only)
-    const int32_t* cam_bad;      // [n_cams] nonzero: fewer than 3 views, or a view with fewer than 4 points
+    const int32_t* cam_bad;      // [n_cams] nonzero: fewer than 3 views, a view with fewer than 4 points, or 2 points < 9 + 6 views
     const double* obj;           // [total][2] board points (X, Y), Z = 0
     const double* img;           // [total][2] their pixels
     double* kd_io;               // [n_cams][9] the caller's: fx, fy, cx, cy, k1, k2, p1, p2, k3

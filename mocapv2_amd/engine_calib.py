@@ -43,8 +43,8 @@ def rig_problem(obs_offset, obs_cam, obs_uv, poses, points):
 
 def board_problem(view_offset, point_offset, obj_xy, img_uv):
     """A board-view problem in the layout of mocap_intrinsics_calibrate: (n_cams, n_views, view_offset, point_offset int32,
-    obj_xy, img_uv [total][2]) as contiguous host arrays.  Only the shapes are checked here: what a camera or a view lacks is
-    that camera's MOCAP_INTR_E_LAYOUT."""
+    obj_xy, img_uv [total][2]) as contiguous host arrays.  Only the shapes are checked here: what a camera or a view lacks
+    (3 views, 4 points a view, 2 points >= 9 + 6 views) is that camera's MOCAP_INTR_E_LAYOUT."""
     voff = np.ascontiguousarray(view_offset, np.int32).reshape(-1)
     poff = np.ascontiguousarray(point_offset, np.int32).reshape(-1)
     obj = np.ascontiguousarray(obj_xy, np.float64).reshape(-1, 2)

@@ -1,5 +1,6 @@
 """NumPy restatement of the intrinsic calibration the HIP kernels implement, and the seeded cases the
-tests share.  Not a test module: the yardstick of tests/test_intrinsics_host.py and tests/test_gpu_intrinsics.py.
+tests share.  Not a test module: the yardstick of tests/test_intrinsics_host.py, tests/test_gpu_intrinsics.py and
+tests/test_gpu_intrinsics_shapes.py.
 
 Definition (all FP64), per camera.  Views v of a planar board: board points (X, Y, 0), their pixels (u, v).  Unknowns: kd =
 (fx, fy, cx, cy, k1, k2, p1, p2, k3) and per view a pose (R_v, t_v) board -> camera.  Residual of a point: the projection of
@@ -17,7 +18,7 @@ what the order of the sums over points and views is worth.
 
 Initialisation (no start given): per view a Hartley-normalised DLT homography (smallest eigenvector of the 9x9 A^T A),
 principal point ((w - 1) / 2, (h - 1) / 2), 1 / fx^2 and 1 / fy^2 from the 2x2 normal equations of two orthogonality
-constraints per view, zero distortion, the poses from K^-1 H.  `Degenerate` when the 2x2 determinant is <= 1e-10 (trace / 2)^2
+constraints per view, zero distortion, the poses from K^-1 H.  A camera must pass `layout_error` first.  `Degenerate` when the 2x2 determinant is <= 1e-10 (trace / 2)^2
 or a solution is not finite and positive."""
 import json
 import os
@@ -258,8 +259,36 @@ def _hartley(p):
     return np.array([[s, 0, -s * c[0]], [0, s, -s * c[1]], [0, 0, 1.0]])
 
 
-def homography(obj, uv):
-    """Hartley-normalised DLT over all points: H with (u, v, 1) ~ H (X, Y, 1), H[2][2] = 1"""
+def layout_error(view_points):
+    """The layout rule of a camera, from the point counts of its views: None, or what it lacks.  At least 3 views of at
+    least 4 points each, and at least as many equations as unknowns: 2 points >= 9 + 6 views.  (3 views of 4 points, 24 for
+    27, keep the damped normal matrix positive definite; the loop then fits the pixels exactly and reports a wrong lens with
+    rms 0 and a positive status: tests/test_intrinsics_host.py::test_fewer_equations_than_unknowns_fit_a_wrong_lens.)"""
+    n = [int(k) for k in view_points]
+    if len(n) < 3:
+        return f"{len(n)} views, at least 3 are needed"
+    if min(n) < 4:
+        return f"view {n.index(min(n))}: {min(n)} points, at least 4 are needed"
+    if 2 * sum(n) < 9 + 6 * len(n):
+        return f"{2 * sum(n)} equations for {9 + 6 * len(n)} unknowns"
+    return None
+
+
+def status_from_own_start(cam, max_iters=50, ftol=1e-12):
+    """The status the definition gives a camera that brings no start: E_LAYOUT, E_DEGENERATE, or the loop's"""
+    if layout_error([len(o) for o, _ in cam.views]) is not None:
+        return E_LAYOUT
+    try:
+        start = initialise(cam)
+    except Degenerate:
+        return E_DEGENERATE
+    return lm(cam, *start, max_iters=max_iters, ftol=ftol)["status"]
+
+
+def homography(obj, uv, null="eigh"):
+    """Hartley-normalised DLT over all points: H with (u, v, 1) ~ H (X, Y, 1), H[2][2] = 1.  null: the route to the null
+    vector, "eigh" (smallest eigenvector of A^T A, the definition's) or "svd" (last right singular vector of A, SciPy's: a
+    second correct FP64 route, for `start_spread`)"""
     To, Ti = _hartley(obj), _hartley(uv)
     o = obj * To[0, 0] + To[:2, 2]
     i = uv * Ti[0, 0] + Ti[:2, 2]
@@ -269,17 +298,21 @@ def homography(obj, uv):
     A[0::2, 6], A[0::2, 7], A[0::2, 8] = i[:, 0] * o[:, 0], i[:, 0] * o[:, 1], i[:, 0]
     A[1::2, 3], A[1::2, 4], A[1::2, 5] = -o[:, 0], -o[:, 1], -1.0
     A[1::2, 6], A[1::2, 7], A[1::2, 8] = i[:, 1] * o[:, 0], i[:, 1] * o[:, 1], i[:, 1]
-    w, V = np.linalg.eigh(A.T @ A)
-    Hn = V[:, 0].reshape(3, 3)
+    if null == "svd":
+        from scipy import linalg
+        Hn = linalg.svd(A)[2][-1].reshape(3, 3)
+    else:
+        w, V = np.linalg.eigh(A.T @ A)
+        Hn = V[:, 0].reshape(3, 3)
     H = np.linalg.inv(Ti) @ Hn @ To
     return H / H[2, 2]
 
 
-def initialise(cam):
+def initialise(cam, null="eigh"):
     """(kd [9], R [n_views][3][3], t [n_views][3]) of the definition; raises Degenerate"""
     w, h = cam.size
     cx, cy = (w - 1) / 2.0, (h - 1) / 2.0
-    Hs = [homography(o, u) for o, u in cam.views]
+    Hs = [homography(o, u, null) for o, u in cam.views]
     AtA, Atb = np.zeros((2, 2)), np.zeros(2)
     for H in Hs:
         Hc = H.copy()
@@ -405,6 +438,24 @@ CASES = {  # name -> (lens, seed, point counts of the views, sigma)
     "noisy_golden": ("golden", 304, (54, 99, 35, 54, 99, 35, 54, 99, 35, 54, 99, 35), 0.3),
 }
 RIG3 = ("clean_mild", "noisy_golden", "noisy_mild")
+BOARD_20 = board(4, 5, 0.04)      # few corners, for cameras of many views
+BOARD_221 = board(13, 17, 0.015)  # a fine board: four chunks of 64 points, the last of 29
+# Outside the shapes the kernels' header calls typical (tests/test_gpu_intrinsics_shapes.py): name -> (lens, seed, point
+# counts of the views, sigma, board).  A view of fewer points than the board has is a seeded subset, rows in board order.
+SHAPE_CASES = {
+    "many_views": ("mild", 501, (20,) * 70, 0.3, BOARD_20),   # past the 64 lanes that deal a camera's views, by 6
+    "views_64": ("mild", 502, (20,) * 64, 0.3, BOARD_20),     # the exact edge,
+    "views_65": ("mild", 503, (20,) * 65, 0.3, BOARD_20),     # and one view in the second pass
+    "edge_points": ("mild", 504, (63, 64, 65, 127, 128, 129, 221), 0.3, BOARD_221),  # chunks of 64: last of 63, 64, 1, 63, 64, 1, 29
+    "small": ("mild", 505, (5, 5, 5), 0.3, BOARD_54),         # 30 equations, 27 unknowns: the smallest layout with 3 views
+}
+SHAPES3 = ("edge_points", "many_views", "small")
+RAGGED5 = ("clean_mild", "noisy_golden", "noisy_mild", "edge_points", "small")  # five different cameras, 33 views, 2 158 points
+SHAPE_START_SEED ={"edge_points": 404, "many_views": 405, "small": 406}  # of perturbed_start
+LAYOUT_CASES = {  # around the layout rule 2 points >= 9 + 6 views; nothing is asserted about the lens they give
+    "three_by_four": ("mild", 506, (4, 4, 4), 0.3, BOARD_54),  # 24 equations, 27 unknowns: refused
+    "five_by_four": ("mild", 507, (4,) * 5, 0.3, BOARD_54),    # 40 for 39: accepted by the rule
+}
 _made = {}
 
 
@@ -413,15 +464,15 @@ def case(name):
     the partial view's choice of corners, the pixel noise."""
     if name in _made:
         return _made[name]
-    lens, seed, counts, sigma = CASES[name]
+    lens, seed, counts, sigma, *own = next(d[name] for d in (CASES, SHAPE_CASES, LAYOUT_CASES) if name in d)
     K, dist, size, rng_d = LENSES[lens]()
     rng = np.random.default_rng(seed)
     views, Rs, ts = [], [], []
     for n in counts:
-        pts = BOARD_99 if n == 99 else BOARD_54
+        pts = own[0] if own else BOARD_99 if n == 99 else BOARD_54
         R, t, px = random_view(rng, pts, K, dist, size, rng_d)
-        if n == 35:
-            keep = np.sort(rng.choice(54, 35, replace=False))
+        if n < len(pts):
+            keep = np.sort(rng.choice(len(pts), n, replace=False))
             pts, px = pts[keep], px[keep]
         px = px + rng.normal(0, 1.0, px.shape) * sigma
         views.append((pts, px))
@@ -440,6 +491,35 @@ def fronto_parallel(seed=305, n_views=4):
         _, _, px = random_view(rng, BOARD_54, K, np.zeros(5), size, rng_d, tilt=0.0)
         views.append((BOARD_54, px))
     return Camera(views, size)
+
+
+def failed_cameras():
+    """Cameras that cannot be calibrated, name -> (Camera, the status it must report): two views; none at all (the offsets
+    admit it); four views of which one has no points; fronto-parallel views"""
+    good = case("noisy_mild")["cam"]
+    none = np.zeros((0, 2))
+    return {"two_views": (Camera(good.views[:2], good.size), E_LAYOUT),
+            "no_views": (Camera([], good.size), E_LAYOUT),
+            "empty_view": (Camera([good.views[0], (none, none), good.views[2], good.views[3]], good.size), E_LAYOUT),
+            "fronto_parallel": (fronto_parallel(), E_DEGENERATE)}
+
+
+def start_spread(cam, n_perm=10):
+    """How far two correct FP64 routes to the initialisation lie apart, as the cost at the start relative to `initialise`'s:
+    (the null vector by scipy.linalg.svd(A) instead of eigh(A^T A); the largest over n_perm seeded permutations of the points
+    within the views, by eigh).  The device's route is a third, cyclic Jacobi on A^T A."""
+    base = cost_of(cam, *initialise(cam))[0]
+    svd = abs(cost_of(cam, *initialise(cam, "svd"))[0] / base - 1)
+    perm = 0.0
+    for s in range(n_perm):
+        rng = np.random.default_rng(3000 + s)
+        views = []
+        for o, u in cam.views:
+            p = rng.permutation(len(o))
+            views.append((o[p], u[p]))
+        cam2 = Camera(views, cam.size)
+        perm = max(perm, abs(cost_of(cam2, *initialise(cam2))[0] / base - 1))
+    return float(svd), float(perm)
 
 
 def with_a_bad_view(cam, bad, shift=5.0, seed=306):
