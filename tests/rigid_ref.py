@@ -274,3 +274,33 @@ def lattice_case():
     equilateral model triangle of that side -- all 4 * 3 * 2 = 24 ordered triples are candidates of its one model triple"""
     tet = np.array([[1.0, 1.0, 1.0], [1.0, -1.0, -1.0], [-1.0, 1.0, -1.0], [-1.0, -1.0, 1.0]]) * 0.1
     return tet, tet[:3].copy()
+
+
+# ---- candidate lists longer than the workgroup ------------------------------------------------------------------------------------
+# Every detection is an exact lattice or tetrahedron point: the lattice's distances are 0.125 sqrt(m), the nearest two of them
+# (0.125 and 0.125 sqrt(2)) 0.05 apart, against TOL = 0.003 and noise of 2e-4 per axis -- no |d - L| < tol is ever close.
+SPACING, LATTICE_NOISE = 0.125, 2e-4
+SQUARE = np.array([[0.0, 0.0, 0.0], [1.0, 0.0, 0.0], [1.0, 1.0, 0.0], [0.0, 1.0, 0.0]]) * SPACING
+TRIANGLE = SQUARE[:3].copy()
+CUBE = np.array([[x, y, z] for z in (0.0, 1.0) for y in (0.0, 1.0) for x in (0.0, 1.0)]) * SPACING
+N_SQUARE, N_TRIANGLE, N_CUBE, N_SQUARE_TIES = 3456, 864, 46656, 912  # test_rigid_host asserts each from the restatement
+
+
+def lattice(noise=0.0, seed=22):
+    """The 4 x 4 x 4 lattice of spacing 0.125 -- 64 detections, the most a step holds -- with its rows in a seeded permutation
+    (the same one with and without noise), and N(0, noise) added per axis"""
+    rng = np.random.default_rng(seed)
+    g = np.arange(4) * SPACING
+    pts = np.array([[x, y, z] for z in g for y in g for x in g])[rng.permutation(64)]
+    return pts + rng.normal(scale=noise, size=pts.shape) if noise else pts
+
+
+def lattice_steps():
+    """(xyz [2, 64, 3], n [2]): the exact lattice and the noisy one as the two time steps of one call"""
+    return np.stack([lattice(), lattice(LATTICE_NOISE)]), np.array([64, 64], np.int32)
+
+
+def tetrahedra(k):
+    """k copies of lattice_case()'s tetrahedron, 5.0 apart along x and y: 24 k candidates for its equilateral model, all of rms 0"""
+    tet, model = lattice_case()
+    return np.concatenate([tet + [5.0 * (i % 4), 5.0 * (i // 4), 0.0] for i in range(k)]), model

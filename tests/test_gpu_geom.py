@@ -6,6 +6,7 @@ import os
 import numpy as np
 import pytest
 
+import ba_cases as bc
 import oracle
 from mocapv2_amd.synth import MILD_DIST, Scene
 
@@ -188,6 +189,72 @@ def test_resident_ba_residuals_match_the_reference_fixture_and_the_oracle():
         for x, e in zip(sets, got):
             exp = oracle.ba_residuals(x, C, pts, valid, K, dist)
             assert e.shape == exp.shape and len(exp) > 40 and np.allclose(e, exp, rtol=2e-5, atol=1e-6), holes
+
+
+# ---- mocap_ba_residuals beyond one round of 256 groups (the problems and what they hold: tests/ba_cases.py, test_ba_cases_host) ----
+@pytest.fixture(scope="module")
+def ba600():
+    from mocapv2_amd.engine import MocapContext
+    p = bc.problem(600)
+    ctx = MocapContext(1, 1)
+    ctx.set_cameras(p["K"], p["dist"], p["R"], p["t"])
+    return ctx, p
+
+
+@pytest.mark.parametrize("B", [1, 13])
+@pytest.mark.parametrize("N", bc.SIZES)
+def test_ba_residuals_of_256_257_and_600_groups_match_the_oracle(ba600, N, B):
+    """No holes: one full round and no second, a second round of one group, three rounds with a partial last; one parameter vector
+    and the 13 of a forward-difference Jacobian of 3 cameras"""
+    ctx, p = ba600
+    pts, sets = p["pts"][:N], p["sets"][:B]
+    got = ctx.ba_problem(pts).residuals(sets)
+    assert len(got) == B
+    for x, e in zip(sets, got):
+        exp = oracle.ba_residuals(x, bc.C, pts, np.ones((N, bc.C), np.uint8), p["K"], p["dist"])
+        assert e.dtype == np.float32 and e.shape == exp.shape == (N,) and np.allclose(e, exp, rtol=2e-5, atol=1e-6)
+
+
+def test_ba_residuals_do_not_show_the_round_a_group_falls_into(ba600):
+    """Every group of a hole-free problem is solved on its own: rows [0, 256) and [256, 512) of the 600-group answer are the
+    answers of those groups alone, byte for byte"""
+    ctx, p = ba600
+    whole = ctx.ba_problem(p["pts"]).residuals(p["sets"])
+    for lo in (0, 256):
+        part = ctx.ba_problem(p["pts"][lo:lo + 256]).residuals(p["sets"])
+        for b in range(len(p["sets"])):
+            assert whole[b].shape == (600,) and part[b].tobytes() == whole[b][lo:lo + 256].tobytes(), (lo, b)
+
+
+@pytest.mark.parametrize("B", [1, 13])
+def test_ba_residuals_with_holes_carry_the_base_across_the_rounds(ba600, B):
+    """Holes before, at and behind the round boundaries of both loops (ba_cases.holes): the object index of every group from 256 on
+    lies below its group index, so the positional pairing crosses the boundaries out of step, and the second loop drops a pair in
+    its first and one in its second round.  The length is the rule's (591 object points, 589 residuals) and the oracle's."""
+    ctx, p = ba600
+    valid = bc.holes()
+    nobj, nres = bc.lengths_by_the_rule(valid)
+    assert (nobj, nres) == (bc.N_TRIANGULATED, bc.N_RESIDUALS)
+    got = ctx.ba_problem(p["pts"], valid).residuals(p["sets"][:B])
+    for x, e in zip(p["sets"][:B], got):
+        exp = oracle.ba_residuals(x, bc.C, p["pts"], valid, p["K"], p["dist"])
+        assert len(exp) == nres and e.shape == exp.shape and np.allclose(e, exp, rtol=2e-5, atol=1e-6)
+
+
+def test_ba_residuals_after_the_contexts_blocks_grew(ba600):
+    """N = 64, N = 600, N = 64 on one fresh context: the pinned block and the object points' buffer grow in between, and the two
+    answers for N = 64 are the same bytes"""
+    from mocapv2_amd.engine import MocapContext
+    _, p = ba600
+    ctx = MocapContext(1, 1)
+    ctx.set_cameras(p["K"], p["dist"], p["R"], p["t"])
+    small, large = ctx.ba_problem(p["pts"][:64]), ctx.ba_problem(p["pts"])
+    first = small.residuals(p["sets"])
+    middle = large.residuals(p["sets"])
+    again = small.residuals(p["sets"])
+    assert all(e.shape == (600,) for e in middle)
+    for a, b in zip(first, again):
+        assert a.shape == (64,) and a.tobytes() == b.tobytes()
 
 
 @pytest.mark.parametrize("C,M,T", [(2, 5, 4), (6, 8, 16), (6, 32, 8), (8, 16, 4)])

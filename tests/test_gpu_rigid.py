@@ -4,6 +4,10 @@ status, n_in and label are compared for EQUALITY everywhere; R, t, q and rms as 
 the floats are unspecified).  The definition fixes every operation and its order, uses + - * / and sqrt only, and the library is
 built without fused multiply-adds, so there is no tolerance anywhere.
 
+Candidate lists from none to 56 come from the seeded scene and the hand-made bodies; lists of 240 to 3456 candidates -- up to 14
+trips of the workgroup's lanes -- and one of 46 656, beyond the LDS list, from the lattice and the tetrahedra of rigid_ref, whose
+counts test_rigid_host asserts.
+
 The trackers (rendered frames, 3 cameras at 640 x 480, one body of 4 discs, sub-pixel centroids) are checked against the scene's
 truth.  Measured on the MI355X over the 4 steps, both visibilities alike: the worst pose is 0.0000479 rad and 0.02119 mm from
 truth (docstring of test_trackers_find_the_rendered_body); the bounds are twice that."""
@@ -177,6 +181,76 @@ def test_exactly_max_hyp_candidates_and_one_more(ctx):
     ok = rest & (fits["status"] == 0)
     for k in FLOATS:
         assert np.array_equal(over[k][ok].view(np.uint64), fits[k][ok].view(np.uint64)), k
+
+
+# ---- candidate lists of many trips of the 256 lanes (the constructions and their counts: rigid_ref, test_rigid_host) ---------------
+LONG_MODELS = [rr.SQUARE, rr.TRIANGLE]
+
+
+@pytest.fixture(scope="module")
+def lattice_want():
+    """The restatement on the exact and the noisy lattice (T = 2) for the square and the triangle: 3456 and 864 candidates each.
+    A result does not depend on max_hyp once the list fits, so the tests below share this one."""
+    xyz, n = rr.lattice_steps()
+    want = run_ref(xyz, n, LONG_MODELS, max_hyp=rr.MAX_HYP)
+    assert (want["status"] == 0).all() and want["n_in"].tolist() == [[4, 3], [4, 3]]
+    assert (want["rms"][0] == 0.0).all() and (want["rms"][1] > 0.0).all()
+    return xyz, n, want
+
+
+def test_lists_of_3456_and_864_candidates(ctx, lattice_want):
+    """Every lane evaluates 13 or 14 candidates of the square and 3 or 4 of the triangle and keeps its best.  Exact lattice: 912
+    candidates tie at rms 0 and the winner, the fourth in (h, i, j, k) order, can stand anywhere in the list.  Noisy lattice: rms^2
+    decides among candidates that label different detections."""
+    xyz, n, want = lattice_want
+    assert_same(run_gpu(ctx, xyz, n, LONG_MODELS, max_hyp=rr.MAX_HYP), want, "lattice")
+
+
+def test_3456_candidates_at_max_hyp_and_one_more(ctx, lattice_want):
+    xyz, n, want = lattice_want
+    fits = run_gpu(ctx, xyz, n, [rr.SQUARE], max_hyp=rr.N_SQUARE)
+    assert_same(fits, {k: v[:, :1] for k, v in want.items()}, "3456")
+    over = check(ctx, xyz, n, [rr.SQUARE], "3455", max_hyp=rr.N_SQUARE - 1)
+    assert (over["status"] == rr.E_HYP).all() and (over["n_in"] == 0).all() and (over["label"] == -1).all()
+
+
+@pytest.mark.parametrize("B", [3, 4])
+def test_a_list_beyond_the_lds_leaves_its_neighbours_untouched(ctx, lattice_want, B):
+    """The cube's 46 656 candidates against max_hyp = 4096, the size of the LDS list itself: MOCAP_RIGID_E_HYP for that body in both
+    steps, and every other body and step is bit for bit what it is in a call without the cube (and what the restatement says)."""
+    xyz, n, want = lattice_want
+    models = [rr.SQUARE, rr.CUBE, rr.TRIANGLE] + [rr.SQUARE] * (B - 3)
+    got = run_gpu(ctx, xyz, n, models, max_hyp=rr.MAX_HYP)
+    assert (got["status"][:, 1] == rr.E_HYP).all() and (got["n_in"][:, 1] == 0).all() and (got["label"][:, 1] == -1).all()
+    keep = [b for b in range(B) if b != 1]
+    rest = {k: v[:, keep] for k, v in got.items()}
+    alone = run_gpu(ctx, xyz, n, [models[b] for b in keep], max_hyp=rr.MAX_HYP)
+    assert (alone["status"] == 0).all()
+    for k in INTS + FLOATS:
+        assert rest[k].tobytes() == alone[k].tobytes(), k
+    assert_same(rest, {k: v[:, [0, 1] + [0] * (B - 3)] for k, v in want.items()}, "beside the cube")  # columns of LONG_MODELS
+
+
+@pytest.mark.parametrize("k,count", [(10, 240), (11, 264)])
+def test_one_trip_of_the_lanes_and_eight_candidates_more(ctx, k, count):
+    """10 tetrahedra: 240 candidates, one each for 240 lanes; 11: 264, eight lanes take a second.  max_hyp at the count and one below.
+    (Which eight candidates come second is the list's business: a kernel that forgot them fails here only when the winner is among
+    them, and fails test_lists_of_3456_and_864_candidates always.)"""
+    det, model = rr.tetrahedra(k)
+    xyz, n = steps_of([det], 64)
+    fits = check(ctx, xyz, n, [model], f"{count}", max_hyp=count)
+    assert fits["status"][0, 0] == 0 and fits["label"][0, 0, :3].tolist() == [0, 1, 2] and fits["rms"][0, 0] == 0.0
+    over = check(ctx, xyz, n, [model], f"{count - 1}", max_hyp=count - 1)
+    assert over["status"][0, 0] == rr.E_HYP and over["n_in"][0, 0] == 0 and (over["label"][0, 0] == -1).all()
+
+
+def test_the_lists_arrival_order_does_not_show(ctx, lattice_want):
+    """The list's order differs from run to run (an LDS atomic hands out its places); no byte of the output may"""
+    xyz, n, _ = lattice_want
+    a, b = (run_gpu(ctx, xyz[:1], n[:1], [rr.SQUARE], max_hyp=rr.MAX_HYP) for _ in range(2))
+    assert (a["status"] == 0).all()
+    for k in INTS + FLOATS:
+        assert a[k].tobytes() == b[k].tobytes(), k
 
 
 def test_bad_arguments_launch_nothing_and_bad_tables_are_reported(ctx, scene):

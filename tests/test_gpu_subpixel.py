@@ -6,8 +6,10 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import subpixel_cases as cases
 import subpixel_ref as ref
 from lens_cases import case
+from subpixel_cases import pyramid, records_of
 from mocapv2_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -21,23 +23,6 @@ def torch_cuda():
     import torch
     assert torch.cuda.is_available(), "these tests need the MI355X"
     return torch
-
-
-def pyramid(img, cx, cy, half=2, peak=250, step=40):
-    H, W = img.shape
-    for y in range(max(cy - half, 0), min(cy + half, H - 1) + 1):
-        for x in range(max(cx - half, 0), min(cx + half, W - 1) + 1):
-            img[y, x] = max(int(img[y, x]), peak - step * max(abs(x - cx), abs(y - cy)))
-
-
-def records_of(point_lists, counts=None, cap=8):
-    """int32 records [n, 2 + 2 cap] as blob_centroids writes them; counts overrides the lists' lengths"""
-    rec = np.zeros((len(point_lists), 2 + 2 * cap), np.int32)
-    for i, pts in enumerate(point_lists):
-        rec[i, 0] = len(pts) if counts is None else counts[i]
-        for j, (x, y) in enumerate(pts):
-            rec[i, 2 + 2 * j], rec[i, 3 + 2 * j] = x, y
-    return rec
 
 
 def strided(torch, frames, pad_rows, pad_cols):
@@ -246,6 +231,103 @@ def test_bayer_frames_equal_the_gray_path(torch_cuda, shift):
             assert same_bits(b[0], want[0]) and same_bits(b[1], want[1])
             assert (want[1][:, :6, 1] & ref.CUT).all() and (want[1][:, :7, 0] > 0).all()
     assert not np.array_equal(grays[0], grays[1]) and not np.array_equal(grays[0], grays[3])  # the patterns do differ
+
+
+# ---- 3b. full lists of 256 blobs, and starts outside the frame (tests/subpixel_cases.py; test_subpixel_host says what they hold) --
+def identity_ctx(W, H):
+    from mocapv2_amd.engine import MocapContext
+    ctx = MocapContext(W, H)
+    assert ctx.set_undistort(0, synth.intrinsics(W, H), synth.ZERO_DIST)
+    return ctx
+
+
+def both(torch, ctx, frames, rec, mb, rows=None, ref_kw={}, **kw):
+    """run() against expect(), bit for bit -> the restatement's (xy, info)"""
+    got = run(torch, ctx, torch.from_numpy(frames).cuda(), rec, mb, rows=rows, **kw)
+    want = expect(frames, rec, mb, rows=rows, **kw, **ref_kw)
+    bad = np.argwhere(got[1] != want[1])
+    assert same_bits(got[1], want[1]), (kw, bad[:4].tolist(), got[1][tuple(bad[0])], want[1][tuple(bad[0])])
+    assert same_bits(got[0], want[0]), (kw, np.argwhere(got[0] != want[0])[:4].tolist())
+    return want
+
+
+@pytest.fixture(scope="module")
+def dense():
+    frame, centres, pts = cases.dense_frame()
+    return frame[None], records_of([pts], cap=256), identity_ctx(cases.W1, cases.H1)
+
+
+@pytest.mark.parametrize("radius", [4, 11, 12])
+def test_256_blobs_in_permuted_rows(torch_cuda, dense, radius):
+    """One centroid per thread up to the last, 64 trips of the four waves.  Radius 4: no flag; 12: every row has a neighbour at
+    exactly dy == r; 11: the same one pixel short"""
+    frames, rec, ctx = dense
+    fl = both(torch_cuda, ctx, frames, rec, 256, radius=radius, floor=cases.FLOOR)[1][0, :, 1]
+    assert not fl.any() if radius == 4 else (fl & ref.NEIGHBOUR).all() if radius == 12 else (fl == ref.EDGE).sum() == 20
+
+
+def test_counts_about_a_wave_and_about_the_limit(torch_cuda, dense):
+    """Counts 1, 64, 65, 255, 256 and 300 (above max_blobs = 256: the first 256 rows are refined) in one batch; max_blobs = 100 on
+    a count of 256: the rows from 100 on keep the sentinel, and the first 100 see only each other as neighbours"""
+    frames, rec, ctx = dense
+    counts = [1, 64, 65, 255, 256, 300]
+    many = np.repeat(rec, len(counts), axis=0)
+    many[:, 0] = counts
+    for radius in (4, 12):
+        info = both(torch_cuda, ctx, np.repeat(frames, len(counts), axis=0), many, 256, radius=radius, floor=cases.FLOOR)[1]
+        assert [(info[i, :, 1] >= 0).sum() for i in range(len(counts))] == [1, 64, 65, 255, 256, 256]
+        assert same_bits(info[4], info[5])
+    info = both(torch_cuda, ctx, frames, rec, 100, rows=256, radius=12, floor=cases.FLOOR)[1]
+    assert (info[0, 100:] == SENT_INFO).all() and (info[0, :100, 1] >= 0).all()
+
+
+def test_a_neighbour_only_one_lane_of_one_trip_sees(torch_cuda):
+    frame, pts = cases.sparse_frame()
+    info = both(torch_cuda, identity_ctx(cases.W2, cases.H2), frame[None], records_of([pts], cap=256), 256, radius=cases.RADIUS2,
+                floor=cases.FLOOR)[1]
+    assert np.flatnonzero(info[0, :, 1] & ref.NEIGHBOUR).tolist() == sorted(r for pair in cases.PAIRS for r in pair)
+
+
+@pytest.mark.parametrize("coords", ["ideal", "raw"])
+def test_starts_outside_the_frame(torch_cuda, coords):
+    """Integer centroids beyond each border, beyond a corner and at the ends of the int32 range: the window starts at the clamped
+    pixel; where it is empty the point comes back as it was handed in, not clamped"""
+    frame, pts = cases.outside_frame()
+    ctx = identity_ctx(cases.W3, cases.H3)
+    empty = [k for k in range(len(pts)) if k not in cases.OUTSIDE_LIT]
+    for radius, iters in cases.OUTSIDE_WINDOWS:
+        xy, info = both(torch_cuda, ctx, frame[None], records_of([pts], cap=16), 16, radius=radius, floor=cases.FLOOR, iters=iters,
+                        coords=coords)
+        assert (info[0, empty, 1] == ref.EMPTY | ref.CUT).all() and xy[0, empty].tolist() == pts[empty].astype(float).tolist()
+        assert (info[0, list(cases.OUTSIDE_LIT), 0] > 0).all()
+
+
+@pytest.mark.parametrize("coords", ["ideal", "raw"])
+def test_a_lens_slot_with_256_centroids_from_corner_to_corner(torch_cuda, coords):
+    """distort_pt in every thread of the workgroup, undistort_pt behind 128 of the 256 windows (the others are EMPTY); the
+    restatement clamps none of these starts (test_subpixel_host)"""
+    from mocapv2_amd.engine import MocapContext
+    frame, pts, start, clamped, lens = cases.lens_frame()
+    ctx = MocapContext(cases.LENS_W, cases.LENS_H)
+    assert not ctx.set_undistort(0, lens[0], lens[1])
+    info = both(torch_cuda, ctx, frame[None], records_of([pts], cap=256), 256, radius=cases.LENS_RADIUS, floor=cases.FLOOR, coords=coords,
+                ref_kw={"lenses": [lens]})[1]
+    assert (info[0, :, 1] == 0).sum() == 128
+
+
+def test_256_blobs_in_a_raw_bayer_frame(torch_cuda, dense):
+    """The dense frame read as a raw Bayer frame (pattern 3, shift 14): window_sums' two-rows-per-trip form on a full list"""
+    torch = torch_cuda
+    frames, rec, ctx = dense
+    d_raw = torch.from_numpy(frames).cuda()
+    gray = ctx.bayer_gray(d_raw, 3, 14)
+    torch.cuda.synchronize()
+    for radius in (4, 12):
+        a = run(torch, ctx, d_raw, rec, 256, radius=radius, floor=cases.FLOOR, bayer_pattern=3, gray_shift=14)
+        b = run(torch, ctx, gray, rec, 256, radius=radius, floor=cases.FLOOR)
+        assert same_bits(a[0], b[0]) and same_bits(a[1], b[1]), radius
+        want = expect(gray.cpu().numpy(), rec, 256, radius=radius, floor=cases.FLOOR)
+        assert same_bits(b[0], want[0]) and same_bits(b[1], want[1]) and (want[1][0, :, 0] > 0).all()
 
 
 # ---- 4. the pipeline ------------------------------------------------------------------------------------------------------

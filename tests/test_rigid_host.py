@@ -54,6 +54,61 @@ def test_the_candidate_list_is_never_shortened():
     assert rr.solve_body(tet, model, [(0, 1, 2)], rr.TOL, rr.GATE, 3, 23)["status"] == rr.E_HYP
 
 
+def _tri(model):
+    return rr.triples_of(model, rr.MIN_AREA)
+
+
+def test_the_lattice_gives_lists_many_times_the_workgroup():
+    """What test_gpu_rigid's long-list cases rely on, from the restatement: on the 4 x 4 x 4 lattice the square has 4 triples of
+    864 candidates each (3456 = 13.5 trips of 256 lanes), all with 4 inliers; on the exact lattice 912 of them share the lowest
+    rms^2 (0.0) bit for bit and the winner is the fourth in (h, i, j, k) order; with 2e-4 of noise the list is as long, and the
+    winner is decided by rms^2 and stands hundreds of places down the ordered list; the triangle has 864 = 3 * 256 + 96; the cube
+    has 56 triples and 46 656 candidates, more than the list holds."""
+    exact, noisy = rr.lattice(), rr.lattice(rr.LATTICE_NOISE)
+    assert exact.shape == (64, 3) and len(np.unique(exact, axis=0)) == 64 and np.array_equal(exact / rr.SPACING, np.round(exact / rr.SPACING))
+    assert not np.array_equal(np.lexsort(exact.T), np.arange(64))  # the rows are permuted
+    assert np.abs(noisy - exact).max() < 5 * rr.LATTICE_NOISE and (noisy != exact).all()
+    for det, slack in ((exact, 1e-12), (noisy, rr.TOL / 2)):  # no distance test is close: a model length, or ten tol off
+        d = rr.dist_table(det)[np.triu_indices(64, 1)]
+        for L in (rr.SPACING, rr.SPACING * np.sqrt(2.0), rr.SPACING * np.sqrt(3.0)):  # the square's two lengths and the cube's third
+            gap = np.abs(d - L)
+            assert ((gap < slack) | (gap > 10 * rr.TOL)).all()
+    assert len(_tri(rr.SQUARE)) == 4 and len(_tri(rr.TRIANGLE)) == 1 and len(_tri(rr.CUBE)) == 56 == rr.MAX_TRIPLES
+    r = rr.solve_body(exact, rr.SQUARE, _tri(rr.SQUARE), rr.TOL, rr.GATE, 3, rr.N_SQUARE)
+    assert r["status"] == 0 and r["n_cand"] == rr.N_SQUARE == 3456 and np.bincount(r["cand"][:, 0]).tolist() == [864] * 4
+    assert (r["cand_n_in"] == 4).all() and r["n_in"] == 4
+    low = r["cand_rms2"].min()
+    assert low == 0.0 and int((r["cand_rms2"] == low).sum()) == rr.N_SQUARE_TIES == 912
+    assert np.array_equal(r["winner"], r["cand"][3]) and r["cand_rms2"][:3].min() > 0.0
+    assert rr.solve_body(exact, rr.SQUARE, _tri(rr.SQUARE), rr.TOL, rr.GATE, 3, rr.N_SQUARE - 1)["status"] == rr.E_HYP
+    rn = rr.solve_body(noisy, rr.SQUARE, _tri(rr.SQUARE), rr.TOL, rr.GATE, 3, rr.N_SQUARE)
+    assert rn["status"] == 0 and rn["n_cand"] == rr.N_SQUARE and (rn["cand_n_in"] == 4).all()
+    place = int(np.flatnonzero((rn["cand"] == rn["winner"]).all(axis=1))[0])
+    best = rn["cand_rms2"] == rn["cand_rms2"].min()
+    assert place >= 256 and best.sum() < 16 and rn["rms"] > 0.0
+    assert not np.array_equal(np.sort(rn["label"][:4]), np.sort(r["label"][:4]))  # it labels other detections than the exact winner
+    for model, count in ((rr.TRIANGLE, rr.N_TRIANGLE), (rr.CUBE, rr.N_CUBE)):
+        for det in (exact, noisy):
+            assert len(rr.candidates(rr.dist_table(det), rr.dist_table(model), _tri(model), rr.TOL)) == count
+    assert rr.N_TRIANGLE == 864 == 3 * 256 + 96 and rr.N_CUBE == 46656 > rr.MAX_HYP
+    assert rr.solve_body(exact, rr.CUBE, _tri(rr.CUBE), rr.TOL, rr.GATE, 3, rr.MAX_HYP)["status"] == rr.E_HYP
+
+
+def test_ten_tetrahedra_fill_one_trip_and_eleven_start_a_second():
+    """k copies of the tetrahedron 5.0 apart: 24 k candidates, 240 at k = 10 and 264 at k = 11.  Every fit is exact but for
+    rounding: rms^2 is 0.0 for five orderings of the copy at the origin (an exact tie that (h, i, j, k) decides) and 1e-33 to
+    1e-30 for all others, so the smallest rms^2 decides among near-ties."""
+    for k, count in ((10, 240), (11, 264)):
+        det, model = rr.tetrahedra(k)
+        assert det.shape == (4 * k, 3)
+        r = rr.solve_body(det, model, _tri(model), rr.TOL, rr.GATE, 3, count)
+        assert r["status"] == 0 and r["n_cand"] == count and r["n_in"] == 3 and (r["cand_n_in"] == 3).all()
+        exact = r["cand_rms2"] == 0.0
+        assert int(exact.sum()) == 5 and (r["cand"][exact, 1:] < 4).all() and r["cand_rms2"].max() < 1e-29
+        assert r["winner"].tolist() == [0, 0, 1, 2] and r["rms"] == 0.0
+        assert rr.solve_body(det, model, _tri(model), rr.TOL, rr.GATE, 3, count - 1)["status"] == rr.E_HYP
+
+
 def test_blind_steps_and_bad_models():
     sc = rr.rigid_scene(2, T=3)
     tri = [rr.triples_of(m, rr.MIN_AREA) for m in sc["models"]]

@@ -10,6 +10,7 @@ import pytest
 
 import oracle
 import lens_cases
+import subpixel_cases as cases
 import subpixel_ref as ref
 from mocapv2_amd import _abi, synth
 
@@ -94,6 +95,69 @@ def test_fallback_values_are_exact_in_both_coordinates():
     a = ref.refine_image(img, [(20, 20)], 6, 0, coords=0)
     b = ref.refine_image(img, [(20, 20)], 6, 0, coords=1)
     assert a[0].tobytes() == b[0].tobytes() and a[2].tolist() == [0]
+
+
+# ---- the constructions of tests/subpixel_cases.py hold what test_gpu_subpixel runs them for -----------------------------
+def test_dense_frame_of_256_blobs_at_radius_4_11_and_12():
+    """256 rows in a permutation, starts -1, 0 or +1 px off in x.  Radius 4: no flag, every centre exact.  Radius 12: the blob one
+    pitch below or above starts at exactly dy == r, so every row is NEIGHBOUR (and EDGE or not).  Radius 11, one pixel short:
+    only rows whose side neighbour starts a pixel towards them keep NEIGHBOUR; the others are EDGE alone."""
+    frame, centres, pts = cases.dense_frame()
+    assert frame.shape == (200, 203) and pts.shape == (256, 2) and len(np.unique(centres, axis=0)) == 256
+    assert sorted(np.unique(pts[:, 0] - centres[:, 0]).tolist()) == [-1, 0, 1] and (pts[:, 1] == centres[:, 1]).all()
+    assert not np.array_equal(np.lexsort(centres.T), np.arange(256))
+    xy, S, fl = ref.refine_image(frame, pts, 4, cases.FLOOR)
+    assert not fl.any() and np.array_equal(xy, centres.astype(float)) and (S == S[0]).all() and S[0] > 0
+    _, _, f12 = ref.refine_image(frame, pts, 12, cases.FLOOR)
+    assert (f12 & ref.NEIGHBOUR).all() and (f12 & ref.EDGE).any() and not (f12 & ref.EDGE).all()
+    _, _, f11 = ref.refine_image(frame, pts, 11, cases.FLOOR)
+    assert (f11 & (ref.NEIGHBOUR | ref.EDGE)).all() and (f11 & ref.NEIGHBOUR).any() and int((f11 == ref.EDGE).sum()) == 20
+
+
+def test_sparse_frame_flags_exactly_the_three_pairs():
+    """Pitch 24 against radius 9: nobody has a neighbour but the rows (0, 255), (3, 64) and (70, 128), 8 px apart -- found by lane
+    63 on the fourth trip of the neighbour search, lane 0 on the second, lane 0 on the third (and back by lanes 0, 3 and 6)"""
+    frame, pts = cases.sparse_frame()
+    assert frame.shape == (392, 395) and len(np.unique(pts, axis=0)) == 256
+    for a, b in cases.PAIRS:
+        assert (pts[b] - pts[a]).tolist() == [8, 0]
+    _, S, fl = ref.refine_image(frame, pts, cases.RADIUS2, cases.FLOOR)
+    assert np.flatnonzero(fl & ref.NEIGHBOUR).tolist() == [0, 3, 64, 70, 128, 255] and (S > 0).all()
+    assert not (fl & ~ref.NEIGHBOUR).any()
+    assert not ref.refine_image(frame, pts[:255], cases.RADIUS2, cases.FLOOR)[2][0]  # row 0 has no other neighbour than row 255
+
+
+def test_starts_outside_the_frame_are_clamped_and_fall_back_to_what_was_handed_in():
+    frame, pts = cases.outside_frame()
+    assert [(ref._start_index(float(x), cases.W3), ref._start_index(float(y), cases.H3)) for x, y in pts] == cases.OUTSIDE_CLAMPED
+    lit = list(cases.OUTSIDE_LIT)
+    empty = [k for k in range(len(pts)) if k not in lit]
+    handed_in = pts.astype(float)
+    for coords in (0, 1):
+        for radius, iters in cases.OUTSIDE_WINDOWS:
+            xy, S, fl = ref.refine_image(frame, pts, radius, cases.FLOOR, iters, coords=coords)
+            assert (fl[empty] == ref.CUT | ref.EMPTY).all() and (S[empty] == 0).all() and np.array_equal(xy[empty], handed_in[empty])
+            assert (S[lit] > 0).all() and (fl[lit] & ref.CUT).all() and not (fl & ref.NEIGHBOUR).any()
+            if (radius, iters) == (6, 3):  # windows cut by the border that find their blobs: refined points inside the frame
+                assert (fl[lit] == ref.CUT).all() and (xy[lit] >= 0).all() and (xy[lit] < [cases.W3, cases.H3]).all()
+            if iters == 1:                   # one window at the clamped pixel: it wants to move, so the point is the one handed in
+                assert (fl[lit] & ref.MOVING).all() and np.array_equal(xy[lit], handed_in[lit])
+    assert xy[5].tolist() == [2147483647.0, -2147483648.0]
+
+
+def test_lens_frame_reaches_the_corners_and_clamps_no_start():
+    """barrel_k123 at 640 x 360, 256 centroids from corner to corner of the undistorted image: the lens pulls every one of them
+    into the raw frame (start pixels from (53, 8) to (602, 350)), so the restatement clamps 0 of the 256 starts.  Half the rows
+    find a blob, half are EMPTY (one of those cut by the border as well)."""
+    frame, pts, start, clamped, lens = cases.lens_frame()
+    assert pts.min(axis=0).tolist() == [0, 0] and pts.max(axis=0).tolist() == [639, 359] and len(np.unique(pts, axis=0)) == 256
+    assert int(clamped.sum()) == 0
+    assert start.min(axis=0).tolist() == [53, 8] and start.max(axis=0).tolist() == [602, 350]
+    for coords in (0, 1):
+        xy, S, fl = ref.refine_image(frame, pts, cases.LENS_RADIUS, cases.FLOOR, K=lens[0], dist=lens[1], identity=False, coords=coords)
+        assert int((fl == 0).sum()) == 128 and int((fl & ref.EMPTY != 0).sum()) == 128
+        if coords == 1:
+            assert np.abs(xy[fl == 0] - pts[fl == 0]).max() < 1.0  # back through the lens: the integer centroid, refined
 
 
 # ---- the symbol, the kernel, the tracker's arguments -------------------------------------------------------------------
