@@ -162,15 +162,20 @@ __device__ __forceinline__ bool solve_from_normal_sums(double B[45], double* V, 
 
 // Inlier test of the definition: e = max(d'^2, d^2) <= thr2 with d' the distance of (x', y') to the line F (x, y, 1) and d
 // that of (x, y) to F^T (x', y', 1).  Each quotient n^2 / den <= thr2 is tested as n^2 <= thr2 * den with den > 0 (no FP64
-// division in the hot loop); a NaN anywhere fails every comparison, so a NaN is not an inlier.  The scoring kernel and the
-// mask kernel both call this function: the mask's population count is the winner's count.
+// division in the hot loop); a NaN anywhere fails every comparison, so a NaN is not an inlier.  A finite point far enough out
+// overflows both sides to +inf, where the quotient is inf / inf = NaN and `inf <= inf` would hold: n^2 must be finite (an
+// infinite n^2 over any den is inf or NaN, never <= thr2; a finite n^2 over an overflowed den would be 0 <= thr2, which
+// the comparison with +inf gives too -- reasoned, not tested: it takes a cancellation in n that no list reaches for a
+// whole table).  The scoring kernel and the mask kernel both call this function: the mask's population count is the
+// winner's count.
 __device__ __forceinline__ bool is_inlier(const double F[9], double x, double y, double xp, double yp, double thr2)
 {
     const double l0 = (F[0] * x + F[1] * y) + F[2], l1 = (F[3] * x + F[4] * y) + F[5], l2 = (F[6] * x + F[7] * y) + F[8];
     const double m0 = (F[0] * xp + F[3] * yp) + F[6], m1 = (F[1] * xp + F[4] * yp) + F[7], m2 = (F[2] * xp + F[5] * yp) + F[8];
     const double n1 = (xp * l0 + yp * l1) + l2, n2 = (x * m0 + y * m1) + m2;
     const double d1 = l0 * l0 + l1 * l1, d2 = m0 * m0 + m1 * m1;
-    return (n1 * n1 <= thr2 * d1) && (n2 * n2 <= thr2 * d2) && d1 > 0.0 && d2 > 0.0;
+    const double q1 = n1 * n1, q2 = n2 * n2;
+    return (q1 <= thr2 * d1) && (q2 <= thr2 * d2) && d1 > 0.0 && d2 > 0.0 && finite(q1) && finite(q2);
 }
 
 } // namespace

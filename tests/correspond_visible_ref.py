@@ -179,6 +179,36 @@ def _member_err(cams, pts, M, X):
     return s / (2 * (M >= 0).sum(axis=1)).astype(np.float64)
 
 
+def _seed_distances(F, pa, pb):
+    """Step 1 for one camera pair: d [len(pa), len(pb)], the distance of every point of pb to the epipolar line of every point of
+    pa (epiline_f64's operations); inf where the line has no direction"""
+    x, y = pa[:, 0], pa[:, 1]
+    la = F[0] * x + F[1] * y + F[2]
+    lb = F[3] * x + F[4] * y + F[5]
+    lc = F[6] * x + F[7] * y + F[8]
+    nu = la * la + lb * lb
+    ok = nu > 0.0
+    sc = 1.0 / np.sqrt(nu)
+    la, lb, lc = la * sc, lb * sc, lc * sc
+    d = np.abs(la[:, None] * pb[:, 0][None, :] + lb[:, None] * pb[:, 1][None, :] + lc[:, None])
+    return np.where(ok[:, None], d, np.inf)
+
+
+def first_pass_distances(pts, counts, K, dist, R, t):
+    """The finite seed distances of pass 0 (nothing claimed yet, undistorted points), sorted: exactly the values step 1 of
+    correspond_visible compares with the cutoff.  The cutoff midway between the k-th and the (k+1)-th gives pass 0 exactly k seeds."""
+    pts = np.asarray(pts).astype(np.float64)
+    counts = np.asarray(counts).astype(np.int64)
+    cams = Cameras(K, dist, R, t)
+    ds = []
+    with np.errstate(all="ignore"):
+        for pr, (a, b) in enumerate(cams.pairs):
+            if counts[a] and counts[b]:
+                d = _seed_distances(cams.F[pr], pts[a, :counts[a]], pts[b, :counts[b]])
+                ds.append(d[np.isfinite(d)])
+    return np.sort(np.concatenate(ds)) if ds else np.zeros(0)
+
+
 def correspond_visible(pts, counts, K, dist, R, t, distorted=0, cutoff=10.0, gate=10.0, min_views=2, max_err=25.0, max_passes=3,
                        max_hyp=8192, Q=None):
     """One time step.  pts [C, P, 2] (any numeric type), counts [C].  Returns dict: n (markers, or E_*), xyz [n, 3], err [n],
@@ -211,17 +241,7 @@ def correspond_visible(pts, counts, K, dist, R, t, distorted=0, cutoff=10.0, gat
                 ia, jb = free[a], free[b]
                 if not len(ia) or not len(jb):
                     continue
-                F = cams.F[pr]
-                x, y = pts[a, ia, 0], pts[a, ia, 1]
-                la = F[0] * x + F[1] * y + F[2]
-                lb = F[3] * x + F[4] * y + F[5]
-                lc = F[6] * x + F[7] * y + F[8]
-                nu = la * la + lb * lb
-                ok = nu > 0.0
-                sc = 1.0 / np.sqrt(nu)
-                la, lb, lc = la * sc, lb * sc, lc * sc
-                d = np.abs(la[:, None] * pts[b, jb, 0][None, :] + lb[:, None] * pts[b, jb, 1][None, :] + lc[:, None])
-                d = np.where(ok[:, None], d, np.inf)
+                d = _seed_distances(cams.F[pr], pts[a, ia], pts[b, jb])
                 if np.isfinite(d).any():
                     margin = min(margin, np.abs(d[np.isfinite(d)] - cutoff).min())
                 ii, jj = np.nonzero(d < cutoff)
