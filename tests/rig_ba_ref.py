@@ -1,5 +1,6 @@
 """NumPy restatement of the rig bundle adjustment the HIP kernels implement, and the seeded cases the
-tests share.  Not a test module: the yardstick of tests/test_rig_ba_host.py and tests/test_gpu_rig_ba.py.
+tests share.  Not a test module: the yardstick of tests/test_rig_ba_host.py, tests/test_gpu_rig_ba.py and
+tests/test_gpu_rig_ba_shapes.py.
 
 Definition (all FP64).  N points, C <= 32 cameras, observations (n, c, u, v) point-major.  Camera 0 is the identity; cameras
 1.. are (R_c, t_c) world -> camera; K and the 5 distortion coefficients are fixed and indexed by the true camera number.
@@ -457,10 +458,12 @@ def permuted(prob, seed):
     return Problem(prob.pt[p], prob.cam[p], prob.uv[p], prob.K, prob.dist, prob.N)
 
 
-def order_spread(prob, R, t, X, lam, n_perm=10):
+def order_spread(prob, R, t, X, lam, n_perm=10, base=None):
     """Largest difference of cost, gradient, S and rhs between the sorted problem and n_perm seeded permutations of its
-    observations, each relative to the quantity's largest entry: dict name -> spread"""
-    base = linearize(prob.sorted(), R, t, X, lam)
+    observations, each relative to the quantity's largest entry: dict name -> spread.  base: the sorted problem's pieces,
+    where the caller has them already."""
+    if base is None:
+        base = linearize(prob.sorted(), R, t, X, lam)
     out = {k: 0.0 for k in ("cost", "gradient", "S", "rhs")}
     for s in range(n_perm):
         lin = linearize(permuted(prob, 1000 + s), R, t, X, lam)
@@ -468,3 +471,121 @@ def order_spread(prob, R, t, X, lam, n_perm=10):
             a, b = np.asarray(base[k], float), np.asarray(lin[k], float)
             out[k] = max(out[k], float(np.abs(a - b).max() / np.abs(a).max()))
     return out
+
+
+# ---- the shapes ------------------------------------------------------------------------------------------------------------
+def first_points(prob, X, n):
+    """(the problem of the first n points, renumbered and sorted, their start X [n][3]): sets N exactly"""
+    keep = prob.pt < n
+    points = np.unique(prob.pt[keep])
+    assert len(points) == n
+    return Problem(np.searchsorted(points, prob.pt[keep]), prob.cam[keep], prob.uv[keep], prob.K, prob.dist, n).sorted(), X[points]
+
+
+def lin_blocks(N):
+    """Workgroups of the point-owning kernels: PT_THREADS = 256 points each (csrc/kernels.h, rig_args' n_lin_blocks)"""
+    return -(-N // 256)
+
+
+def schur_chunks(N):
+    """(workgroups per camera pair of rig_schur_kernel, points of the last one): SCHUR_CHUNK = 1024 points each (csrc/rig_ba.hip)"""
+    chunks = -(-N // 1024)
+    return chunks, N - 1024 * (chunks - 1)
+
+
+# The rigs of tests/test_gpu_rig_ba_shapes.py, each named for the seam of the pose-only solver it stands on: name -> (cameras,
+# points drawn, points kept, seed of _rig_case, seed of perturbed_start, loss scale or None, rig_robust_ref.dirty data, the
+# small perturbation of test_thirty_two_cameras_with_64_points, walks the loop).  All 1920 x 1080, sigma 0.5 px, dropout 0.3;
+# _rig_case drops the points that fewer than two cameras see, so more are drawn than kept and the first `kept` are the case.
+# PT_THREADS = 256 points make a workgroup of the point kernels, SCHUR_CHUNK = 1024 one of the Schur kernel, 90 rows (16
+# cameras) is the most the Cholesky holds in LDS, rig_init_kernel and rig_finish_kernel have at most 1024 x 256 = 262 144
+# threads for their 3 N and N loops.
+# Seeds that are not the first tried, and why (tests/test_rig_ba_host.py asserts what they are chosen for): 302 and 306 are the
+# first at which points 255 and 256 of the 4-camera rigs, and 1023 and 1024 of the 3-camera ones, are each seen by two free
+# cameras; pose_2049_cauchy has seed 354 AND the small perturbation, see
+# test_rig_ba_host.py::test_shape_loop_cases_are_far_from_every_decision_boundary; from start 405 the fifth iteration of pose_c17 lowers the cost by 1.05 x ftol, too near the stop to compare
+# loops (from 407: 17.6 x and 0.005 x).
+SHAPE_CASES = {
+    "pose_two": (2, 1500, 600, 301, 401, None, False, False, True),
+    "pose_255": (4, 400, 255, 302, 402, None, False, False, False),
+    "pose_256": (4, 400, 256, 302, 402, None, False, False, False),
+    "pose_257": (4, 400, 257, 302, 402, None, False, False, True),
+    "pose_1023": (3, 1600, 1023, 306, 403, None, False, False, False),
+    "pose_1024": (3, 1600, 1024, 306, 403, None, False, False, False),
+    "pose_1025": (3, 1600, 1025, 306, 403, None, False, False, True),
+    "pose_2049_cauchy": (3, 3200, 2049, 354, 404, 2.0, True, True, True),
+    "pose_c17": (17, 330, 300, 305, 407, None, False, False, True),
+    "pose_c17_cauchy": (17, 330, 300, 305, 407, 2.0, False, False, True),
+    "pose_c32_cauchy": (32, 150, 140, 309, 406, 2.0, False, True, True),
+    "pose_stride_3n": (2, 205000, 87382, 307, 407, None, False, False, False),
+    "pose_stride_n": (2, 610000, 262145, 308, 408, None, False, False, False),
+}
+SHAPE_LOOPS = [k for k, v in SHAPE_CASES.items() if v[8]]
+SHAPE_STRIDES = ("pose_stride_3n", "pose_stride_n")  # 2 permutations for the spread, and no loop of the restatement
+# the cases whose LAST point stands on a seam: the first of a second workgroup, or alone in the last Schur chunk, or on the
+# second trip of a grid-stride loop
+SHAPE_SEAMS = ("pose_256", "pose_257", "pose_1024", "pose_1025", "pose_2049_cauchy", "pose_stride_3n", "pose_stride_n")
+
+_shape_cases, _shape_pieces, _shape_loops = {}, {}, {}
+
+
+def shape_case(name):
+    """A case of SHAPE_CASES, computed once: dict with prob (sorted, exactly the N named), R, t, X (the start; camera 0 exactly
+    the world frame), loss_c (None or the Cauchy scale), cpu_s (what making it took)"""
+    if name not in _shape_cases:
+        import time
+        t0 = time.process_time()
+        n_cam, n_draw, n_keep, seed, start_seed, loss_c, dirty, small, _ = SHAPE_CASES[name]
+        c = _rig_case(n_cam, 1920, 1080, n_draw, seed, 0.5)
+        R, t, X = perturbed_start(c, start_seed, **({"rot": 0.003, "trans": 0.005, "point": 0.005} if small else {}))
+        assert c["prob"].N >= n_keep, (name, c["prob"].N)
+        c = {**c, "X": c["X"][:n_keep], "image_points": c["image_points"][:, :n_keep], "valid": c["valid"][:, :n_keep],
+             "prob": first_points(c["prob"], X, n_keep)[0]}
+        X = X[:n_keep]
+        if dirty:
+            import rig_robust_ref
+            c = rig_robust_ref.dirty(c)
+        # the gauge of the definition, which the device imposes on the state it is handed and `lm` on its own: perturbed_start
+        # leaves camera 0 a few 1e-16 off the world frame, and `linearize` would take that as it comes
+        R[0], t[0] = np.eye(3), 0.0
+        _shape_cases[name] = {"prob": c["prob"].sorted(), "R": R, "t": t, "X": X, "loss_c": loss_c, "cpu_s": time.process_time() - t0}
+    return _shape_cases[name]
+
+
+def shape_linearize(prob, R, t, X, lam, loss_c):
+    """linearize, or rig_robust_ref.linearize under a loss"""
+    if loss_c is None:
+        return linearize(prob, R, t, X, lam)
+    import rig_robust_ref
+    return rig_robust_ref.linearize(prob, R, t, X, lam, loss_c)
+
+
+def shape_pieces(name):
+    """(the restatement's cost, gradient, S, rhs of the case's start at lambda = 1e-3 on the sorted problem, their order_spread),
+    computed once: 10 seeded permutations, 2 for SHAPE_STRIDES"""
+    if name not in _shape_pieces:
+        c = shape_case(name)
+        args = (c["R"], c["t"], c["X"], 1e-3)
+        n_perm = 2 if name in SHAPE_STRIDES else 10
+        lin = shape_linearize(c["prob"], *args, c["loss_c"])
+        ref = {k: lin[k] for k in ("cost", "gradient", "S", "rhs")}
+        del lin
+        if c["loss_c"] is None:
+            spread = order_spread(c["prob"], *args, n_perm=n_perm, base=ref)
+        else:
+            import rig_robust_ref
+            spread = rig_robust_ref.order_spread(c["prob"], *args, c["loss_c"], n_perm=n_perm)
+        _shape_pieces[name] = (ref, spread)
+    return _shape_pieces[name]
+
+
+def shape_loop(name):
+    """The restatement's loop at LOOP_FTOL from the case's start (rig_robust_ref.lm's dict under a loss), computed once"""
+    if name not in _shape_loops:
+        c = shape_case(name)
+        if c["loss_c"] is None:
+            _shape_loops[name] = lm(c["prob"], c["R"], c["t"], c["X"], ftol=LOOP_FTOL)
+        else:
+            import rig_robust_ref
+            _shape_loops[name] = rig_robust_ref.lm(c["prob"], c["R"], c["t"], c["X"], c["loss_c"], ftol=LOOP_FTOL)
+    return _shape_loops[name]

@@ -1,6 +1,6 @@
 """Rig bundle adjustment, the part that needs no GPU: the NumPy restatement of the definition (tests/rig_ba_ref.py) against
-central differences, a dense solve and SciPy; the bars of tests/test_gpu_rig_ba.py met by the restatement alone; the host-side
-helpers; the C-ABI surface of the two new entry points; the code-object table of the new kernels."""
+central differences, a dense solve and SciPy; the bars of tests/test_gpu_rig_ba.py met by the restatement alone; the
+conditions the cases of tests/test_gpu_rig_ba_shapes.py must meet; the host-side helpers; the C-ABI surface of the two new entry points; the code-object table of the new kernels."""
 import ctypes
 import importlib.util
 import os
@@ -145,6 +145,132 @@ def test_loop_cases_are_far_from_every_decision_boundary():
         print(name, "rho", out["rho"], "relative decrease", rel)
         assert (np.abs(out["rho"]) >= 1e-3).all() and (np.abs(out["rho"] - 1) < 0.01).all()
         assert ((rel > 1.2 * rb.LOOP_FTOL) | (rel < rb.LOOP_FTOL / 1.2)).all() and out["status"] == rb.STOP_FTOL
+
+
+# ---- the shapes of tests/test_gpu_rig_ba_shapes.py -------------------------------------------------------------------------------
+def test_shape_cases_have_the_shapes_they_are_named_for():
+    """What each case of rig_ba_ref.SHAPE_CASES is there for, restated from its sizes: the workgroups of the point kernels
+    (PT_THREADS = 256, csrc/kernels.h), rig_schur_kernel's chunks and the points of the last one (SCHUR_CHUNK = 1024,
+    csrc/rig_ba.hip), the rows of S against the 90 the Cholesky holds in LDS (CHOL_LDS_ROWS, csrc/rig_lm.h), the 3 N and N of the
+    grid-stride loops against grid_for's 1024 workgroups of 256 threads; every point has 2..C views in ascending camera order;
+    visibility is partial (the Schur kernel finds a camera's W block by counting the mask's bits below it); camera 31 sees
+    points of pose_c32_cauchy.  Prints each case's shape and the CPU time of making it."""
+    source = {}
+    for name in ("rig_ba.hip", "rig_lm.h", "kernels.h"):
+        with open(os.path.join(ROOT, "mocapv2_amd", "csrc", name)) as f:
+            source[name] = f.read()
+    constants = {k: int(v) for text in source.values() for k, v in re.findall(r"constexpr int (PT_THREADS|SCHUR_CHUNK|CHOL_LDS_ROWS) = (\d+);", text)}
+    assert constants == {"PT_THREADS": 256, "SCHUR_CHUNK": 1024, "CHOL_LDS_ROWS": 90}  # what lin_blocks and schur_chunks restate
+    assert "g > 1024 ? 1024 : g" in source["rig_lm.h"] and "grid_for(3 * most)" in source["rig_lm.h"] and "grid_for(3 * a.N)" in source["rig_lm.h"]
+    grid = 1024 * 256
+    want = {  # name: (cameras, points, workgroups of the point kernels, (Schur chunks, points of the last), rows of S)
+        "pose_two": (2, 600, 3, (1, 600), 6),
+        "pose_255": (4, 255, 1, (1, 255), 18), "pose_256": (4, 256, 1, (1, 256), 18), "pose_257": (4, 257, 2, (1, 257), 18),
+        "pose_1023": (3, 1023, 4, (1, 1023), 12), "pose_1024": (3, 1024, 4, (1, 1024), 12), "pose_1025": (3, 1025, 5, (2, 1), 12),
+        "pose_2049_cauchy": (3, 2049, 9, (3, 1), 12),
+        "pose_c17": (17, 300, 2, (1, 300), 96), "pose_c17_cauchy": (17, 300, 2, (1, 300), 96),
+        "pose_c32_cauchy": (32, 140, 1, (1, 140), 186),
+        "pose_stride_3n": (2, 87382, 342, (86, 342), 6), "pose_stride_n": (2, 262145, 1025, (257, 1), 6),
+    }
+    assert set(want) == set(rb.SHAPE_CASES)
+    for name, (n_cam, n, blocks, chunks, rows) in want.items():
+        case = rb.shape_case(name)
+        prob = case["prob"]
+        counts = np.bincount(prob.pt, minlength=prob.N)
+        print(f"{name}: C {prob.C}  N {prob.N}  observations {len(prob.pt)}  views per point {counts.min()} .. {counts.max()}  point workgroups "
+              f"{rb.lin_blocks(prob.N)}  Schur chunks {rb.schur_chunks(prob.N)}  rows of S {prob.D}  loss {case['loss_c']}  CPU {case['cpu_s']:.2f} s")
+        assert (prob.C, prob.N, rb.lin_blocks(prob.N), rb.schur_chunks(prob.N), prob.D) == (n_cam, n, blocks, chunks, rows), name
+        assert case["X"].shape == (n, 3) and (case["loss_c"] == 2.0) == name.endswith("_cauchy"), name
+        off, cam, uv = prob.point_major()
+        assert counts.min() >= 2 and counts.max() <= n_cam and off[-1] == len(cam) == len(prob.pt), name
+        inner = np.ones(len(cam), bool)
+        inner[off[:-1]] = False
+        assert (np.diff(cam, prepend=-1)[inner] > 0).all() and np.array_equal(prob.pt, np.repeat(np.arange(n), counts)), name
+        if n_cam > 2:
+            # partial visibility (the 30 % dropout): most points miss a camera, and which ones they miss differs
+            assert (counts < n_cam).mean() > 0.5 and len({tuple(cam[off[i]:off[i + 1]]) for i in range(n)}) >= 4, name
+        assert np.array_equal(case["R"][0], np.eye(3)) and not case["t"][0].any(), name  # the gauge, to the bit
+        assert rb.cost_of(prob, case["R"], case["t"], case["X"])[1], name
+    D = {name: rb.shape_case(name)["prob"].D for name in want}
+    assert D["pose_c17"] == 96 > constants["CHOL_LDS_ROWS"] >= 6 * (16 - 1) and 16 * 17 // 2 == 136 and 31 * 32 // 2 == 496
+    rig = rb.shape_case("pose_c32_cauchy")["prob"]
+    assert np.bincount(rig.cam, minlength=32)[31] >= 1
+    assert 3 * 87382 == grid + 2 and 3 * 87381 < grid and 262145 == grid + 1  # a second trip of two elements, and of one point
+
+
+@pytest.mark.parametrize("name", rb.SHAPE_SEAMS)
+def test_a_seam_cases_last_point_cannot_be_lost_unseen(name):
+    """The last point of every case that ends on a seam (the first point of a second workgroup, the one point of a last Schur
+    chunk, the point of a second trip) is seen by at least two free cameras (index >= 1), so that it lands in an off-diagonal
+    block of the Schur complement too; with two cameras there is one free camera and one block, and the point is in it.  And
+    the restatement without that point differs from the full one in S and in rhs by more than 100 x what
+    tests/test_gpu_rig_ba_shapes.py allows (8 x the order spread): a kernel that drops it fails there.  pose_256 and pose_1024
+    end just before the seam: their last point is the one a `<` for a `<=` would lose.
+    The seeds of the 4-camera and 3-camera families (302, 306) are the first at which points 255 and 256, and 1023 and 1024,
+    all have two free cameras.
+    Measured (S, rhs: without the last point / allowed): printed; the smallest factor is pose_stride_n's."""
+    import time
+    t0 = time.process_time()
+    case = rb.shape_case(name)
+    prob, R, t, X, loss_c = (case[k] for k in ("prob", "R", "t", "X", "loss_c"))
+    last = prob.cam[prob.pt == prob.N - 1]
+    assert (last >= 1).sum() >= min(2, prob.C - 1), last
+    ref, spread = rb.shape_pieces(name)
+    less, X_less = rb.first_points(prob, X, prob.N - 1)
+    lost = rb.shape_linearize(less, R, t, X_less, 1e-3, loss_c)
+    for k in ("S", "rhs"):
+        d = float(np.abs(ref[k] - lost[k]).max() / np.abs(ref[k]).max())
+        print(f"{name} {k}: without the last point {d:.3e}  allowed {8 * spread[k]:.3e}  factor {d / (8 * spread[k]):.3g}")
+        assert d > 100 * 8 * spread[k], k
+    print(f"{name}: last point's cameras {last}  CPU {time.process_time() - t0:.1f} s")
+
+
+@pytest.mark.parametrize("name", rb.SHAPE_LOOPS)
+def test_shape_loop_cases_are_far_from_every_decision_boundary(name):
+    """The two conditions tests/test_gpu_rig_ba.py's loop test rests on, for the cases tests/test_gpu_rig_ba_shapes.py walks
+    beside the restatement: no iteration at LOOP_FTOL has |rho| < 1e-3 (none is a failed solve either), and the damped S of the
+    start has a condition number below 1e6.  More than that: the stop is ftol's, no relative decrease lies within a factor 1.2
+    of ftol, and the restatement walks the same loop on two seeded permutations of the observations with every step length
+    within 2.5e-7 of the sorted problem's: a quarter of the 1e-6 the device is held to, so that the restatement's own
+    dependence on the order of its sums leaves three quarters of that bar to the device.
+    That last condition is what pose_2049_cauchy needed another seed AND the small perturbation for.  The damping falls by 3
+    with every accepted step, the cost does not depend on the rig's scale, so at a small lambda S is singular along the scale
+    gauge to working precision, and the component of a step along it, which the cost does not see, is rounding: cond(S) < 1e6
+    at lambda = 1e-3 says nothing about iteration 19.  With rig_robust_ref.dirty's outliers on three cameras the loop under
+    the loss is slow (a point of three views that carries two outliers hangs on one good view).  From the default
+    perturbation, of the seeds 300 .. 399 none stops on ftol in fewer than 17 iterations, half end in failed solves
+    (at 1e-3 / 3^26 numpy's Cholesky gives up), and the first tried that stops on ftol with all other conditions met (318, 19
+    iterations, lambda 8.6e-13 at the end) has step lengths that differ by 3.6e-4 between two orders of the restatement's own
+    sums -- and by 3.9e-4 between the MI355X and the restatement, with every other figure of the loop test inside its bar
+    (cost 1.0e-14, returned state 6.9e-14 of what it moved).  From the small perturbation four seeds of 300 .. 399 stop within 13
+    iterations; of the two whose last point two free cameras see, 354 has the wider margins (2.8 x and 0.68 x ftol, 4.6e-8
+    between orders; 321: 1.4 x, 0.46 x, 1.5e-7).
+    Measured (iterations, smallest |rho|, the two relative decreases nearest ftol as multiples of it, cond(S), step lengths
+    between orders): printed per case."""
+    import time
+    import rig_robust_ref as rr
+    t0 = time.process_time()
+    case, ref = rb.shape_case(name), rb.shape_loop(name)
+    prob, start, loss_c = case["prob"], (case["R"], case["t"], case["X"]), case["loss_c"]
+    lin = rb.shape_linearize(prob, *start, 1e-3, loss_c)
+    cond = np.linalg.cond(lin["S"])
+    costs = np.r_[ref["cost_initial"], ref["history"][:, 0]]
+    ok = ref["history"][:, 2] > 0
+    rel = ((costs[:-1] - costs[1:]) / costs[:-1])[ok]
+    between = 0.0
+    for seed in (1000, 1001):
+        p = rb.permuted(prob, seed)
+        other = rb.lm(p, *start, ftol=rb.LOOP_FTOL) if loss_c is None else rr.lm(p, *start, loss_c, ftol=rb.LOOP_FTOL)
+        assert other["iterations"] == ref["iterations"] and np.array_equal(other["history"][:, 2], ref["history"][:, 2]), seed
+        between = max(between, float(np.abs(other["history"][:, 3] / ref["history"][:, 3] - 1).max()))
+    print(f"{name}: {ref['iterations']} iterations, status {ref['status']}, accepted {int(ok.sum())}, smallest |rho| {np.abs(ref['rho']).min():.3g}, "
+          f"relative decreases nearest ftol {rel[np.argsort(np.abs(np.log(rel / rb.LOOP_FTOL)))[:2]] / rb.LOOP_FTOL} x ftol, cond(S) {cond:.3e}, "
+          f"step lengths between orders {between:.1e}, CPU {time.process_time() - t0:.1f} s")
+    assert ref["status"] == rb.STOP_FTOL and ref["iterations"] < 50
+    assert np.isfinite(ref["rho"]).all() and (np.abs(ref["rho"]) >= 1e-3).all()
+    assert ((rel >= 1.2 * rb.LOOP_FTOL) | (rel <= rb.LOOP_FTOL / 1.2)).all()
+    assert cond < 1e6
+    assert between <= 2.5e-7
 
 
 def aligned_errors(scene, X_true, R, t):
