@@ -90,7 +90,18 @@ SIGNATURES = {
     "mocap_profile_read": [_vp, _dp, _ip],
 }
 
+# libmocap_learn.so (include/mocap_learn.h): a library of its own, bound apart from the table above
+LEARN_LIB_PATH = os.path.join(_HERE, "libmocap_learn.so")
+LEARN_ABI_VERSION = 1
+LEARN_SIGNATURES = {
+    "mocap_learn_abi_version": [],
+    "mocap_learn_last_error": [],
+    "mocap_learn_marker_pair_stats": [_i, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp],
+    "mocap_learn_rigid_bodies": [_i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+}
+
 _lib = None
+_learn = None
 
 
 def load():
@@ -117,6 +128,32 @@ def load():
         raise RuntimeError(f"libmocap_hip ABI {lib.mocap_abi_version()} != expected {ABI_VERSION}")
     _lib = lib
     return lib
+
+
+def load_learn():
+    """Load libmocap_learn.so; raises if it was not built (the same `make` builds both libraries)."""
+    global _learn
+    if _learn is not None:
+        return _learn
+    if not os.path.exists(LEARN_LIB_PATH):
+        raise RuntimeError(f"{LEARN_LIB_PATH} is missing: build it with `make -C mocapv2_amd/csrc` "
+                           "(hipcc --offload-arch=gfx950); there is no CPU fallback")
+    load()  # torch's HIP runtime first, as for the main library
+    lib = C.CDLL(LEARN_LIB_PATH)
+    for name, args in LEARN_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.argtypes = args
+        fn.restype = C.c_char_p if name == "mocap_learn_last_error" else C.c_int
+    if lib.mocap_learn_abi_version() != LEARN_ABI_VERSION:
+        raise RuntimeError(f"libmocap_learn ABI {lib.mocap_learn_abi_version()} != expected {LEARN_ABI_VERSION}")
+    _learn = lib
+    return lib
+
+
+def check_learn(rc):
+    if rc != 0:
+        msg = load_learn().mocap_learn_last_error()
+        raise MocapError(rc, msg.decode() if msg else "")
 
 
 def check(rc):

@@ -636,6 +636,70 @@ struct RigidArgs {
 };
 void launch_rigid_poses(const RigidArgs& a, hipStream_t s);
 
+// rigid-body models learned from a tracked capture (rigid_learn.hip).  The codes and caps are
+// include/mocap_hip.h's MOCAP_LEARN_*.  Every sum over time is formed per chunk of LEARN_CHUNK steps, in ascending t from 0, and
+// the chunks' partial sums are added in ascending chunk: the partials live in the caller's workspace, cut up by LearnWork.
+enum { LEARN_ERR_MEMBERS = -2, LEARN_ERR_INCOMPLETE = -3 };
+constexpr int LEARN_CHUNK = 32;
+constexpr int LEARN_MAX_IDS = 64;      // identities of one mocap_learn_marker_pair_stats
+constexpr int LEARN_MAX_GROUPS = 16;   // groups of one mocap_learn_rigid_bodies
+constexpr int LEARN_MAX_WANTED = LEARN_MAX_GROUPS * RIGID_MAX_MARKERS; // identities either call locates per step
+struct LearnWanted { int32_t id[LEARN_MAX_WANTED]; }; // travels by value in the kernel arguments; -1 = a column nobody wants
+// the caller's workspace (MOCAP_LEARN_WORK_BYTES): doubles first, then the integers, each array whole
+struct LearnWork {
+    double *pmin, *pmax, *psum, *psum2; // pair stats: [chunks][P] each, P = K (K + 1) / 2 pairs a <= b
+    double *model;                      // rigid learn: [G][8][3] the current model
+    double *gsum;                       // [chunks][G][8][3] a pass's partial sums (b per axis; the squared residual in [..][0])
+    int32_t *pcnt;                      // [chunks][P]
+    int32_t *row;                       // [T][W] the row of each wanted identity in each step, -1 = absent
+    int32_t *gcnt;                      // [chunks][G][8] additions per member
+    int32_t *gused;                     // [chunks][G] used steps
+    int32_t *gstate;                    // [G][2] ref_step, status
+    size_t bytes;
+    LearnWork() = default;
+    // T steps, K identities of the pair statistics (0: none), G groups (0: none); base may be null (only `bytes` counts)
+    LearnWork(void* base, long long T, int K, int G)
+    {
+        const size_t C = (size_t)((T + LEARN_CHUNK - 1) / LEARN_CHUNK), P = (size_t)K * (K + 1) / 2, W = (size_t)K + 8 * (size_t)G;
+        double* d = (double*)base;
+        pmin = d; pmax = pmin + C * P; psum = pmax + C * P; psum2 = psum + C * P;
+        model = psum2 + C * P; gsum = model + 24 * (size_t)G;
+        int32_t* i = (int32_t*)(gsum + C * G * 24);
+        pcnt = i; row = pcnt + C * P; gcnt = row + (size_t)T * W; gused = gcnt + C * G * 8; gstate = gused + C * G;
+        bytes = (size_t)((char*)(gstate + 2 * (size_t)G) - (char*)base);
+    }
+};
+struct PairArgs {
+    const double* xyz;         // [T][Q][3]
+    const int32_t* n;          // [T]; < 0 or > Q: a blind step
+    const int32_t* id;         // [T][Q] identities, -1 = none
+    int T, Q, K;
+    LearnWanted ids;           // [K] strictly ascending, >= 0 (the host checked)
+    LearnWork w;
+    int32_t* count;            // [K][K] outputs
+    double *dmin, *dmax, *dsum, *dsum2;
+};
+void launch_marker_pair_stats(const PairArgs& a, hipStream_t s);
+struct LearnArgs {
+    const double* xyz;
+    const int32_t* n;
+    const int32_t* id;
+    int T, Q, G;
+    LearnWanted members;       // [G][8]; -1 from n_members on and in every slot of a group that is not valid
+    int32_t n_members[LEARN_MAX_GROUPS];
+    uint32_t valid;            // bit g: the group's members are 3..8 distinct identities >= 0, at least min_present of them
+    int rounds, min_present;
+    LearnWork w;
+    double* model;             // [G][8][3]
+    double* rms;               // [G]
+    double* member_rms;        // [G][8]
+    int32_t* member_count;     // [G][8]
+    int32_t* steps_used;       // [G]
+    int32_t* ref_step;         // [G]
+    int32_t* status;           // [G]
+};
+void launch_rigid_learn(const LearnArgs& a, hipStream_t s);
+
 // sub-pixel centroids from the frames (subpixel.hip): the flag bits are include/mocap_hip.h's MOCAP_SUBPIX_*
 enum { SUBPIX_EMPTY = 1, SUBPIX_EDGE = 2, SUBPIX_NEIGHBOUR = 4, SUBPIX_MOVING = 8, SUBPIX_CUT = 16 };
 constexpr int SUBPIX_MAX_BLOBS = 256; // centroids of one image at most: one per thread of its workgroup

@@ -20,8 +20,10 @@ from .engine_blob import (GRAY_SHIFT, MAX_BLOBS, REC_INTS, SUBPIX_COORDS, SUBPIX
 from .engine_calib import RIG_LOSSES, CalibStage  # noqa: F401
 from .engine_comm import CommStage, comm_available, comm_unique_id  # noqa: F401
 from .engine_geom import BAProblem, GeomStage  # noqa: F401
-from .engine_track import (RIGID_E_BLIND, RIGID_E_CAPACITY, RIGID_E_HYP, RIGID_E_MODEL, RIGID_LOST, RIGID_MAX_BODIES,  # noqa: F401
-                           RIGID_MAX_DETECTIONS, RIGID_MAX_HYP, RIGID_MAX_MARKERS, RIGID_MAX_TRIPLES, TrackStage, rigid_tables)
+from .engine_track import (LEARN_CHUNK, LEARN_E_INCOMPLETE, LEARN_E_MEMBERS, LEARN_MAX_GROUPS, LEARN_MAX_IDS,  # noqa: F401
+                           RIGID_E_BLIND, RIGID_E_CAPACITY, RIGID_E_HYP, RIGID_E_MODEL, RIGID_LOST, RIGID_MAX_BODIES,
+                           RIGID_MAX_DETECTIONS, RIGID_MAX_HYP, RIGID_MAX_MARKERS, RIGID_MAX_TRIPLES, TrackStage, learn_work_bytes,
+                           rigid_groups, rigid_tables)
 
 
 class MocapContext(BlobStage, GeomStage, CalibStage, TrackStage, CommStage):

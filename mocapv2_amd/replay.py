@@ -201,6 +201,25 @@ class ReplayTracker:
                 send_many(res["messages"])
             yield res
 
+    def learn_bodies(self, frames, *, spread, min_steps, **kw):
+        """Rigid-body models learned from a take (MocapContext.learn_rigid_bodies, whose keywords `kw` are): the frames run
+        through the tracker, which must have been built with `track`; per batch the marker rows that `track` read, their counts
+        and their identities are kept on the device, for the real time steps only -- the black frames that pad the last batch
+        are not included -- and the whole take is handed over at once.  Returns learn_rigid_bodies' dict: its `models` are ready
+        for bodies={"models": ...}.  Use a tracker that has seen nothing else: the identities continue from its state."""
+        if not self.tracked:
+            raise ValueError("learn_bodies needs the marker identities: build the tracker with track={'gate': ...}")
+        xyz, n, ids = [], [], []
+        for b0, nb, out in self._submit(frames):
+            self.tracker.finish(out, first_step=b0)  # raises CapacityError: no model is learned from shortened lists
+            xyz.append(self.tracker._marker_rows(out)[:nb].clone())
+            n.append(out["n"][:nb].clone())
+            ids.append(out["id"][:nb].clone())
+        if not xyz:
+            raise ValueError("learn_bodies: the take has no frames")
+        return self.tracker.ctx.learn_rigid_bodies(torch.cat(xyz).contiguous(), torch.cat(n).contiguous(), torch.cat(ids).contiguous(),
+                                                   spread=spread, min_steps=min_steps, **kw)
+
     def run(self, frames, send=None):
         """Generator over time steps.  frames: uint8 [T, C, H, W] NumPy array or torch tensor (host or device).
         Yields dicts: object_points [<= obj_count+1, 3] (or shape (0,)), image_points [roots, C, 2] (or (0,)),
